@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """DCANet cost-volume hot path benchmark on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--mode fwdbwd|fwd] [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--mode fwdbwd|fwd] [--batch B] [--full] [--dump-outputs DIR]
 
 Per-GPU batch (weak scaling): 4 stereo pairs for the training step -- BASELINE.json configs[2] "fwd+bwd, batch=4" and
 configs[3] "8 GPUs, batch=32" -- and 1 for the eval forward (configs[1]); `value` counts cost volumes, not steps.
@@ -16,9 +16,11 @@ One *step* = one pass of the hot path over one batch of synthetic SceneFlow-test
       Adam step (main_dca.py:64).
   fwd: eval-mode forward only (BASELINE config[1]), BN folded into the conv epilogues.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-measured live with HIP events on the launch stream) and `cpu_baseline` (the CPU oracle on the host cores,
-rank 0 / N=1 only, on a bounded sample).
+Prints ONE JSON line on rank 0: the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`
+over the K timed steps) and the whole path against its rooflines (`path_roofline`, from the timed steps).  --full adds
+what takes runs of its own: `roofline` (dominant kernel, measured live with HIP events on the launch stream) and
+`cpu_baseline` (the CPU oracle on the host cores, rank 0 / N=1 only, on a bounded sample).  --dump-outputs DIR writes
+what the last timed step computed as DIR/<name>.npy (rank 0), bit for bit the same in two runs with equal arguments.
 """
 import argparse
 import copy
@@ -73,8 +75,9 @@ def _conv_x3():
     return ops.CONV_X3
 
 
-def train_local(m, fL, fR, guid, gt, bucket):
-    """this rank's part of the step: forward (all heads), losses, backward, gradients gathered into the flat bucket"""
+def train_local(m, fL, fR, guid, gt, bucket, keep=None):
+    """this rank's part of the step: forward (all heads), losses, backward, gradients gathered into the flat bucket.
+    `keep` (a dict, --dump-outputs) receives the step's predictions and loss."""
     from dcanet_amd.models.loss import focal_loss, model_loss
     bucket.zero()
     fL.grad = fR.grad = None
@@ -85,20 +88,43 @@ def train_local(m, fL, fR, guid, gt, bucket):
         + model_loss([r["pred_dca3"], pred4], gt, mask)
     loss.backward()
     bucket.gather()
+    if keep is not None:
+        keep.update(r, pred4=pred4, loss=loss)
     return loss.detach()
 
 
-def train_step(m, fL, fR, guid, gt, bucket, opt):
-    loss = train_local(m, fL, fR, guid, gt, bucket)
+def train_step(m, fL, fR, guid, gt, bucket, opt, keep=None):
+    loss = train_local(m, fL, fR, guid, gt, bucket, keep)
     bucket.reduce_flat()
     opt.step()
     return loss
 
 
-def eval_step(m, fL, fR, guid):
+def eval_step(m, fL, fR, guid, keep=None):
     with torch.no_grad():
         r = m.hot_path(fL, fR)
-        return m.prop(guid, r["pred4_q"])
+        pred4 = m.prop(guid, r["pred4_q"])
+    if keep is not None:
+        keep.update(r, pred4=pred4)
+    return pred4
+
+
+DUMP_MAX_NUMEL = 1 << 20     # per array; at most 14 arrays per step -> < 56 MB of float32
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array.  An array of more than DUMP_MAX_NUMEL elements is written as
+    the flat sample x.reshape(-1)[idx], idx = DUMP_MAX_NUMEL sorted indices drawn with a generator seeded by 0, so two
+    runs with the same arguments sample the same elements."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_NUMEL:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(t.numel(), (DUMP_MAX_NUMEL,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.float().cpu().numpy())
 
 
 
@@ -365,8 +391,16 @@ def main():
                     help="f32 (default, the headline: fp32 storage, fp32-grade arithmetic) or the reduced-precision INFERENCE "
                          "path of BASELINE configs 2 / 5 (2-byte storage of the 1/4-res tensors, one MFMA product per "
                          "multiply, fp32 accumulation; --mode fwd only, EPE-gated in tests/test_gpu_lowprec.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the per-kernel rooflines (`roofline`, `roofline_other`, with the "
+                         "PMC traffic committed under profiles/) and the CPU oracle (`cpu_baseline`, `vs_cpu_baseline`); "
+                         "off by default: a plain run times the steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle")
     ap.add_argument("--cpu-rows", type=int, default=16)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (predictions, loss, gradients, updated parameters) as "
+                         "float32 DIR/<name>.npy; the inputs and weights are seeded and MIOpen runs in its deterministic "
+                         "mode, so two runs with equal arguments agree bit for bit (the step is ~5 %% slower: time plain runs)")
     ap.add_argument("--no-prepack", action="store_true", help="fwdbwd mode: re-lay-out each weight in its own launch")
     ap.add_argument("--graph", action="store_true",
                     help="replay the eval hot path (fwd) / the whole training step (fwdbwd, dcanet_amd.graph."
@@ -397,17 +431,23 @@ def main():
         raise SystemExit("bench.py needs an MI355X (no CPU fallback for the hot path)")
     device = torch.device("cuda", local % torch.cuda.device_count())
     torch.cuda.set_device(device)
+    if args.dump_outputs:
+        # The only non-HIP kernels of the step are MIOpen's, for the two 2D convolutions of the convex up-sampler (m.prop).
+        # Their weight gradients vary at the 1e-9 level from run to run, and Adam (which scales noise-level gradients to
+        # lr-sized steps) makes that visible in every output after a few dozen steps.  Deterministic mode fixes it.
+        torch.backends.cudnn.deterministic = True
 
     m = build_model(device)
     fL, fR, guid, gt = make_inputs(args.batch, rank, device)
     train_graphed, graph_error, prepack_n = False, None, 0
+    keep = {} if args.dump_outputs else None      # the step's outputs, overwritten by every step
     if args.mode == "fwdbwd":
         m.train()
         fL.requires_grad_(); fR.requires_grad_()
         params = hot_params(m)
         bucket = FlatGradBucket(params)
         opt = torch.optim.Adam(params, lr=1e-3, betas=(0.9, 0.999), capturable=bool(args.graph))
-        step = lambda: train_step(m, fL, fR, guid, gt, bucket, opt)
+        step = lambda: train_step(m, fL, fR, guid, gt, bucket, opt, keep)
         if not args.graph and not args.no_prepack:
             # all weight re-layouts of a step (forward + backward-data images of every conv) as ONE launch right after
             # the optimizer update instead of ~130 five-microsecond launches (ops.PrepackPlan)
@@ -420,7 +460,7 @@ def main():
 
             def step():
                 with plan.active():
-                    loss = train_step(m, fL, fR, guid, gt, bucket, opt)
+                    loss = train_step(m, fL, fR, guid, gt, bucket, opt, keep)
                 plan.refresh()
                 return loss
             prepack_n = plan.n
@@ -428,13 +468,13 @@ def main():
             # the whole step as hipGraph replays (dcanet_amd.graph.GraphedTrainStep); any capture problem -> eager
             try:
                 from dcanet_amd.graph import GraphedTrainStep
-                step = GraphedTrainStep(lambda: train_local(m, fL, fR, guid, gt, bucket), opt.step,
+                step = GraphedTrainStep(lambda: train_local(m, fL, fR, guid, gt, bucket, keep), opt.step,
                                         bucket.reduce_flat if world > 1 else None)
                 train_graphed = True
             except Exception as e:   # noqa: BLE001
                 graph_error = f"{type(e).__name__}: {e}"[:200]
                 torch.cuda.synchronize()
-                step = lambda: train_step(m, fL, fR, guid, gt, bucket, opt)
+                step = lambda: train_step(m, fL, fR, guid, gt, bucket, opt, keep)
     else:
         m.eval()
         if args.graph:
@@ -443,9 +483,13 @@ def main():
 
             def step():
                 with torch.no_grad():
-                    return m.prop(guid, graphed(fL, fR)["pred4_q"])
+                    r = graphed(fL, fR)
+                    pred4 = m.prop(guid, r["pred4_q"])
+                if keep is not None:
+                    keep.update(r, pred4=pred4)
+                return pred4
         else:
-            step = lambda: eval_step(m, fL, fR, guid)
+            step = lambda: eval_step(m, fL, fR, guid, keep)
 
     import contextlib
     frozen = contextlib.ExitStack()
@@ -482,6 +526,11 @@ def main():
         dist.all_gather(every, mine)
         rank_ms = [float(v.item()) / args.steps * 1e3 for v in every]
         dt = max(rank_ms) * args.steps / 1e3           # the job's time is its slowest rank's
+    if keep is not None and rank == 0:
+        if args.mode == "fwdbwd":
+            keep.update(grad_fL=fL.grad, grad_fR=fR.grad, param_grads=bucket.flat,
+                        params=torch.cat([p.detach().reshape(-1) for p in params]))
+        dump_outputs(args.dump_outputs, keep)
 
     if rank == 0:
         volumes = args.steps * args.batch * world
@@ -525,11 +574,11 @@ def main():
                        (f"every step, {prepack_n} layouts in one launch (ops.PrepackPlan)" if prepack_n else
                         "every step, one launch per layout")},
         }
-        roof = kernel_roofline(device, args.dtype) if not args.shape else {}
+        roof = kernel_roofline(device, args.dtype) if args.full and not args.shape else {}
         names = list(roof)
         # HBM bytes per launch from the PMC passes committed under profiles/ (cannot be collected inside this run)
         try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_FILE)))
+            pmc = json.load(open(os.path.join(ROOT, "profiles", PMC_FILE))) if names else {}
             for n in names:
                 key = roof[n].pop("pmc_key", None)
                 if key in pmc:
@@ -549,7 +598,7 @@ def main():
         if names:
             line["roofline"] = dict(roof[names[0]], kernel=names[0])
             line["roofline_other"] = {n: roof[n] for n in names[1:]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(m, args.mode, args.cpu_rows)
             # `vs_baseline` stays null (BASELINE.md publishes no number for this metric); the ratio to the CPU oracle timed
             # beside it is reported under its own name -- a large ratio says nothing about kernel quality, `roofline.frac` does
