@@ -10,11 +10,8 @@
 // contiguous bytes per channel).  MFMA column tile j is the voxel set {4r + j}: the lane's B fragment for tile j is the
 // 8 channels of its own voxel 4r + j, assembled from the loaded words with four v_perm -- no LDS.  The results of the
 // four tiles give, per output channel, the lane's four voxels again: one 8-byte (or 16-byte fp32) store per channel.
-#include "dca_common.h"
+#include "dca_frag.h"
 #include "../../include/dca_hip.h"
-
-typedef __bf16 c1_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 c1_f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -32,31 +29,6 @@ struct C1LpArgs {
   long S;
 };
 
-template <typename MT> struct C1;
-template <> struct C1<__bf16> {
-  typedef c1_bf16x8 vec8;
-  static __device__ __forceinline__ f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct C1<_Float16> {
-  typedef c1_f16x8 vec8;
-  static __device__ __forceinline__ f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-template <typename MT> __device__ __forceinline__ unsigned c1_pack2(float a, float b) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef MT mtx2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, mtx2));
-}
-template <typename MT> __device__ __forceinline__ float c1_lo(unsigned w) {
-  return (float)__builtin_bit_cast(MT, (unsigned short)(w & 0xffffu));
-}
-template <typename MT> __device__ __forceinline__ float c1_hi(unsigned w) {
-  return (float)__builtin_bit_cast(MT, (unsigned short)(w >> 16));
-}
 
 constexpr int MAXCH = 8;   // 16-channel chunks over both inputs (Cin <= 128)
 
@@ -68,7 +40,7 @@ constexpr int MAXCH = 8;   // 16-channel chunks over both inputs (Cin <= 128)
 #endif
 template <typename MT, bool OUT32>
 __global__ __launch_bounds__(256, C1_OCC) void conv1_lp_kernel(C1LpArgs a) {
-  typedef typename C1<MT>::vec8 vec8;
+  typedef typename Lp<MT>::vec8 vec8;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l31 = lane & 31, half = lane >> 5;
   const int nch = a.NCH1 + a.NCH2;
   vec8 wf[MAXCH];
@@ -113,7 +85,7 @@ __global__ __launch_bounds__(256, C1_OCC) void conv1_lp_kernel(C1LpArgs a) {
           f.y = __builtin_amdgcn_perm(t < 2 ? q[3].x : q[3].y, t < 2 ? q[2].x : q[2].y, sel);
           f.z = __builtin_amdgcn_perm(t < 2 ? q[5].x : q[5].y, t < 2 ? q[4].x : q[4].y, sel);
           f.w = __builtin_amdgcn_perm(t < 2 ? q[7].x : q[7].y, t < 2 ? q[6].x : q[6].y, sel);
-          acc[t] = C1<MT>::mfma(wf[c], __builtin_bit_cast(vec8, f), acc[t]);
+          acc[t] = Lp<MT>::mfma(wf[c], __builtin_bit_cast(vec8, f), acc[t]);
         }
       }
     }
@@ -139,7 +111,7 @@ __global__ __launch_bounds__(256, C1_OCC) void conv1_lp_kernel(C1LpArgs a) {
             rp[q][0] = __uint_as_float(w.x); rp[q][1] = __uint_as_float(w.y); rp[q][2] = __uint_as_float(w.z); rp[q][3] = __uint_as_float(w.w);
           } else {
             const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(pr, off, 0, 0);
-            rp[q][0] = c1_lo<MT>(w.x); rp[q][1] = c1_hi<MT>(w.x); rp[q][2] = c1_lo<MT>(w.y); rp[q][3] = c1_hi<MT>(w.y);
+            rp[q][0] = lp_lo<MT>(w.x); rp[q][1] = lp_hi<MT>(w.x); rp[q][2] = lp_lo<MT>(w.y); rp[q][3] = lp_hi<MT>(w.y);
           }
         }
       }
@@ -152,7 +124,7 @@ __global__ __launch_bounds__(256, C1_OCC) void conv1_lp_kernel(C1LpArgs a) {
             rq[q][0] = __uint_as_float(w.x); rq[q][1] = __uint_as_float(w.y); rq[q][2] = __uint_as_float(w.z); rq[q][3] = __uint_as_float(w.w);
           } else {
             const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(qr, off, 0, 0);
-            rq[q][0] = c1_lo<MT>(w.x); rq[q][1] = c1_hi<MT>(w.x); rq[q][2] = c1_lo<MT>(w.y); rq[q][3] = c1_hi<MT>(w.y);
+            rq[q][0] = lp_lo<MT>(w.x); rq[q][1] = lp_hi<MT>(w.x); rq[q][2] = lp_lo<MT>(w.y); rq[q][3] = lp_hi<MT>(w.y);
           }
         }
       }
@@ -166,7 +138,7 @@ __global__ __launch_bounds__(256, C1_OCC) void conv1_lp_kernel(C1LpArgs a) {
           const u32x4 w = {__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3])};
           __builtin_amdgcn_raw_buffer_store_b128(w, yr, off, 0, 0);
         } else {
-          const u32x2 w = {c1_pack2<MT>(o[0], o[1]), c1_pack2<MT>(o[2], o[3])};
+          const u32x2 w = {lp_pack2<MT>(o[0], o[1]), lp_pack2<MT>(o[2], o[3])};
           __builtin_amdgcn_raw_buffer_store_b64(w, yr, off, 0, 0);
         }
       }

@@ -16,11 +16,9 @@
 // the four voxels 4r..4r+3 as one 16-byte load.  MFMA column tile t is the voxel set {4r + t}: the lane's B fragment of
 // a term is the 8 channels of its own voxel 4r + t -- four dwords, each the packed pair (channel 2j, 2j+1) -- built in
 // registers.  Per output channel the four tiles give the lane's four voxels again: one 16-byte store.
-#include "dca_common.h"
+#include "dca_frag.h"
 #include "bn_fused_stats.h"
 #include "../../include/dca_hip.h"
-
-typedef __bf16 cx_bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -38,13 +36,6 @@ struct C1XArgs {
   long S;
   double* stat_part;         // STATS: one partial {K, n, s, q} per (channel of CoutTotal, workgroup): bn_fused_stats.h
 };
-
-__device__ __forceinline__ unsigned cx_pack2(float a, float b) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bfx2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bfx2));
-}
 
 // NC1 / NC2: 16-channel chunks of the first / second input (C1 = 16 * NC1 exactly; S % 4 == 0, aligned bases).
 // STATS: the output feeds a training-mode BatchNorm; the kernel also emits the per-(channel, workgroup) partial statistics
@@ -66,11 +57,11 @@ __global__ __launch_bounds__(256, 2) void conv1_x3_kernel(C1XArgs a) {
     aff[threadIdx.x] = has_aff ? (threadIdx.x < 32 ? a.scale[a.co_off + co] : a.shift[a.co_off + co])
                                : (threadIdx.x < 32 ? 1.f : 0.f);
   }
-  cx_bf16x8 wf[NCH][3];
+  bf16x8 wf[NCH][3];
 #pragma unroll
   for (int c = 0; c < NCH; ++c)
 #pragma unroll
-    for (int t = 0; t < 3; ++t) wf[c][t] = *(const cx_bf16x8*)(a.wfrag + (((long)c * 3 + t) * 64 + lane) * 8);
+    for (int t = 0; t < 3; ++t) wf[c][t] = *(const bf16x8*)(a.wfrag + (((long)c * 3 + t) * 64 + lane) * 8);
   __syncthreads();
 
   constexpr bool LANE_ACC = STATS && NCH <= 2;   // the 64-channel forms have no 32 registers to spare
@@ -105,14 +96,14 @@ __global__ __launch_bounds__(256, 2) void conv1_x3_kernel(C1XArgs a) {
         for (int j = 0; j < 4; ++j) {
           const float va = t == 0 ? q[2 * j].x : (t == 1 ? q[2 * j].y : (t == 2 ? q[2 * j].z : q[2 * j].w));
           const float vb = t == 0 ? q[2 * j + 1].x : (t == 1 ? q[2 * j + 1].y : (t == 2 ? q[2 * j + 1].z : q[2 * j + 1].w));
-          const unsigned h2 = cx_pack2(va, vb);
+          const unsigned h2 = lp_pack2<__bf16>(va, vb);
           const float ra = va - __uint_as_float(h2 << 16), rb = vb - __uint_as_float(h2 & 0xffff0000u);      // exact
-          const unsigned m2 = cx_pack2(ra, rb);
-          const unsigned l2 = cx_pack2(ra - __uint_as_float(m2 << 16), rb - __uint_as_float(m2 & 0xffff0000u));
+          const unsigned m2 = lp_pack2<__bf16>(ra, rb);
+          const unsigned l2 = lp_pack2<__bf16>(ra - __uint_as_float(m2 << 16), rb - __uint_as_float(m2 & 0xffff0000u));
           H[j] = h2; M[j] = m2; L[j] = l2;
         }
-        const cx_bf16x8 bh = __builtin_bit_cast(cx_bf16x8, H), bm = __builtin_bit_cast(cx_bf16x8, M),
-                        bl = __builtin_bit_cast(cx_bf16x8, L);
+        const bf16x8 bh = __builtin_bit_cast(bf16x8, H), bm = __builtin_bit_cast(bf16x8, M),
+                        bl = __builtin_bit_cast(bf16x8, L);
         // smallest terms first (as conv3d_bf16x3.hip): w_h x_l, w_l x_h, w_m x_m, w_h x_m, w_m x_h, w_h x_h
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[c][0], bl, acc[t], 0, 0, 0);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[c][2], bh, acc[t], 0, 0, 0);
@@ -203,28 +194,11 @@ __global__ __launch_bounds__(256, 2) void conv1_x3_kernel(C1XArgs a) {
   }
 }
 
-__device__ __forceinline__ void cx_split3(float v, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)v;
-  const float r1 = v - (float)h;
-  m = (__bf16)r1;
-  const float r2 = r1 - (float)m;
-  l = (__bf16)r2;
-}
-
-// wfrag[chunk][term][lane][j] = term of W[b = lane & 31][a = chunk*16 + 8*(lane >> 5) + j], W[b][a] = src_ab ?
-// w[a*Btotal + b_off + b] : w[(b_off + b)*A + a], zero for b >= Bn or a >= A.
+// the bf16x3 weight fragments wfrag[chunk][term][lane][j] (w1x3_elem, dca_frag.h)
 __global__ void conv1_x3_prep_kernel(const float* __restrict__ w, unsigned short* __restrict__ dst, int A, int Bn,
                                      int src_ab, int Btotal, int b_off, int total) {
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-    const int j = idx & 7, lane = (idx >> 3) & 63, term = (idx >> 9) % 3, chunk = (idx >> 9) / 3;
-    const int bi = lane & 31, ai = chunk * 16 + 8 * (lane >> 5) + j;
-    float v = 0.f;
-    if (ai < A && bi < Bn) v = src_ab ? w[(long)ai * Btotal + b_off + bi] : w[(long)(b_off + bi) * A + ai];
-    __bf16 h, m, l;
-    cx_split3(v, h, m, l);
-    const __bf16 o = term == 0 ? h : (term == 1 ? m : l);
-    dst[idx] = __builtin_bit_cast(unsigned short, o);
-  }
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x)
+    dst[idx] = w1x3_elem(w, idx, A, Bn, src_ab, Btotal, b_off);
 }
 
 }  // namespace

@@ -21,11 +21,9 @@
 // (x3_prep_weight_kernel) and stream through a double-buffered LDS slab of 9 taps (one kd plane) per phase, so a
 // channel chunk is three phases of 108 MFMAs per wave with one barrier each; the next slab / next halo tile are
 // fetched into registers (hardware-predicated buffer loads) while the current phase's MFMAs run.
-#include "dca_common.h"
+#include "dca_frag.h"
 #include "bn_fused_stats.h"
 #include <type_traits>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // Non-temporal output stores (X3_NT=1): y is written once, so it need not displace the halo lines the neighbouring tiles
 // re-read from this XCD's L2 -- 591 -> 568 us on the fused-epilogue 32->32 launch at 48x136x240 in isolation
@@ -80,14 +78,6 @@ struct X3Args {
 };
 
 constexpr int STAT_LDS = 8 * FS_WAVE_FLOATS * 4;
-
-__device__ __forceinline__ void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)v;
-  const float r1 = v - (float)h;   // exact
-  m = (__bf16)r1;
-  const float r2 = r1 - (float)m;  // exact
-  l = (__bf16)r2;
-}
 
 // STATS: the raw convolution output feeds a training-mode BatchNorm -- the kernel also produces, per channel and workgroup,
 // the partial statistics {K, n, sum (y - K), sum (y - K)^2} that dca_bn_finalize_centered consumes (bn_fused_stats.h), so the
@@ -222,7 +212,7 @@ __global__ __launch_bounds__(512) void conv3_bf16x3_kernel(X3Args a) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       __bf16 h, m, l;
-      split3(v[j], h, m, l);
+      x3_split(v[j], h, m, l);
       hv[j] = h; mv[j] = m; lv[j] = l;
     }
     *(bf16x8*)(b_lds + vox_off) = hv;
@@ -446,29 +436,11 @@ __global__ __launch_bounds__(512) void conv3_bf16x3_kernel(X3Args a) {
   }
 }
 
-// wx[cblk][chunk][tap][term][lane][j] (bf16): lane (r = lane & 31, h = lane >> 5) holds A[row = output channel
-// cblk*32 + r][k = input channel chunk*16 + 8h + j] of the tap, split into term 0/1/2 = h/m/l; zero padded.
-// Source indexing as dca_conv3d_prep_weight: src_ab ? src[a][b][27] : src[b][a][27]; flip reverses the tap order.
+// the bf16x3 weight fragments wx[cblk][chunk][tap][term][lane][j] (wx3_elem, dca_frag.h)
 __global__ void x3_prep_weight_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int A, int Bn,
                                       int NCH, int src_ab, int flip, long total) {
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-    const int j = idx & 7, lane = (idx >> 3) & 63;
-    long t = idx >> 9;
-    const int term = t % 3; t /= 3;
-    const int tap = t % 27; t /= 27;
-    const int chunk = t % NCH;
-    const int cblk = (int)(t / NCH);
-    const int bi = cblk * 32 + (lane & 31), ai = chunk * 16 + 8 * (lane >> 5) + j;
-    float v = 0.f;
-    if (ai < A && bi < Bn) {
-      const int st = flip ? 26 - tap : tap;
-      v = src_ab ? src[((long)ai * Bn + bi) * 27 + st] : src[((long)bi * A + ai) * 27 + st];
-    }
-    __bf16 h, m, l;
-    split3(v, h, m, l);
-    const __bf16 o = term == 0 ? h : (term == 1 ? m : l);
-    dst[idx] = __builtin_bit_cast(unsigned short, o);
-  }
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x)
+    dst[idx] = wx3_elem(src, idx, A, Bn, NCH, src_ab, flip);
 }
 
 }  // namespace

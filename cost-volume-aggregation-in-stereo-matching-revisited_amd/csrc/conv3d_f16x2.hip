@@ -37,11 +37,9 @@
 // loads, the [split and] LDS stores of the next chunk and the MFMAs of this one need no ordering among themselves.  The
 // staging steps sit at compile-time positions between the tap pairs (one global load or one LDS store per pair): issued as a
 // burst they held the matrix pipe for 1-2.4 k cycles per chunk (s_memtime stamps, tools/x2_stamps.py).
-#include "dca_common.h"
+#include "dca_frag.h"
 #include "bn_fused_stats.h"
 #include <type_traits>
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // Non-temporal output stores (X2_NT=1; measured on the bf16x3 kernel, whose epilogue this is): y is written once, so it need not displace the halo lines the neighbouring tiles
 // re-read from this XCD's L2 -- 591 -> 568 us on the fused-epilogue 32->32 launch at 48x136x240 in isolation
@@ -56,11 +54,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // receives s_memtime stamps of the first 96 chunks (8 marks per chunk) of workgroup 0, waves 0 and 7
 #ifndef X2_STAMP
 #define X2_STAMP 0
-#endif
-// X2_LD_FRONT (A/B builds): 1 = the staging loads of a phase in one burst in front of the slab stores, 2 = two per tap
-// behind the first four taps, 0 (shipped) = one per tap
-#ifndef X2_LD_FRONT
-#define X2_LD_FRONT 0
 #endif
 #if X2_STAMP
 #define X2_MARK(i) do { if (stamp_on && stamp_k < 96) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) stamps[stamp_k * 8 + (i)] = t_; } } while (0)
@@ -102,7 +95,6 @@ struct X2Args {
   int N, Cin, Cout, NCH;
   int D, H, W;
   int nTD, nTH, nTW;
-  int order;                 // tile traversal: 0 = w fastest (w, h, d, n), 1 = d fastest (d, w, h, n)
   double* stat_part;         // STATS: one partial {K, n, s, q} per (channel, workgroup): bn_fused_stats.h
   const int* xexps;          // fp32 x: the scale exponent of every input channel (Cin ints); unused for packed x
   const int* ofo;            // behind the packed weight image: f_o of every output channel (dca_conv3d_x2_prep_weight)
@@ -113,13 +105,6 @@ struct X2Args {
 };
 
 constexpr int STAT_LDS = 8 * FS_WAVE_FLOATS * 4;
-
-// x 2^e = h + l (+ <= 2^-22 relative)
-__device__ __forceinline__ void split2(float v, int e, _Float16& h, _Float16& l) {
-  const float u = ldexpf(v, e);   // exact (v_ldexp_f32); scaled maximum < 2^15
-  h = (_Float16)u;
-  l = (_Float16)(u - (float)h);   // the residual is exact in fp32
-}
 
 
 // STATS: the raw convolution output feeds a training-mode BatchNorm -- the kernel also produces, per channel and workgroup,
@@ -317,7 +302,7 @@ __global__ __launch_bounds__(512) void conv3_f16x2_kernel(X2Args a) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       _Float16 h, l;
-      split2(v[j], e[j], h, l);
+      x2_split(v[j], e[j], h, l);
       hv[j] = h; lv[j] = l;
     }
     *(f16x8*)dst = hv;
@@ -360,18 +345,10 @@ __global__ __launch_bounds__(512) void conv3_f16x2_kernel(X2Args a) {
     }
   };
   auto decode = [&](int tile, int& n, int& d0, int& h0, int& w0) __attribute__((always_inline)) {
-    int td, th, tw;
-    if (a.order == 0) {
-      tw = tile % a.nTW; tile /= a.nTW;
-      th = tile % a.nTH; tile /= a.nTH;
-      td = tile % a.nTD;
-      n = tile / a.nTD;
-    } else {
-      td = tile % a.nTD; tile /= a.nTD;
-      tw = tile % a.nTW; tile /= a.nTW;
-      th = tile % a.nTH;
-      n = tile / a.nTH;
-    }
+    const int tw = tile % a.nTW; tile /= a.nTW;
+    const int th = tile % a.nTH; tile /= a.nTH;
+    const int td = tile % a.nTD;
+    n = tile / a.nTD;
     d0 = td * TD; h0 = th * TH; w0 = tw * TW;
   };
 
@@ -684,7 +661,7 @@ __global__ __launch_bounds__(512) void x2_prep_weight_kernel(const float* __rest
         e = fo - xe[ai];
       }
       _Float16 h, l;
-      split2(v, e, h, l);
+      x2_split(v, e, h, l);
       hv[j] = h; lv[j] = l;
     }
     const long o = ((long)(chunk * NPAIR + pair) * NT) * 512 + (hf * 32 + r0 + r) * 8;      // f16 elements; term stride 512
@@ -762,10 +739,6 @@ int x2_launch(const void* x, int packed, const int* xexps, const void* wx, float
   a.D = D; a.H = H; a.W = W;
   a.nTD = cdiv(D, TD); a.nTH = cdiv(H, TH); a.nTW = cdiv(W, TW);
   a.stat_part = stat_part;
-  {
-    static const int order = [] { const char* e = getenv("DCA_X2_ORDER"); return e ? atoi(e) : 0; }();
-    a.order = order;
-  }
   a.xexps = xexps;
   a.y_cmax = y_cmax;
 #if X2_STAMP

@@ -18,12 +18,9 @@
 //           once per workgroup) and the halo image is double buffered (68 KB);
 //   MODE 2  Cin <= 64: resident weights (108 KB), single halo image (two barriers per chunk);
 //   MODE 0  wider inputs: weights stream through a double-buffered 27-tap slab next to the double-buffered halo image.
-#include "dca_common.h"
+#include "dca_frag.h"
 #include "../../include/dca_hip.h"
 #include <type_traits>
-
-typedef __bf16 lp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 lp_f16x8 __attribute__((ext_vector_type(8)));
 
 // compile-time ablation switches for tools/lp_ablate.sh (never set in the shipped library):
 // 1 no halo loads, 2 no MFMAs, 4 no epilogue stores, 8 no LDS fragment reads, 16 no LDS halo writes
@@ -38,9 +35,6 @@ typedef _Float16 lp_f16x8 __attribute__((ext_vector_type(8)));
 #endif
 #ifndef LP_NT      // non-temporal output stores
 #define LP_NT 0
-#endif
-#ifndef LP_DEFER   // experiment: epilogue deferred into the next tile's first step (slower: the VALU work does not hide)
-#define LP_DEFER 0
 #endif
 
 namespace {
@@ -75,34 +69,6 @@ struct LpArgs {
   int nTD, nTH, nTW;
 };
 
-// 2-byte matrix types: conversion from fp32 (round to nearest even), raw 16-bit pattern, MFMA
-template <typename MT> struct Lp;
-template <> struct Lp<__bf16> {
-  typedef lp_bf16x8 vec8;
-  static __device__ __forceinline__ f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Lp<_Float16> {
-  typedef lp_f16x8 vec8;
-  static __device__ __forceinline__ f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-template <typename MT> __device__ __forceinline__ unsigned short lp_bits(float v) {
-  const MT m = (MT)v;
-  return __builtin_bit_cast(unsigned short, m);
-}
-template <typename MT> __device__ __forceinline__ float lp_float(unsigned short b) {
-  return (float)__builtin_bit_cast(MT, b);
-}
-// two fp32 values -> one dword of two 2-byte values (lo = a, hi = b), round to nearest even
-template <typename MT> __device__ __forceinline__ unsigned lp_pack2(float a, float b) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef MT mtx2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, mtx2));
-}
 // value of lane ^ 1 (DPP quad_perm [1,0,3,2]: no LDS traffic, unlike __shfl_xor)
 __device__ __forceinline__ unsigned lp_swap1(unsigned v) {
   return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true);
@@ -297,7 +263,7 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
   // the MIDDLE of step s, right after the registers that held step s+1's tile were written to the other LDS image --
   // a full step of latency tolerance, and the pack + ds_write work overlaps the second half of the step's MFMAs.
   constexpr bool PIPE = MODE == 1;
-  constexpr int SPLIT = 13, ESPLIT = 3;
+  constexpr int SPLIT = 13;
   struct Cursor { int tile, chunk, n, d0, h0, w0; };
   auto advance = [&](Cursor& c) __attribute__((always_inline)) {   // next step; c.tile >= t_end marks "none"
     if (c.chunk + 1 < a.NCH) { ++c.chunk; return; }
@@ -330,9 +296,8 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
   }
   __syncthreads();
 
-  // epilogue: y = act(acc * scale + shift + res_pre) + res_post, fp32 arithmetic, stored as OUT.  `live` = 0 turns every
-  // access into an out-of-range one (the deferred epilogue slot of a step that has nothing to write).
-  auto epilogue = [&](const f32x16 (&eacc)[2], int n, int d0, int h0, int w0, int live) __attribute__((always_inline)) {
+  // epilogue: y = act(acc * scale + shift + res_pre) + res_post, fp32 arithmetic, stored as OUT
+  auto epilogue = [&](const f32x16 (&eacc)[2], int n, int d0, int h0, int w0) __attribute__((always_inline)) {
     const long osample = (long)a.Cout * cstride;
     const __amdgpu_buffer_rsrc_t yr = dca_rsrc((char*)a.y + (long)n * osample * OSZ, osample * OSZ);
     const __amdgpu_buffer_rsrc_t pr = dca_rsrc((const char*)(has_pre ? a.res_pre : a.y) + (long)n * osample * OSZ, osample * OSZ);
@@ -347,7 +312,7 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int r0 = (wv * 2 + t) * 2 + (l31 >> 4), d = d0 + (r0 >> 3), h = h0 + (r0 & 7), w = w0 + wlane;
-      const int ok = live & (int)(d < a.D) & (int)(h < a.H) & (int)(w < a.W) & (int)!((LP_ABL & 4) && eacc[t][1] != 12345.f);
+      const int ok = (int)(d < a.D) & (int)(h < a.H) & (int)(w < a.W) & (int)!((LP_ABL & 4) && eacc[t][1] != 12345.f);
       // Byte offsets: ONE hardware-predicated base per lane; register r adds the uniform cu(r) * cstride.  An output
       // channel >= Cout lands beyond the descriptor's range (Cout * cstride elements) and is dropped / read as zero by
       // the range check, so partial channel blocks need no per-register predicate.
@@ -409,13 +374,6 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
       }
     }
   };
-  f32x16 pacc[2];
-  int pn = 0, pd0 = 0, ph0 = 0, pw0 = 0, pvalid = 0;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) pacc[t][r] = 0.f;
-
   int buf = 0;
 #pragma unroll 1
   for (int tile = t_begin; tile < t_end; tile += t_step) {
@@ -455,10 +413,6 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
 #pragma unroll
       for (int tap = 0; tap < 27; ++tap) {
         const int cur = tap % NS;
-        if (PIPE && LP_DEFER && tap == ESPLIT) {   // the previous tile's epilogue, overlapped with this tile's first MFMAs
-          epilogue(pacc, pn, pd0, ph0, pw0, pvalid & (int)(chunk == 0));
-          if (chunk == 0) pvalid = 0;
-        }
         if (PIPE && tap == SPLIT) {
           if (c1.tile < t_end && !(LP_ABL & 16)) store_B(buf ^ 1);                                  // step s+1 -> other image
           if (c2.tile < t_end && !(LP_ABL & 1)) load_B(c2.n, c2.d0, c2.h0, c2.w0, c2.chunk);        // request step s+2
@@ -494,17 +448,9 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
       }
     }
 
-    if constexpr (PIPE && LP_DEFER) {   // deferred: runs inside the first step of the next tile (or after the loop)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) pacc[t] = acc[t];
-      pn = n; pd0 = d0; ph0 = h0; pw0 = w0;
-      pvalid = 1;
-    } else {
-      epilogue(acc, n, d0, h0, w0, 1);
-    }
+    epilogue(acc, n, d0, h0, w0);
     n = nn; d0 = nd0; h0 = nh0; w0 = nw0;
   }
-  if constexpr (PIPE && LP_DEFER) epilogue(pacc, pn, pd0, ph0, pw0, pvalid);
 }
 
 // wx[cblk][chunk][tap][lane][j] (2-byte): lane (r = lane & 31, h = lane >> 5) holds A[row = output channel

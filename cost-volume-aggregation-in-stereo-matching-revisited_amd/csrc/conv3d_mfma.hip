@@ -11,8 +11,9 @@
 // contiguous along W (128 B per half wave).  K runs over (tap, cin) with the input halo tile and
 // the per-chunk weights staged in LDS.  The same three kernels serve the backward-data passes with
 // re-laid-out weights (see dca_conv3d_prep_weight).
-#include "dca_common.h"
+#include "dca_frag.h"
 #include <stdlib.h>
+#include <type_traits>
 #include "../../include/dca_hip.h"
 
 struct ConvArgs {
@@ -43,21 +44,8 @@ __device__ __forceinline__ float epilogue(const ConvArgs& a, float v, int co, lo
 // 2-byte storage types of the reduced-precision inference path (include/dca_hip.h: DCA_BF16 = 1, DCA_FP16 = 2); 0 = fp32.
 // The stride-2 convolution can READ them (XT) and the transposed convolution can WRITE them (YT, residuals included);
 // the arithmetic stays the exact-fp32 MFMA of this file.
-template <int DT> struct Two;
-template <> struct Two<1> { typedef __bf16 T; };
-template <> struct Two<2> { typedef _Float16 T; };
-template <int DT> __device__ __forceinline__ float two_lo(unsigned w) {
-  return (float)__builtin_bit_cast(typename Two<DT>::T, (unsigned short)(w & 0xffffu));
-}
-template <int DT> __device__ __forceinline__ float two_hi(unsigned w) {
-  return (float)__builtin_bit_cast(typename Two<DT>::T, (unsigned short)(w >> 16));
-}
-template <int DT> __device__ __forceinline__ unsigned two_pack(float a, float b) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef typename Two<DT>::T mtx2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, mtx2));
-}
+// Two<DT>: the matrix type of a 2-byte tag (a placeholder for 0, whose 2-byte branches are compiled out).
+template <int DT> using Two = std::conditional_t<DT == 2, _Float16, __bf16>;
 
 // ---------------------------------------------------------------------------------------------
 // 3x3x3, pad 1, stride S.  Block = 4 waves; output tile TD x TH x TW; an MFMA column tile is 32 voxels =
@@ -162,14 +150,14 @@ __global__ __launch_bounds__(256, 2) void conv3_mfma_kernel(ConvArgs a) {
       const int it = tid + 256 * k;
       if constexpr (XT != 0) {
         const unsigned w0_ = __float_as_uint(rx[k].x), w1_ = __float_as_uint(rx[k].y);
-        rx[k] = make_float4(two_lo<XT ? XT : 1>(w0_), two_hi<XT ? XT : 1>(w0_), two_lo<XT ? XT : 1>(w1_), two_hi<XT ? XT : 1>(w1_));
+        rx[k] = make_float4(lp_lo<Two<XT>>(w0_), lp_hi<Two<XT>>(w0_), lp_lo<Two<XT>>(w1_), lp_hi<Two<XT>>(w1_));
       }
       if (it < ROWS * QPR) *(float4*)(in_lds + (it / QPR) * IWP + 4 + 4 * (it % QPR)) = rx[k];
     }
 #pragma unroll
     for (int k = 0; k < KH; ++k) {
       const int it = tid + 256 * k;
-      if constexpr (XT != 0) rh[k] = two_lo<XT ? XT : 1>(__float_as_uint(rh[k]));
+      if constexpr (XT != 0) rh[k] = lp_lo<Two<XT>>(__float_as_uint(rh[k]));
       if (it < ROWS * NH) in_lds[(it / NH) * IWP + 3 + ((it % NH) ? (IW - 1) : 0)] = rh[k];
     }
 #pragma unroll
@@ -437,7 +425,7 @@ __global__ __launch_bounds__(256, 2) void deconv3_mfma_kernel(ConvArgs a) {
             if constexpr (YT == 0) rp[q] = *(const float2*)(a.res_pre + off);
             else {
               const unsigned w_ = *(const unsigned*)((const unsigned short*)a.res_pre + off);
-              rp[q] = make_float2(two_lo<YT ? YT : 1>(w_), two_hi<YT ? YT : 1>(w_));
+              rp[q] = make_float2(lp_lo<Two<YT>>(w_), lp_hi<Two<YT>>(w_));
             }
           }
         }
@@ -449,7 +437,7 @@ __global__ __launch_bounds__(256, 2) void deconv3_mfma_kernel(ConvArgs a) {
             if constexpr (YT == 0) rq[q] = *(const float2*)(a.res_post + off);
             else {
               const unsigned w_ = *(const unsigned*)((const unsigned short*)a.res_post + off);
-              rq[q] = make_float2(two_lo<YT ? YT : 1>(w_), two_hi<YT ? YT : 1>(w_));
+              rq[q] = make_float2(lp_lo<Two<YT>>(w_), lp_hi<Two<YT>>(w_));
             }
           }
         }
@@ -462,7 +450,7 @@ __global__ __launch_bounds__(256, 2) void deconv3_mfma_kernel(ConvArgs a) {
           if (has_post) { o.x += rq[q].x; o.y += rq[q].y; }
           if (ok && co < a.Cout) {
             if constexpr (YT == 0) *(float2*)(a.y + base + co * plane) = o;
-            else *(unsigned*)((unsigned short*)a.y + base + co * plane) = two_pack<YT ? YT : 1>(o.x, o.y);
+            else *(unsigned*)((unsigned short*)a.y + base + co * plane) = lp_pack2<Two<YT>>(o.x, o.y);
           }
         }
       }
@@ -586,20 +574,12 @@ __global__ __launch_bounds__(256, CONV1_OCC) void conv1_mfma_kernel(ConvArgs a) 
   }
 }
 
-// dst[tap][a][b] (a < Apad rows = contraction channels, b < Bpad = output channels, zero padded)
-// from a PyTorch weight: src_ab ? src[a][b][K] : src[b][a][K]; flip reverses the tap order.
+// dst[tap][a][b] (a < Apad rows = contraction channels, b < Bpad = output channels, zero padded: wt_f32_elem, dca_frag.h)
 __global__ void prep_weight_kernel(const float* __restrict__ src, float* __restrict__ dst, int A, int Bn,
                                    int Apad, int Bpad, int K, int src_ab, int flip, int Btotal, int b_off) {
   const int total = K * Apad * Bpad;
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-    const int tap = idx / (Apad * Bpad), ai = (idx / Bpad) % Apad, bi = idx % Bpad;
-    float v = 0.f;
-    if (ai < A && bi < Bn) {
-      const int st = flip ? K - 1 - tap : tap;
-      v = src_ab ? src[((long)ai * Btotal + b_off + bi) * K + st] : src[((long)(b_off + bi) * A + ai) * K + st];
-    }
-    dst[idx] = v;
-  }
+  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x)
+    dst[idx] = wt_f32_elem(src, idx, A, Bn, Apad, Bpad, K, src_ab, flip, Btotal, b_off);
 }
 
 template <typename KernelT>

@@ -30,14 +30,17 @@
 // K-steps 3-5 (compile-time schedule, as in conv3d_f16x2.hip).
 //
 // Measured (tools/s2_time.py, 32 -> 64 at 48x136x240, batch 4): 0.45 ms against 0.87 ms for the fp32 MFMA kernel.  Ablations
-// (DCA_S2_ABL): without staging loads 0.34, without split + LDS stores 0.38, with neither 0.24 ms -- the MFMAs alone need 0.14 ms
+// (S2_ABL): without staging loads 0.34, without split + LDS stores 0.38, with neither 0.24 ms -- the MFMAs alone need 0.14 ms
 // at the clock held.  The kernel moves 1 KB of LDS reads per MFMA (a 32 x 32 accumulator tile reuses nothing) and 78 KB of LDS
 // stores per chunk of 42 MFMAs per wave (the weights' 28 KB are re-staged for every tile): LDS traffic, not the matrix pipe,
 // sets its speed.
-#include "dca_common.h"
+#include "dca_frag.h"
 
-typedef _Float16 s2_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 s2_f16x4 __attribute__((ext_vector_type(4)));
+// compile-time ablation switches for the measurements above (DCA_EXTRA_CFLAGS=-DS2_ABL=..., never set in the shipped
+// library): 1 no staging loads, 2 no LDS stores, 4 no split
+#ifndef S2_ABL
+#define S2_ABL 0
+#endif
 
 namespace {
 
@@ -74,17 +77,11 @@ struct S2Args {
   const float* shift;
   float slope;
   unsigned* y_cmax;          // EPI: optional per-channel slots [c][blockIdx.x] <- max |y| (dca_common.h)
-  int abl;                   // ablation switches (DCA_S2_ABL, tools/s2_time.py): 1 no staging loads, 2 no LDS stores, 4 no split
 };
 
-__device__ __forceinline__ void s2_split(float v, int e, _Float16& h, _Float16& l) {   // v 2^e = h + l (+ <= 2^-22 relative)
-  const float u = ldexpf(v, e);
-  h = (_Float16)u;
-  l = (_Float16)(u - (float)h);
-}
-__device__ __forceinline__ void s2_split_abl(float v, int e, _Float16& h, _Float16& l, int abl) {
-  if (abl & 4) { h = (_Float16)v; l = h; return; }
-  s2_split(v, e, h, l);
+__device__ __forceinline__ void s2_split_abl(float v, int e, _Float16& h, _Float16& l) {
+  if (S2_ABL & 4) { h = (_Float16)v; l = h; return; }
+  x2_split(v, e, h, l);
 }
 
 // byte offset inside a term image of tap t's fragment relative to the lane's base (2 dl, 2 hl, slot w)
@@ -192,32 +189,32 @@ __global__ __launch_bounds__(512) void conv3s2_f16x2_kernel(S2Args a) {
 #pragma unroll
     for (int par = 0; par < 2; ++par) {
       const int va = par ? 0 : 1, vb = va + 2;
-      s2_f16x8 hv, lv;
+      f16x8 hv, lv;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float* c = (const float*)&rq[k][j];
         _Float16 h, l;
-        s2_split_abl(c[va], e[j], h, l, a.abl); hv[j] = h; lv[j] = l;
-        s2_split_abl(c[vb], e[j], h, l, a.abl); hv[4 + j] = h; lv[4 + j] = l;
+        s2_split_abl(c[va], e[j], h, l); hv[j] = h; lv[j] = l;
+        s2_split_abl(c[vb], e[j], h, l); hv[4 + j] = h; lv[4 + j] = l;
       }
       char* dst = img + (par ? B_PLANE + (2 * qq[k]) * 8 : (2 * qq[k] + 2) * 8);
-      *(s2_f16x8*)dst = hv;
-      *(s2_f16x8*)(dst + B_TERM) = lv;
+      *(f16x8*)dst = hv;
+      *(f16x8*)(dst + B_TERM) = lv;
     }
   };
   auto store_edge = [&](int chunk, int buf) __attribute__((always_inline)) {      // iw = 0: even plane, position 0 = slot 1
     if (erow < 0) return;
     const int4 e4 = *(const int4*)(xe_lds + chunk * 4);
     const int e[4] = {e4.x, e4.y, e4.z, e4.w};
-    s2_f16x4 hv, lv;
+    f16x4 hv, lv;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       _Float16 h, l;
-      s2_split(re[j], e[j], h, l); hv[j] = h; lv[j] = l;
+      x2_split(re[j], e[j], h, l); hv[j] = h; lv[j] = l;
     }
     char* dst = b_lds + buf * B_BYTES + erow * ROWB + 8;
-    *(s2_f16x4*)dst = hv;
-    *(s2_f16x4*)(dst + B_TERM) = lv;
+    *(f16x4*)dst = hv;
+    *(f16x4*)(dst + B_TERM) = lv;
   };
   auto decode = [&](int tile, int& n, int& d0, int& h0, int& w0) __attribute__((always_inline)) {
     const int tw = tile % a.nTW; tile /= a.nTW;
@@ -243,7 +240,7 @@ __global__ __launch_bounds__(512) void conv3s2_f16x2_kernel(S2Args a) {
     }
   };
   auto load_all = [&](const Cursor& c, int part) __attribute__((always_inline)) {     // part 0: quad 0; 1: quad 1 + edge; 2: weights
-    const int on = (c.tile < t_end && !(a.abl & 1)) ? 1 : 0;
+    const int on = (c.tile < t_end && !(S2_ABL & 1)) ? 1 : 0;
     const __amdgpu_buffer_rsrc_t xr = dca_rsrc(a.x + (long)c.n * sample, sample * 4);
     if (part == 0) load_quad(0, xr, c.d0, c.h0, c.w0, c.chunk, on);
     if (part == 1) { load_quad(1, xr, c.d0, c.h0, c.w0, c.chunk, on); load_edge(xr, c.d0, c.h0, c.w0, c.chunk, on); }
@@ -275,17 +272,17 @@ __global__ __launch_bounds__(512) void conv3s2_f16x2_kernel(S2Args a) {
   for (; cur.tile < t_end; buf ^= 1) {
     const char* ab = a_lds + buf * A_CHUNK + lane * 16;
     const char* bb = b_lds + buf * B_BYTES + lanebase;
-    const bool st_on = st.tile < t_end && !(a.abl & 2);
-    s2_f16x8 fa[2][2][2], fb[2][2];      // [slot][channel block][term], [slot][term]
+    const bool st_on = st.tile < t_end && !(S2_ABL & 2);
+    f16x8 fa[2][2][2], fb[2][2];      // [slot][channel block][term], [slot][term]
     auto load_frag = [&](int s, int slot) __attribute__((always_inline)) {
       const int oa = half ? s2_toff(4 * s + 2) : s2_toff(4 * s), ob = half ? s2_toff(4 * s + 3) : s2_toff(4 * s + 1);
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
-        for (int term = 0; term < 2; ++term) fa[slot][cb][term] = *(const s2_f16x8*)(ab + ((s * 2 + cb) * 2 + term) * 1024);
+        for (int term = 0; term < 2; ++term) fa[slot][cb][term] = *(const f16x8*)(ab + ((s * 2 + cb) * 2 + term) * 1024);
 #pragma unroll
       for (int term = 0; term < 2; ++term) {
-        const s2_f16x4 lo = *(const s2_f16x4*)(bb + term * B_TERM + oa), hi = *(const s2_f16x4*)(bb + term * B_TERM + ob);
+        const f16x4 lo = *(const f16x4*)(bb + term * B_TERM + oa), hi = *(const f16x4*)(bb + term * B_TERM + ob);
         fb[slot][term] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
       }
     };
@@ -424,7 +421,7 @@ __global__ __launch_bounds__(512) void s2x2_prep_weight_kernel(const float* __re
   for (int it = tid; it < nitems; it += 512) {
     const int r = it % PREP_ROWS, hf = (it / PREP_ROWS) & 1, t = it / (2 * PREP_ROWS), s = t % NSTEP, chunk = t / NSTEP;
     const int rr = r0 + r, cb = rr >> 5, rl = rr & 31, bi = cblk * 64 + rr, fo = rowmax[r][0];
-    s2_f16x8 hv, lv;
+    f16x8 hv, lv;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int tap = 4 * s + 2 * hf + (j >> 2), ai = chunk * 4 + (j & 3);
@@ -436,12 +433,12 @@ __global__ __launch_bounds__(512) void s2x2_prep_weight_kernel(const float* __re
         e = fo - xe[ai];
       }
       _Float16 h, l;
-      s2_split(v, e, h, l);
+      x2_split(v, e, h, l);
       hv[j] = h; lv[j] = l;
     }
     const long o = (((long)(chunk * NSTEP + s) * 2 + cb) * 2) * 512 + (hf * 32 + rl) * 8;      // f16 elements; term stride 512
-    *(s2_f16x8*)(out + o) = hv;
-    *(s2_f16x8*)(out + o + 512) = lv;
+    *(f16x8*)(out + o) = hv;
+    *(f16x8*)(out + o + 512) = lv;
   }
 }
 
@@ -502,10 +499,6 @@ extern "C" int dca_conv3d_s2x2_forward(const float* x, const int* xexps, const v
   DCA_REQUIRE((long)(Cin + 3) * Di * Hi * Wi * 4 < 0x7ffffff0L && (long)(Cout + 63) * a.Do * a.Ho * a.Wo * 4 < 0x7ffffff0L);
   a.nTD = cdiv(a.Do, TD); a.nTH = cdiv(a.Ho, TH); a.nTW = cdiv(a.Wo, TW);
   a.xexps = xexps;
-  {
-    static const int abl = [] { const char* e = getenv("DCA_S2_ABL"); return e ? atoi(e) : 0; }();
-    a.abl = abl;
-  }
   const int cblks = (Cout + 63) / 64;
   a.ofo = (const int*)((const char*)wx + (long)cblks * a.NC4 * A_CHUNK);
   const long tiles = (long)N * a.nTD * a.nTH * a.nTW;

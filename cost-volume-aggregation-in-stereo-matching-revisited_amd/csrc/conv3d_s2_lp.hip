@@ -13,11 +13,8 @@
 // 3 x 3 x 2 = 18 K-steps; a wave owns one column tile of 32 coarse positions and both 32-channel output blocks.
 // LDS: the chunk's fine 5 x 17 x 34 halo image as [voxel][8 x 2 B] (45 KB) + the chunk's 36 KB of pre-swizzled weight
 // fragments; the next chunk's image and weights are fetched into registers while the current chunk's MFMAs run.
-#include "dca_common.h"
+#include "dca_frag.h"
 #include "../../include/dca_hip.h"
-
-typedef __bf16 s2_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 s2_f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -45,24 +42,10 @@ struct S2Args {
   int nTD, nTH, nTW;
 };
 
-template <typename MT> struct S2;
-template <> struct S2<__bf16> {
-  typedef s2_bf16x8 vec8;
-  static __device__ __forceinline__ f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct S2<_Float16> {
-  typedef s2_f16x8 vec8;
-  static __device__ __forceinline__ f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-
 // W % 4 == 0 and an 8-byte aligned x (the caller checks)
 template <typename MT>
 __global__ __launch_bounds__(512) void conv3_s2_lp_kernel(S2Args a) {
-  typedef typename S2<MT>::vec8 vec8;
+  typedef typename Lp<MT>::vec8 vec8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* b_lds = smem;
   char* a_lds = smem + B_IMG;
@@ -192,8 +175,8 @@ __global__ __launch_bounds__(512) void conv3_s2_lp_kernel(S2Args a) {
         const int kd = ks / 6, kh = (ks / 2) % 3, ws = ks & 1;     // ws 0: delta_w = 0 (taps kw 1 | 2), ws 1: delta_w = -1 (tap kw 0)
         const vec8 fb = *(const vec8*)(bb + ((kd * FH + kh) * FW + (ws ? 0 : 2)) * 16);
         const vec8 fa0 = *(const vec8*)(ab + (ks * 2 + 0) * 1024), fa1 = *(const vec8*)(ab + (ks * 2 + 1) * 1024);
-        acc[0] = S2<MT>::mfma(fa0, fb, acc[0]);
-        acc[1] = S2<MT>::mfma(fa1, fb, acc[1]);
+        acc[0] = Lp<MT>::mfma(fa0, fb, acc[0]);
+        acc[1] = Lp<MT>::mfma(fa1, fb, acc[1]);
       }
       __syncthreads();     // every wave is done with this chunk's image and weights
       if (stage) {

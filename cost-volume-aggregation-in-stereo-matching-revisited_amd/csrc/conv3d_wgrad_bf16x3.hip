@@ -21,11 +21,8 @@
 // fetched into registers during the MFMA phase, split and written to LDS between two barriers.  At the end the two
 // groups are summed through LDS and the workgroup writes one slab of partial sums; wgrad_reduce_kernel
 // (conv3d_wgrad.hip) adds the slabs in a fixed order: bitwise reproducible, no atomics.
-#include "dca_common.h"
+#include "dca_frag.h"
 #include <type_traits>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 int dca_internal_wgrad_reduce(const float* part, float* dw, int nblk, int nCxT, int nCT, int K, int Cy, int Cx,
                               long s_cy, long s_cx, hipStream_t stream);  // conv3d_wgrad.hip
@@ -34,9 +31,6 @@ int dca_internal_wgrad_reduce(const float* part, float* dw, int nblk, int nCxT, 
 // allocates it) that receives s_memtime stamps of the first 64 tiles of workgroup 0, waves 0 and 3
 #ifndef WX3_STAMP
 #define WX3_STAMP 0
-#endif
-#ifndef WX3_LOADS_IN
-#define WX3_LOADS_IN 1
 #endif
 #if WX3_STAMP
 #define WX3_MARK(i) do { if (stamp_on && stamp_k < 64) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) stamps[((wq == 3) * 64 + stamp_k) * 8 + (i)] = t_; } } while (0)
@@ -67,14 +61,6 @@ struct WX3Args {
   int N, Cx, Cy, D, H, W;
   int nTD, nTH, nTW, nCxT;
 };
-
-__device__ __forceinline__ void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)v;
-  const float r1 = v - (float)h;
-  m = (__bf16)r1;
-  const float r2 = r1 - (float)m;
-  l = (__bf16)r2;
-}
 
 __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -142,7 +128,7 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       __bf16 h, m, l;
-      split3(v[j], h, m, l);
+      x3_split(v[j], h, m, l);
       hv[j] = h; mv[j] = m; lv[j] = l;
     }
     *(bf16x8*)(base + off) = hv;
@@ -158,7 +144,7 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
     for (int k = 0; k < KE; ++k) {
       const int it = tid + 512 * k, side = (it >> 5) & 1;
       __bf16 h, m, l;
-      split3(re[k], h, m, l);
+      x3_split(re[k], h, m, l);
       // left edge (side 0) sits in the HIGH half of its dword, right edge (side 1) in the LOW half (see shifts below)
       const unsigned sh = side ? 0 : 16;
       *(unsigned*)(smem + XE_OFF + it * 4) = (unsigned)__builtin_bit_cast(unsigned short, h) << sh;
@@ -177,7 +163,7 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
     constexpr int R0 = TAP0 / 3, R1 = (TAP1 - 1) / 3;  // (kd, kh) rows this wave touches
 #pragma unroll 1
     for (int i = 0; i < NROW / 2; ++i) {
-      if (WX3_LOADS_IN && i == 1 && more) {
+      if (i == 1 && more) {
         int nn, nd0, nh0, nw0;
         decode(next_tile, nn, nd0, nh0, nw0);
         load_tile(nn, nd0, nh0, nw0);
@@ -191,15 +177,15 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
       for (int rr = R0; rr <= R1; ++rr) {
         const int kd = rr / 3, kh = rr % 3;
         const int hrow = (dl + kd) * HH + hl + kh;
-        u32x4v g[3];
+        u32x4 g[3];
         unsigned e[3];
 #pragma unroll
         for (int term = 0; term < 3; ++term) {
-          g[term] = *(const u32x4v*)(smem + X_OFF + term * X_TERM + ((hrow * 2 + half) * 32 + l31) * 16);
+          g[term] = *(const u32x4*)(smem + X_OFF + term * X_TERM + ((hrow * 2 + half) * 32 + l31) * 16);
           e[term] = *(const unsigned*)(smem + XE_OFF + term * XE_TERM + ((hrow * 2 + half) * 32 + l31) * 4);
         }
         // fragments for kw = 0 (g itself), kw = -1 (s[0..3]) and kw = +1 (s[1..4])
-        u32x4v fm[3], fp[3];
+        u32x4 fm[3], fp[3];
 #pragma unroll
         for (int term = 0; term < 3; ++term) {
           const auto sw = __builtin_amdgcn_permlane32_swap(g[term][0], g[term][3], false, false);
@@ -210,8 +196,8 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
           const unsigned s2 = __builtin_amdgcn_alignbit(g[term][2], g[term][1], 16);
           const unsigned s3 = __builtin_amdgcn_alignbit(g[term][3], g[term][2], 16);
           const unsigned s4 = __builtin_amdgcn_alignbit(rd, g[term][3], 16);
-          fm[term] = (u32x4v){s0, s1, s2, s3};
-          fp[term] = (u32x4v){s1, s2, s3, s4};
+          fm[term] = (u32x4){s0, s1, s2, s3};
+          fp[term] = (u32x4){s1, s2, s3, s4};
         }
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) {
@@ -249,10 +235,6 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
     for (int tile = t_begin; tile < t_end; tile += t_step) {
       const bool more = tile + t_step < t_end;
       WX3_MARK(0);
-      if (more && !WX3_LOADS_IN) {
-        decode(tile + t_step, n, d0, h0, w0);
-        load_tile(n, d0, h0, w0);
-      }
       WX3_MARK(1);
       switch (wq) {
         case 0: mfma_tile(std::integral_constant<int, 0>{}, more, tile + t_step); break;

@@ -24,13 +24,8 @@
 // phase and written to LDS between two barriers.  At the end the two groups are summed through LDS and the workgroup writes
 // one slab of partial sums; wgrad_reduce_kernel (conv3d_wgrad.hip) adds the slabs in a fixed order: bitwise
 // reproducible, no atomics.
-#include "dca_common.h"
+#include "dca_frag.h"
 #include <type_traits>
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
-typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 int dca_internal_wgrad_reduce(const float* part, float* dw, int nblk, int nCxT, int nCT, int K, int Cy, int Cx,
                               long s_cy, long s_cx, hipStream_t stream);  // conv3d_wgrad.hip
@@ -67,20 +62,6 @@ struct WX2Args {
   const int* xexps;         // per-channel scale exponents of x / dy (Cx / Cy ints, dca_common.h)
   const int* yexps;
 };
-
-__device__ __forceinline__ void split2(float v, int e, _Float16& h, _Float16& l) {
-  const float u = ldexpf(v, e);   // exact; scaled maximum < 2^15
-  h = (_Float16)u;
-  l = (_Float16)(u - (float)h);   // the residual is exact in fp32
-}
-
-// the 8 voxels x 1 channel MFMA fragment of this lane from a [voxel][32 channels] image: two transposing reads of 4 voxels
-__device__ __forceinline__ f16x8 tr_frag(const char* p) {
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * VB));
-  const s16x8 c = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(f16x8, c);
-}
 
 template <bool XP, bool YP>
 __global__ __launch_bounds__(512) void wgrad3_f16x2_kernel(WX2Args a) {
@@ -277,7 +258,7 @@ __global__ __launch_bounds__(512) void wgrad3_f16x2_kernel(WX2Args a) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       _Float16 h, l;
-      split2(v[j], ex8[j], h, l);
+      x2_split(v[j], ex8[j], h, l);
       hv[j] = h; lv[j] = l;
     }
     *(f16x8*)dst = hv;
@@ -343,12 +324,12 @@ __global__ __launch_bounds__(512) void wgrad3_f16x2_kernel(WX2Args a) {
       const char* xb = smem + buf * IMG_BYTES + X_OFF + ((grp * HH + i) * XV) * VB + lane_off;
       f16x8 ay[NT];
 #pragma unroll
-      for (int term = 0; term < NT; ++term) ay[term] = tr_frag(yb + term * Y_TERM);
+      for (int term = 0; term < NT; ++term) ay[term] = tr_frag(yb + term * Y_TERM, 4 * VB);
       f16x8 bx[2][NT];
       auto load_b = [&](int tap, int slot) __attribute__((always_inline)) {
         const int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
 #pragma unroll
-        for (int term = 0; term < NT; ++term) bx[slot][term] = tr_frag(xb + term * X_TERM + ((kd * HH + kh) * XV + kw) * VB);
+        for (int term = 0; term < NT; ++term) bx[slot][term] = tr_frag(xb + term * X_TERM + ((kd * HH + kh) * XV + kw) * VB, 4 * VB);
       };
       load_b(TAP0, 0);
 #pragma unroll

@@ -24,13 +24,8 @@
 // phase and scaled, split and written to LDS between two barriers.  At the end every wave writes its taps of its block's
 // slab of partial sums; wgrad_reduce_kernel (conv3d_wgrad.hip) adds the slabs in a fixed order: bitwise reproducible, no
 // atomics.
-#include "dca_common.h"
+#include "dca_frag.h"
 #include <type_traits>
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
-typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 int dca_internal_wgrad_reduce(const float* part, float* dw, int nblk, int nCxT, int nCT, int K, int Cy, int Cx,
                               long s_cy, long s_cx, hipStream_t stream);  // conv3d_wgrad.hip
@@ -64,22 +59,6 @@ struct WS2Args {
   const int* xexps;         // per-channel scale exponents of the fine / coarse operand (Cx / Cy ints, dca_common.h)
   const int* yexps;
 };
-
-__device__ __forceinline__ void split2(float v, int s, _Float16& h, _Float16& l) {
-  const float u = ldexpf(v, s);   // exact; scaled maximum < 2^15
-  h = (_Float16)u;
-  l = (_Float16)(u - (float)h);   // the residual is exact in fp32
-}
-
-// 8 voxels x 1 channel MFMA fragment from a [voxel][32 channels] image: two transposing reads of 4 voxel rows each; the
-// lane supplies the address of ITS row (dca_wgrad: consecutive voxels; here every second fine voxel), `step` = bytes between
-// the two blocks of four
-__device__ __forceinline__ f16x8 tr_frag(const char* p, int step) {
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + step));
-  const s16x8 c = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(f16x8, c);
-}
 
 __global__ __launch_bounds__(512) void wgrad3s2_f16x2_kernel(WS2Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -170,7 +149,7 @@ __global__ __launch_bounds__(512) void wgrad3s2_f16x2_kernel(WS2Args a) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       _Float16 h, l;
-      split2(v[j], ex[j], h, l);
+      x2_split(v[j], ex[j], h, l);
       hv[j] = h; lv[j] = l;
     }
     *(f16x8*)dst = hv;

@@ -17,11 +17,8 @@
 // current step (same pipeline as conv3d_lp.hip).  The two w-parities of a coarse position are adjacent fine voxels, so the
 // epilogue packs them into one dword per (d-parity, h-parity, channel): 64 coalesced dword stores per lane, no lane
 // exchange; residuals come in the same way.
-#include "dca_common.h"
+#include "dca_frag.h"
 #include "../../include/dca_hip.h"
-
-typedef __bf16 dl_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 dl_f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -51,35 +48,10 @@ struct DlArgs {
   int nTD, nTH, nTW;
 };
 
-template <typename MT> struct Dl;
-template <> struct Dl<__bf16> {
-  typedef dl_bf16x8 vec8;
-  static __device__ __forceinline__ f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Dl<_Float16> {
-  typedef dl_f16x8 vec8;
-  static __device__ __forceinline__ f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-template <typename MT> __device__ __forceinline__ unsigned dl_pack2(float a, float b) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef MT mtx2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, mtx2));
-}
-template <typename MT> __device__ __forceinline__ float dl_lo(unsigned w) {
-  return (float)__builtin_bit_cast(MT, (unsigned short)(w & 0xffffu));
-}
-template <typename MT> __device__ __forceinline__ float dl_hi(unsigned w) {
-  return (float)__builtin_bit_cast(MT, (unsigned short)(w >> 16));
-}
 
 template <typename MT, bool VEC>
 __global__ __launch_bounds__(512) void deconv3_lp_kernel(DlArgs a) {
-  typedef typename Dl<MT>::vec8 vec8;
+  typedef typename Lp<MT>::vec8 vec8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* b_lds = smem;                 // two coarse halo images
   char* a_lds = smem + 2 * B_IMG;     // weight fragments of all chunks
@@ -169,10 +141,10 @@ __global__ __launch_bounds__(512) void deconv3_lp_kernel(DlArgs a) {
         for (int i = 0; i < 4; ++i) {
           if (q == 4 && i > 0) continue;            // the row has 17 voxels: the fifth quad contributes one
           u32x4 o;
-          o.x = dl_pack2<MT>(__uint_as_float(rq[0][i]), __uint_as_float(rq[1][i]));
-          o.y = dl_pack2<MT>(__uint_as_float(rq[2][i]), __uint_as_float(rq[3][i]));
-          o.z = dl_pack2<MT>(__uint_as_float(rq[4][i]), __uint_as_float(rq[5][i]));
-          o.w = dl_pack2<MT>(__uint_as_float(rq[6][i]), __uint_as_float(rq[7][i]));
+          o.x = lp_pack2<MT>(__uint_as_float(rq[0][i]), __uint_as_float(rq[1][i]));
+          o.y = lp_pack2<MT>(__uint_as_float(rq[2][i]), __uint_as_float(rq[3][i]));
+          o.z = lp_pack2<MT>(__uint_as_float(rq[4][i]), __uint_as_float(rq[5][i]));
+          o.w = lp_pack2<MT>(__uint_as_float(rq[6][i]), __uint_as_float(rq[7][i]));
           *(u32x4*)(img + o_base + 16 * i) = o;
         }
       }
@@ -183,10 +155,10 @@ __global__ __launch_bounds__(512) void deconv3_lp_kernel(DlArgs a) {
         if (crd >= 0) {
           const int o = ((((crd >> 24) & 1) * ID + (crd & 255)) * IH + ((crd >> 8) & 255)) * IW * 16 + ((crd >> 16) & 255) * 16;
           u32x4 w;
-          w.x = dl_pack2<MT>(__uint_as_float(rb[k][0]), __uint_as_float(rb[k][1]));
-          w.y = dl_pack2<MT>(__uint_as_float(rb[k][2]), __uint_as_float(rb[k][3]));
-          w.z = dl_pack2<MT>(__uint_as_float(rb[k][4]), __uint_as_float(rb[k][5]));
-          w.w = dl_pack2<MT>(__uint_as_float(rb[k][6]), __uint_as_float(rb[k][7]));
+          w.x = lp_pack2<MT>(__uint_as_float(rb[k][0]), __uint_as_float(rb[k][1]));
+          w.y = lp_pack2<MT>(__uint_as_float(rb[k][2]), __uint_as_float(rb[k][3]));
+          w.z = lp_pack2<MT>(__uint_as_float(rb[k][4]), __uint_as_float(rb[k][5]));
+          w.w = lp_pack2<MT>(__uint_as_float(rb[k][6]), __uint_as_float(rb[k][7]));
           *(u32x4*)(img + o) = w;
         }
       }
@@ -250,7 +222,7 @@ __global__ __launch_bounds__(512) void deconv3_lp_kernel(DlArgs a) {
         const int pc = ((kd != 1) * 2 + (kh != 1)) * 2 + (kw != 1);          // output parity class
         const int dlt = ((kd == 0) * 2 + (kh == 0)) * 2 + (kw == 0);         // coarse neighbour x[m + delta]
         const vec8 fa = *(const vec8*)(ab + tap * 1024);
-        acc[pc] = Dl<MT>::mfma(fa, fb[dlt], acc[pc]);
+        acc[pc] = Lp<MT>::mfma(fa, fb[dlt], acc[pc]);
       }
       __syncthreads();
     }
@@ -292,9 +264,9 @@ __global__ __launch_bounds__(512) void deconv3_lp_kernel(DlArgs a) {
           for (int q = 0; q < 8; ++q) {
             const int r = rc + q, cl = (r & 3) + 8 * (r >> 2) + 4 * half;
             const float sc = aff_lds[cl], sh = aff_lds[32 + cl];
-            const float v0 = act_apply(acc[pc0][r] * sc + sh + dl_lo<MT>(wp[q]), a.slope) + dl_lo<MT>(wq[q]);
-            const float v1 = act_apply(acc[pc0 + 1][r] * sc + sh + dl_hi<MT>(wp[q]), a.slope) + dl_hi<MT>(wq[q]);
-            __builtin_amdgcn_raw_buffer_store_b32(dl_pack2<MT>(v0, v1), yr, base + ((r & 3) + 8 * (r >> 2)) * ostride * 2, 0, 0);
+            const float v0 = act_apply(acc[pc0][r] * sc + sh + lp_lo<MT>(wp[q]), a.slope) + lp_lo<MT>(wq[q]);
+            const float v1 = act_apply(acc[pc0 + 1][r] * sc + sh + lp_hi<MT>(wp[q]), a.slope) + lp_hi<MT>(wq[q]);
+            __builtin_amdgcn_raw_buffer_store_b32(lp_pack2<MT>(v0, v1), yr, base + ((r & 3) + 8 * (r >> 2)) * ostride * 2, 0, 0);
           }
         }
       }

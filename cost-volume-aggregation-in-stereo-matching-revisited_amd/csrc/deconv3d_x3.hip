@@ -32,18 +32,13 @@
 // the split into the three bf16 terms happens IN REGISTERS in the compute slot, per neighbour fragment, interleaved
 // with the MFMAs (11 instructions per channel pair), the pass epilogue runs at the end of the compute slot, and a load
 // slot is nothing but waits, register moves and LDS stores.
-#include "dca_common.h"
+#include "dca_frag.h"
 #include "bn_fused_stats.h"
 #include "../../include/dca_hip.h"
-
-typedef __bf16 dx_bf16x8 __attribute__((ext_vector_type(8)));
 
 // non-temporal output stores: off, as in conv3d_bf16x3.hip (the consumer finds y in the infinity cache)
 #ifndef DX3_NT
 #define DX3_NT 0
-#endif
-#ifndef DX3_SOFF
-#define DX3_SOFF 1
 #endif
 
 // DX3_STAMP (debug build, tools/dx3_stamps.py): res_post is reinterpreted as an unsigned long long buffer that receives
@@ -90,12 +85,6 @@ struct DxArgs {
 
 constexpr int STAT_LDS = 8 * FS_WAVE_FLOATS * 4;
 
-__device__ __forceinline__ unsigned dx_pack2(float a, float b) {   // v_cvt_pk_bf16_f32
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bfx2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bfx2));
-}
 __device__ __forceinline__ float dx_sub(float a, float b) {   // plain v_sub_f32: hipcc's SLP pass would pair these into
   float r;                                                     // v_pk_add_f32, which is slow beside MFMAs
   asm("v_sub_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -106,16 +95,16 @@ __device__ __forceinline__ float dx_sub(float a, float b) {   // plain v_sub_f32
 __device__ __forceinline__ void dx_split_h(const float4 lo, const float4 hi, int j, u32x4& H) {
   const float va = j == 0 ? lo.x : (j == 1 ? lo.z : (j == 2 ? hi.x : hi.z));
   const float vb = j == 0 ? lo.y : (j == 1 ? lo.w : (j == 2 ? hi.y : hi.w));
-  H[j] = dx_pack2(va, vb);
+  H[j] = lp_pack2<__bf16>(va, vb);
 }
 __device__ __forceinline__ void dx_split_ml(const float4 lo, const float4 hi, int j, const u32x4& H, u32x4& M, u32x4& L) {
   const float va = j == 0 ? lo.x : (j == 1 ? lo.z : (j == 2 ? hi.x : hi.z));
   const float vb = j == 0 ? lo.y : (j == 1 ? lo.w : (j == 2 ? hi.y : hi.w));
   const unsigned h2 = H[j];
   const float ra = dx_sub(va, __uint_as_float(h2 << 16)), rb = dx_sub(vb, __uint_as_float(h2 & 0xffff0000u));      // exact
-  const unsigned m2 = dx_pack2(ra, rb);
+  const unsigned m2 = lp_pack2<__bf16>(ra, rb);
   M[j] = m2;
-  L[j] = dx_pack2(dx_sub(ra, __uint_as_float(m2 << 16)), dx_sub(rb, __uint_as_float(m2 & 0xffff0000u)));
+  L[j] = lp_pack2<__bf16>(dx_sub(ra, __uint_as_float(m2 << 16)), dx_sub(rb, __uint_as_float(m2 & 0xffff0000u)));
 }
 __device__ __forceinline__ void dx_split_pair(const float4 lo, const float4 hi, int j, u32x4& H, u32x4& M, u32x4& L) {
   dx_split_h(lo, hi, j, H);
@@ -206,8 +195,7 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
     const int sbase = (step_chunk(s) * 3 + step_kd(s)) * A_SLAB + grp * HALF_A * 16;
 #pragma unroll
     for (int k = 0; k < KA; ++k) {
-      const u32x4 v = DX3_SOFF ? __builtin_amdgcn_raw_buffer_load_b128(wr, a_voff[k], sbase + 256 * 16 * k, 0)
-                               : __builtin_amdgcn_raw_buffer_load_b128(wr, a_voff[k] + sbase + 256 * 16 * k, 0, 0);
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(wr, a_voff[k], sbase + 256 * 16 * k, 0);
       ra[k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
     }
   };
@@ -235,7 +223,7 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
     const int base = dca_pred_off((c0 * cstride + (di * a.Hi + hi) * a.Wi + wi) * 4, okv);
     // the channel part of the address as a scalar offset (no vector instruction per load) -- but scalar offsets are
     // excluded from the hardware range check, which a partial last chunk relies on, so only when Cin fills its chunks
-    if (cin_full && DX3_SOFF) {
+    if (cin_full) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) rq[j] = __builtin_amdgcn_raw_buffer_load_b64(xr, base, j * cstride * 4, 0);
     } else {
@@ -329,10 +317,10 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
       constexpr int SLOT[9] = {0, 0, 0, 0, 1, 1, 2, 2, 0};          // fragment slot a tap multiplies with
       constexpr int SPLIT_D[7] = {0, 1, 1, 2, 2, 3, 3};             // neighbour split beside tap i < 7 ...
       constexpr int SPLIT_S[7] = {0, 1, 1, 2, 2, 0, 0};             // ... into this slot
-      dx_bf16x8 fa[2][3];
+      bf16x8 fa[2][3];
       u32x4 fw[3][3];                                               // [slot][term]
 #pragma unroll
-      for (int term = 0; term < 3; ++term) fa[0][term] = *(const dx_bf16x8*)(ab + (TAPS[0] * 3 + term) * 1024);
+      for (int term = 0; term < 3; ++term) fa[0][term] = *(const bf16x8*)(ab + (TAPS[0] * 3 + term) * 1024);
 #pragma unroll
       for (int j = 0; j < 4; ++j) dx_split_h(raw[0][0], raw[0][1], j, fw[0][0]);
       // register double buffer for the weight fragments: the three reads of the next tap are issued in front of the six
@@ -346,7 +334,7 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
         if (i < 8) {
 #pragma unroll
           for (int term = 0; term < 3; ++term)
-            fa[cs ^ 1][term] = *(const dx_bf16x8*)(ab + (TAPS[i + 1] * 3 + term) * 1024);
+            fa[cs ^ 1][term] = *(const bf16x8*)(ab + (TAPS[i + 1] * 3 + term) * 1024);
           __builtin_amdgcn_sched_barrier(0);
         }
         const int kh = tap9 / 3, kw = tap9 % 3;
@@ -366,7 +354,7 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
 #pragma unroll
         for (int q = 0; q < 6; ++q)
           acc[pc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cs][i == 0 ? PA0[q] : PA[q]],
-                                                            __builtin_bit_cast(dx_bf16x8, fw[SLOT[i]][i == 0 ? PB0[q] : PB[q]]),
+                                                            __builtin_bit_cast(bf16x8, fw[SLOT[i]][i == 0 ? PB0[q] : PB[q]]),
                                                             acc[pc], 0, 0, 0);
         if (i == 0) {   // high-term products first; the chains of the middle and low terms fill the gaps in that order
 #pragma unroll

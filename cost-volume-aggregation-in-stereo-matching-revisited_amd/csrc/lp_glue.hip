@@ -4,23 +4,10 @@
 //   trilinear_lp   F.interpolate(scale_factor=(2,2,2), mode='trilinear') (cva.py:64), fp32 in -> 2-byte out
 // Same arithmetic as the fp32 kernels of pointwise.hip (count_include_pad=True: always / 27; align_corners=False weights
 // .25 / .75 with clamped ends); only the storage type of the large side differs.
-#include "dca_common.h"
+#include "dca_frag.h"
 #include "../../include/dca_hip.h"
 
 namespace {
-
-template <typename MT> __device__ __forceinline__ float g_lo(unsigned w) {
-  return (float)__builtin_bit_cast(MT, (unsigned short)(w & 0xffffu));
-}
-template <typename MT> __device__ __forceinline__ float g_hi(unsigned w) {
-  return (float)__builtin_bit_cast(MT, (unsigned short)(w >> 16));
-}
-template <typename MT> __device__ __forceinline__ unsigned g_pack2(float a, float b) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef MT mtx2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, mtx2));
-}
 
 // One thread per PAIR of outputs (ow0 = 2p, 2p + 1): per (kd, kh) row it needs the inputs w = 4p-1 .. 4p+3 = one
 // aligned 8-byte quad + the 2-byte sample left of it (hardware-predicated buffer loads: out-of-range rows / columns
@@ -45,8 +32,8 @@ __global__ __launch_bounds__(256) void avgpool3d_lp_kernel(const unsigned short*
       const int row = (d * Hi + h) * Wi;
       const u32x2 q = __builtin_amdgcn_raw_buffer_load_b64(xr, dca_pred_off((row + 4 * p) * 2, okr), 0, 0);
       const unsigned e = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(xr, dca_pred_off((row + 4 * p - 1) * 2, okr & (int)(p > 0)), 0, 0);
-      const float a0 = g_lo<MT>(q.x), a1 = g_hi<MT>(q.x), a2 = g_lo<MT>(q.y), a3 = g_hi<MT>(q.y);
-      s0 += g_lo<MT>(e) + a0 + a1;
+      const float a0 = lp_lo<MT>(q.x), a1 = lp_hi<MT>(q.x), a2 = lp_lo<MT>(q.y), a3 = lp_hi<MT>(q.y);
+      s0 += lp_lo<MT>(e) + a0 + a1;
       s1 += a1 + a2 + a3;
     }
   }
@@ -86,7 +73,7 @@ __global__ __launch_bounds__(256) void trilinear_up2_lp_kernel(const float* __re
       const float wa0 = pd ? 0.75f : 0.25f, wa1 = pd ? 0.25f : 0.75f, wb0 = ph ? 0.75f : 0.25f, wb1 = ph ? 0.25f : 0.75f;
       const float ox = wa0 * (wb0 * r0[a0][b0] + wb1 * r0[a0][b1]) + wa1 * (wb0 * r0[a1][b0] + wb1 * r0[a1][b1]);
       const float oy = wa0 * (wb0 * r1[a0][b0] + wb1 * r1[a0][b1]) + wa1 * (wb0 * r1[a1][b0] + wb1 * r1[a1][b1]);
-      q[((long)(2 * md + pd) * Ho + 2 * mh + ph) * Wi + mw] = g_pack2<MT>(ox, oy);
+      q[((long)(2 * md + pd) * Ho + 2 * mh + ph) * Wi + mw] = lp_pack2<MT>(ox, oy);
     }
 }
 

@@ -8,7 +8,7 @@
 //
 // All tensors are NC[D]HW fp32: channel c owns contiguous runs of S = D*H*W floats per sample, so
 // every kernel streams 16 B per lane along S.
-#include "dca_common.h"
+#include "dca_frag.h"
 #include "../../include/dca_hip.h"
 
 // ------------------------------------------------------------------------------------ BN statistics
@@ -207,11 +207,10 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
   if (ymax) dca_cmax_put(ym, ymax + (long)c * DCA_AMAX_CSLOTS + ch);
 }
 
-// x 2^e = h + l (+ <= 2^-22 relative): the two f16 terms of the f16x2 kernels
+// the two f16 terms of the f16x2 kernels (x2_split) as 16-bit patterns
 __device__ __forceinline__ void px2_split(float v, int e, unsigned short& h, unsigned short& l) {
-  const float u = ldexpf(v, e);       // exact
-  const _Float16 hh = (_Float16)u;
-  const _Float16 ll = (_Float16)(u - (float)hh);   // the residual is exact in fp32
+  _Float16 hh, ll;
+  x2_split(v, e, hh, ll);
   h = __builtin_bit_cast(unsigned short, hh);
   l = __builtin_bit_cast(unsigned short, ll);
 }

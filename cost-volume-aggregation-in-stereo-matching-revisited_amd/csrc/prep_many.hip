@@ -1,8 +1,8 @@
-// One launch that re-lays-out MANY convolution weights (both the fp32 wt[tap][cin][cout] images of conv3d_mfma.hip and
-// the pre-split bf16x3 fragment images of conv3d_bf16x3.hip): a training step re-packs every weight twice (forward and
-// backward-data layouts) right after the optimizer update, which as ~130 separate 5-us launches costs more GPU time
-// than the work itself.  The descriptors live in a device table built once (ops.PrepackPlan).
-#include "dca_common.h"
+// One launch that re-lays-out MANY convolution weights (the fp32 wt[tap][cin][cout] images of conv3d_mfma.hip and the
+// pre-split bf16x3 fragment images of conv3d_bf16x3.hip / conv1_x3.hip, laid out by the element functions of dca_frag.h): a
+// training step re-packs every weight twice (forward and backward-data layouts) right after the optimizer update, which as
+// ~130 separate 5-us launches costs more GPU time than the work itself.  The descriptors live in a device table built once (ops.PrepackPlan).
+#include "dca_frag.h"
 
 namespace {
 
@@ -17,56 +17,12 @@ struct PrepDesc {          // mirrored by ops.PrepackPlan (72 bytes)
   long total;              // elements of dst
 };
 
-__device__ __forceinline__ void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
-  h = (__bf16)v;
-  const float r1 = v - (float)h;
-  m = (__bf16)r1;
-  const float r2 = r1 - (float)m;
-  l = (__bf16)r2;
-}
-
-
 __global__ __launch_bounds__(256) void prep_many_kernel(const PrepDesc* __restrict__ table) {
   const PrepDesc d = table[blockIdx.y];
   for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < d.total; idx += (long)gridDim.x * 256) {
-    if (d.kind == 0) {
-      const int ab = d.Apad * d.Bpad;
-      const int tap = (int)(idx / ab), ai = (int)((idx / d.Bpad) % d.Apad), bi = (int)(idx % d.Bpad);
-      float v = 0.f;
-      if (ai < d.A && bi < d.Bn) {
-        const int st = d.flip ? d.K - 1 - tap : tap;
-        v = d.src_ab ? d.src[((long)ai * d.Btotal + d.b_off + bi) * d.K + st]
-                     : d.src[((long)(d.b_off + bi) * d.A + ai) * d.K + st];
-      }
-      ((float*)d.dst)[idx] = v;
-    } else if (d.kind == 2) {
-      const int j = idx & 7, lane = (idx >> 3) & 63, term = (int)((idx >> 9) % 3), chunk = (int)((idx >> 9) / 3);
-      const int bi = lane & 31, ai = chunk * 16 + 8 * (lane >> 5) + j;
-      float v = 0.f;
-      if (ai < d.A && bi < d.Bn)
-        v = d.src_ab ? d.src[(long)ai * d.Btotal + d.b_off + bi] : d.src[(long)(d.b_off + bi) * d.A + ai];
-      __bf16 h, m, l;
-      split3(v, h, m, l);
-      const __bf16 o = term == 0 ? h : (term == 1 ? m : l);
-      ((unsigned short*)d.dst)[idx] = __builtin_bit_cast(unsigned short, o);
-    } else {
-      const int j = idx & 7, lane = (idx >> 3) & 63;
-      long t = idx >> 9;
-      const int term = t % 3; t /= 3;
-      const int tap = t % 27; t /= 27;
-      const int chunk = t % d.NCH;
-      const int cblk = (int)(t / d.NCH);
-      const int bi = cblk * 32 + (lane & 31), ai = chunk * 16 + 8 * (lane >> 5) + j;
-      float v = 0.f;
-      if (ai < d.A && bi < d.Bn) {
-        const int st = d.flip ? 26 - tap : tap;
-        v = d.src_ab ? d.src[((long)ai * d.Bn + bi) * 27 + st] : d.src[((long)bi * d.A + ai) * 27 + st];
-      }
-      __bf16 h, m, l;
-      split3(v, h, m, l);
-      const __bf16 o = term == 0 ? h : (term == 1 ? m : l);
-      ((unsigned short*)d.dst)[idx] = __builtin_bit_cast(unsigned short, o);
-    }
+    if (d.kind == 0) ((float*)d.dst)[idx] = wt_f32_elem(d.src, idx, d.A, d.Bn, d.Apad, d.Bpad, d.K, d.src_ab, d.flip, d.Btotal, d.b_off);
+    else if (d.kind == 2) ((unsigned short*)d.dst)[idx] = w1x3_elem(d.src, idx, d.A, d.Bn, d.src_ab, d.Btotal, d.b_off);
+    else if (d.kind == 1) ((unsigned short*)d.dst)[idx] = wx3_elem(d.src, idx, d.A, d.Bn, d.NCH, d.src_ab, d.flip);
   }
 }
 

@@ -14,7 +14,7 @@
 // channel two ds_read_b128 fetch the 8 right-feature values R[x0-i0-4 .. x0-i0+3] that the 4 x 4 (disparity, x) outputs
 // need, so an output costs CPG FMAs plus 1/8 LDS read -- the kernel sits on the volume's HBM write, not on the VALU
 // (the round-1 kernel spent ~19 instructions per output on a sliding register window and 4-byte LDS reads).
-#include "dca_common.h"
+#include "dca_frag.h"
 #include "../../include/dca_hip.h"
 
 namespace {
@@ -40,30 +40,21 @@ template <typename OT> struct Out;
 #ifndef VF_NT
 #define VF_NT 1
 #endif
-typedef float vf_f32x4 __attribute__((ext_vector_type(4)));
 template <> struct Out<float> {
   static __device__ __forceinline__ void store4(float* p, const float (&o)[4]) {
-    const vf_f32x4 v = {o[0], o[1], o[2], o[3]};
-    if (VF_NT) __builtin_nontemporal_store(v, (vf_f32x4*)p);
-    else *(vf_f32x4*)p = v;
+    const f32x4 v = {o[0], o[1], o[2], o[3]};
+    if (VF_NT) __builtin_nontemporal_store(v, (f32x4*)p);
+    else *(f32x4*)p = v;
   }
 };
-template <typename MT> __device__ __forceinline__ unsigned vf_pack2(float a, float b) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef MT mtx2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, mtx2));
-}
-typedef unsigned vf_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned vf_u32x4 __attribute__((ext_vector_type(4)));
 template <> struct Out<__bf16> {
   static __device__ __forceinline__ void store4(__bf16* p, const float (&o)[4]) {
-    *(vf_u32x2*)p = vf_u32x2{vf_pack2<__bf16>(o[0], o[1]), vf_pack2<__bf16>(o[2], o[3])};
+    *(u32x2*)p = u32x2{lp_pack2<__bf16>(o[0], o[1]), lp_pack2<__bf16>(o[2], o[3])};
   }
 };
 template <> struct Out<_Float16> {
   static __device__ __forceinline__ void store4(_Float16* p, const float (&o)[4]) {
-    *(vf_u32x2*)p = vf_u32x2{vf_pack2<_Float16>(o[0], o[1]), vf_pack2<_Float16>(o[2], o[3])};
+    *(u32x2*)p = u32x2{lp_pack2<_Float16>(o[0], o[1]), lp_pack2<_Float16>(o[2], o[3])};
   }
 };
 

@@ -1141,9 +1141,8 @@ class PrepackPlan:
         for out, desc, tensors in self.entries.values():
             kind, A, Bn, Apad, Bpad, K, src_ab, flip, Btotal, b_off = desc
             nch = (A + 15) // 16
-            total = out.numel() - (8 if kind == 3 else 0)    # kind 3: f16 elements in front of the 16-byte scale tail
             rows.append(struct.pack("<QQ12iq", tensors[0].data_ptr(), out.data_ptr(), kind, A, Bn, Apad, Bpad, K, src_ab,
-                                    flip, Btotal, b_off, nch, 0, total))
+                                    flip, Btotal, b_off, nch, 0, out.numel()))
         self.n = len(rows)
         if self.n:
             dev = next(iter(self.entries.values()))[0].device
