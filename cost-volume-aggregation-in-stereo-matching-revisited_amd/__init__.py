@@ -4,8 +4,10 @@ Import as `dcanet_amd` (see the shim at the repository root).  Mirrors the refer
     dcanet_amd.models.submodule      <- models/submodule.py   (build_gwc_volume, disparity_regression, ...)
     dcanet_amd.models.gwcnet_dca_g   <- models/gwcnet_dca_g.py (GwcNet, GwcNet_G, GwcNet_GC)
     dcanet_amd.models.augment.*      <- models/augment/{cva,semantic_level,SelfAttention_bn}.py
+    dcanet_amd.evaluation            <- main_dca.py:66-120,143-246 (SegmentationMetric, mytest; EvalStep)
 """
 from . import _lib  # noqa: F401
 from . import ops  # noqa: F401
+from . import evaluation  # noqa: F401
 
-__all__ = ["ops", "_lib"]
+__all__ = ["ops", "_lib", "evaluation"]

@@ -8,7 +8,7 @@ LIB_PATH = os.path.join(HERE, "libdca_hip.so")
 
 _p, _i, _l, _f, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_double
 
-ABI_VERSION = 19  # == DCA_ABI_VERSION of include/dca_hip.h
+ABI_VERSION = 20  # == DCA_ABI_VERSION of include/dca_hip.h
 
 # name -> (restype, argtypes); mirrors include/dca_hip.h one to one
 SIGNATURES = {
@@ -96,6 +96,11 @@ SIGNATURES = {
     "dca_focal_loss_workspace": (_l, [_i, _i, _l]),
     "dca_focal_loss_fwd": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _l, _f, _p]),
     "dca_focal_loss_bwd": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _i, _l, _f, _p]),
+    "dca_disp_metrics_workspace": (_l, [_i, _i, _i]),
+    "dca_disp_metrics": (_i, [_p] * 5 + [_i] * 5 + [_f, _p]),
+    "dca_region_confusion": (_i, [_p] * 5 + [_i] * 7 + [_p]),
+    "dca_eval_state_len": (_l, [_i]),
+    "dca_eval_accumulate": (_i, [_p, _p, _p] + [_i] * 5 + [_p]),
 }
 
 _lib = None

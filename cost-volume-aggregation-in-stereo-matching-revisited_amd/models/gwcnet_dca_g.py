@@ -135,13 +135,15 @@ class GwcNet(nn.Module):
                 m.bias.data.zero_()
 
     # ---- the hot path proper: 1/4-res features -> 1/4-res disparity (+ training heads)
-    def hot_path(self, gwc_left, gwc_right, concat_left=None, concat_right=None):
+    def hot_path(self, gwc_left, gwc_right, concat_left=None, concat_right=None, aux_volumes=False):
         with ops.batched_bn_counters():   # one multi-tensor add for all BatchNorm step counters
-            return self._hot_path(gwc_left, gwc_right, concat_left, concat_right)
+            return self._hot_path(gwc_left, gwc_right, concat_left, concat_right, aux_volumes)
 
-    def _hot_path(self, gwc_left, gwc_right, concat_left=None, concat_right=None):
+    def _hot_path(self, gwc_left, gwc_right, concat_left=None, concat_right=None, aux_volumes=False):
         """reference gwcnet_dca_g.py:216-239 (+ :244-275 when training).  Returns a dict with `pred4_q`
-        (B,1,H/4,W/4) in 1/4-res pixels, `prob_volume2` and, in training mode, the auxiliary heads."""
+        (B,1,H/4,W/4) in 1/4-res pixels, `prob_volume2` and, in training mode, the auxiliary heads.  `aux_volumes`
+        adds `prob_volume1` and `prob_volume3` (fp32, also under ops.reduced_precision): the three region heads the
+        reference's evaluation step scores (main_dca.py:211-213)."""
         d = self.maxdisp // 4
         lp = ops._lp_dtype()
         if lp is not None and (self.training or torch.is_grad_enabled()):
@@ -169,6 +171,8 @@ class GwcNet(nn.Module):
         prob_volume3, out3 = self.cva3(out2)
         logits3 = self.classif3(out3).squeeze(1)
         res = {"pred4_q": ops.softargmin(logits3), "prob_volume2": prob_volume2}
+        if aux_volumes:
+            res["prob_volume1"], res["prob_volume3"] = prob_volume1, prob_volume3
         if self.training:
             res["pred0"] = ops.softmax_dim1(logits0.squeeze(1))
             res["pred_dca1"] = ops.softmax_dim1(ops.trilinear_upsample(prob_volume1, 2).squeeze(1))

@@ -1787,3 +1787,88 @@ def conv3d_c1_lp(x, weight):
     with torch.cuda.device_of(x):
         _chk(_L().dca_conv3d_c1_gather(_ptr(T), _ptr(y), N, D, H, W, _stream()), "dca_conv3d_c1_gather")
     return y
+
+
+# ------------------------------------------------------------------------------------------------
+# Evaluation step (main_dca.py:143-246 `mytest`): disparity metrics, region confusion matrices, run state
+# (csrc/eval_metrics.hip; state layout in include/dca_hip.h).  No launch synchronises; all buffers are torch's.
+# ------------------------------------------------------------------------------------------------
+EVAL_REC = 8             # DCA_EVAL_REC
+EVAL_STATE_HEAD = 32     # DCA_EVAL_STATE_HEAD
+EVAL_MAX_CLASSES = 64    # DCA_EVAL_MAX_CLASSES
+
+
+def disp_metrics(pred, gt, maxdisp, mask=None):
+    """Per-image error statistics of a (padded) prediction against the ground truth in one pass: pred (B,Hp,Wp) or
+    (B,1,Hp,Wp) with Hp >= H, Wp >= W (rows padded on top, columns on the right: the crop of main_dca.py:171-174 is
+    done by addressing), gt (B,H,W), mask bool (B,H,W) or None (gt > 0 & gt < maxdisp).  Returns (B,8) float64:
+    #mask, #(gt>0), sum e, sum smooth_l1(e), #(e>1), #(e>2), #(e>3), #(e>3 & e/|gt|>0.05), e = |pred - gt| in fp32."""
+    pred, gt = _req(pred, "disp_metrics"), _req(gt, "disp_metrics")
+    if pred.dim() == 4 and pred.shape[1] == 1:
+        pred = pred[:, 0]
+    if pred.dim() != 3 or gt.dim() != 3 or pred.shape[0] != gt.shape[0]:
+        raise RuntimeError(f"disp_metrics: expected pred (B,Hp,Wp) and gt (B,H,W), got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    (B, Hp, Wp), (H, W) = pred.shape, gt.shape[1:]
+    if Hp < H or Wp < W:
+        raise RuntimeError("disp_metrics: the prediction is smaller than the ground truth")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+            raise RuntimeError("disp_metrics: the mask must be on the ROCm device; there is no CPU fallback")
+        if mask.dtype != torch.bool or mask.shape != gt.shape:
+            raise RuntimeError("disp_metrics: expected a bool mask of the ground truth's shape")
+        mask = mask.contiguous()
+    rec = torch.empty((B, EVAL_REC), device=gt.device, dtype=torch.float64)
+    with torch.cuda.device_of(gt):
+        ws = torch.empty(_L().dca_disp_metrics_workspace(B, H, W), device=gt.device, dtype=torch.uint8)
+        _chk(_L().dca_disp_metrics(_ptr(pred), _ptr(gt), _ptr(mask), _ptr(rec), _ptr(ws), B, H, W, Hp - H, Wp - W,
+                                   float(maxdisp), _stream()), "dca_disp_metrics")
+    return rec
+
+
+def region_confusion(volumes, gt):
+    """Confusion matrices of 1..3 region-probability volumes (B,C,hp,wp) (or (B,1,C,hp,wp)) at 1/8 resolution against
+    label = floor(adaptive_avg_pool2d(gt / 8, (H//8, W//8))), gt (B,H,W); prediction = arg-max over C at row
+    i + (hp - H//8), column j.  Returns (len(volumes), C, C) int64, rows = label, columns = prediction."""
+    if isinstance(volumes, torch.Tensor):
+        volumes = [volumes]
+    vols = []
+    for v in volumes:
+        v = _req(v, "region_confusion")
+        vols.append(v[:, 0] if v.dim() == 5 and v.shape[1] == 1 else v)
+    gt = _req(gt, "region_confusion")
+    if not 1 <= len(vols) <= 3 or any(v.dim() != 4 or v.shape != vols[0].shape for v in vols):
+        raise RuntimeError("region_confusion: expected 1 to 3 volumes (B,C,hp,wp) of one shape")
+    (B, C, hp, wp), (H, W) = vols[0].shape, gt.shape[1:]
+    if gt.dim() != 3 or gt.shape[0] != B or H < 8 or W < 8 or hp < H // 8 or wp < W // 8 or C > EVAL_MAX_CLASSES:
+        raise RuntimeError(f"region_confusion: volumes {tuple(vols[0].shape)} do not fit the ground truth {tuple(gt.shape)} "
+                           f"(C <= {EVAL_MAX_CLASSES})")
+    cm = torch.empty((len(vols), C, C), device=gt.device, dtype=torch.int64)
+    p = [_ptr(v) for v in vols] + [None] * (3 - len(vols))
+    with torch.cuda.device_of(gt):
+        _chk(_L().dca_region_confusion(p[0], p[1], p[2], _ptr(gt), _ptr(cm), len(vols), B, C, hp, wp, H, W, _stream()),
+             "dca_region_confusion")
+    return cm
+
+
+def eval_state(num_classes, device):
+    """zeroed run state of `eval_accumulate` (float64; layout: include/dca_hip.h)"""
+    n = _L().dca_eval_state_len(int(num_classes))
+    if n <= 0:
+        raise RuntimeError(f"eval_state: 1 <= num_classes <= {EVAL_MAX_CLASSES}")
+    return torch.zeros(n, device=device, dtype=torch.float64)
+
+
+def eval_accumulate(state, rec, cm, gt_shape):
+    """Adds one batch -- rec of `disp_metrics`, cm of `region_confusion` -- to the run state, in place."""
+    for t, dt, name in ((state, torch.float64, "state"), (rec, torch.float64, "rec"), (cm, torch.int64, "cm")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"eval_accumulate: {name} must be on the ROCm device; there is no CPU fallback")
+        if t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError(f"eval_accumulate: {name} must be a contiguous {dt} tensor")
+    nvol, C = cm.shape[0], cm.shape[1]
+    if state.numel() != _L().dca_eval_state_len(C) or rec.dim() != 2 or rec.shape[1] != EVAL_REC or cm.shape[2] != C:
+        raise RuntimeError("eval_accumulate: state / rec / cm do not fit together")
+    with torch.cuda.device_of(state):
+        _chk(_L().dca_eval_accumulate(_ptr(rec), _ptr(cm), _ptr(state), rec.shape[0], nvol, C, int(gt_shape[-2]),
+                                      int(gt_shape[-1]), _stream()), "dca_eval_accumulate")
+    return state

@@ -23,7 +23,7 @@ extern "C" {
 
 /* Bumped whenever an argument list below changes; the ctypes loader (_lib.py) refuses a library built from another
  * version of this header. */
-#define DCA_ABI_VERSION 19
+#define DCA_ABI_VERSION 20
 int dca_abi_version(void);
 
 /* storage types of the reduced-precision inference path (0 = fp32) */
@@ -410,6 +410,61 @@ int dca_deconv3d_lp_forward(const float* x, const void* wx, void* y, const float
  * F.interpolate(scale_factor=(2,2,2), mode='trilinear') (cva.py:64): x (NC,Di,Hi,Wi) fp32 -> y (NC,2Di,2Hi,2Wi) 2-byte. */
 int dca_avgpool3d_lp_fwd(const void* x, float* y, long NC, int Di, int Hi, int Wi, int dtype, hipStream_t stream);
 int dca_trilinear_up2_lp_fwd(const float* x, void* y, long NC, int Di, int Hi, int Wi, int dtype, hipStream_t stream);
+
+/* ---- evaluation step (eval_metrics.hip): the tail of main_dca.py:143-246 `mytest` without a host round trip -------------
+ * All results are bitwise reproducible run to run: counts are integers, floating sums are fp64 per-workgroup partials
+ * reduced in a fixed order.
+ *
+ * dca_disp_metrics: pred (B,H+top_pad,W+right_pad) fp32 -- the padded frame; the crop `[:, top_pad:, :W]` of
+ * main_dca.py:171-174 is done by addressing -- gt (B,H,W) fp32, mask (B,H,W) bytes (non-zero = use) or NULL:
+ * mask = gt > 0 && gt < maxdisp (main_dca.py:151).  rec: (B, DCA_EVAL_REC) doubles, one record PER IMAGE, with
+ * e = |pred - gt| evaluated in fp32:
+ *   [0] #mask  [1] #(gt > 0)  [2] sum e  [3] sum smooth_l1(e), beta 1  [4] #(e > 1)  [5] #(e > 2)  [6] #(e > 3)
+ *   [7] #(e > 3 && e / |gt| > 0.05)
+ * workspace: dca_disp_metrics_workspace(B, H, W) bytes. */
+#define DCA_EVAL_REC 8
+long dca_disp_metrics_workspace(int B, int H, int W);
+int dca_disp_metrics(const float* pred, const float* gt, const unsigned char* mask, double* rec, void* workspace, int B,
+                     int H, int W, int top_pad, int right_pad, float maxdisp, hipStream_t stream);
+/* dca_region_confusion: nvol (1..3) volumes (B,C,hp,wp) fp32 at 1/8 resolution, gt (B,H,W).  With h = H / 8, w = W / 8
+ * (integer division): label(i,j) = floor(adaptive_avg_pool2d(gt / 8, (h, w))) (main_dca.py:210; window
+ * [floor(i H / h), ceil((i + 1) H / h)), summed row-major in fp32, one division), prediction = arg-max over C (lowest
+ * index on ties) of the volume at row i + (hp - h), column j (main_dca.py:211-213: `argmax(1)[:, 1:, ...]` at 540 rows
+ * padded to 544).  Labels outside [0, C) are skipped (main_dca.py:98-104).  cm: (nvol, C, C) int64, rows = label,
+ * columns = prediction, counts of THIS call (zeroed by the launcher).  C <= DCA_EVAL_MAX_CLASSES. */
+#define DCA_EVAL_MAX_CLASSES 64
+int dca_region_confusion(const float* vol0, const float* vol1, const float* vol2, const float* gt, long long* cm,
+                         int nvol, int B, int C, int hp, int wp, int H, int W, hipStream_t stream);
+/* dca_eval_accumulate: adds one batch (rec of dca_disp_metrics, cm of dca_region_confusion) to the run state, a vector of
+ * dca_eval_state_len(C) = DCA_EVAL_STATE_HEAD + 3 C C doubles that the caller zeroes at the start of a run.  Every entry
+ * is a sum or a count, so the states of several ranks add up:
+ *   [DCA_EVAL_BATCHES]         batches seen
+ *   [DCA_EVAL_SUMS + 0..9]     sum over batches of the values `mytest` returns: loss (smooth-L1 mean), epe, 1px, 3px over
+ *                              the batch's masked pixels; mpa0, mpa1, mpa2; mIoU0, mIoU1, mIoU2 (np.nanmean over classes:
+ *                              0/0 classes left out).  Two quirks of the reference are kept: a batch with an empty mask
+ *                              adds 0 to all ten and still counts (main_dca.py:177-195); the metric object is never reset
+ *                              between the heads, so mpa1 / mIoU1 come from CM0 + CM1 and mpa2 / mIoU2 from
+ *                              CM0 + CM1 + CM2 (main_dca.py:215-232)
+ *   [DCA_EVAL_IMG_KEPT]        images that pass the 10 % rule of utils/metrics.py (mask mean / (gt > 0) mean >= 0.1, fp32)
+ *                              and have a non-empty mask
+ *   [DCA_EVAL_IMG_EPE], [DCA_EVAL_IMG_D1], [DCA_EVAL_IMG_THRES + 0..2]   sum over those images of the per-image EPE, D1,
+ *                              Thres(1), Thres(2), Thres(3)
+ *   [DCA_EVAL_IMG_SEEN]        images seen          [DCA_EVAL_PIXELS]  masked pixels seen
+ *   [.. DCA_EVAL_STATE_HEAD)   reserved, zero
+ *   [DCA_EVAL_STATE_HEAD + (k C + label) C + pred]   confusion matrix of head k alone, summed over the run
+ * H, W: the size of the ground truth (for the 10 % rule). */
+#define DCA_EVAL_BATCHES 0
+#define DCA_EVAL_SUMS 1
+#define DCA_EVAL_IMG_KEPT 11
+#define DCA_EVAL_IMG_EPE 12
+#define DCA_EVAL_IMG_D1 13
+#define DCA_EVAL_IMG_THRES 14
+#define DCA_EVAL_IMG_SEEN 17
+#define DCA_EVAL_PIXELS 18
+#define DCA_EVAL_STATE_HEAD 32
+long dca_eval_state_len(int C);
+int dca_eval_accumulate(const double* rec, const long long* cm, double* state, int B, int nvol, int C, int H, int W,
+                        hipStream_t stream);
 
 #ifdef __cplusplus
 }
