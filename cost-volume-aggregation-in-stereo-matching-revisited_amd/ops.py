@@ -825,6 +825,11 @@ class _Conv3d(torch.autograd.Function):
             raise RuntimeError("conv3d.backward: expected the packed px2 gradient of the BatchNorm behind this convolution "
                                "(the tag was lost on the way through autograd)")
         dy = _req(dy, "conv3d.backward", packed_ok=True)
+        if ctx.x_twin is not None and not _is_packed(dy) and x.shape[-1] % 4:
+            # the f16x2 weight-gradient kernel pairs a packed operand with an fp32 one only at W % 4 == 0, and an fp32 x of
+            # such a width never gets a packed dy (_pack_dy_ok): the weight gradient reads the fp32 x and takes the kernel
+            # that serves this width; the forward read the twin, which holds the same values
+            xw = x
         ksize = weight.shape[2]
         K = ksize ** 3
         gx = gx2 = gw = None
@@ -1215,7 +1220,9 @@ def bn_act(y, bn, slope=1.0, res_pre=None, res_post=None, stats_part=None, pack_
     stats_part: batch-statistics partial sums of y from the producing convolution (`_Conv3d` with want_stats), if it made them.
     pack_out: True -- the result has ONE consumer, an f16x2 3x3x3 stride-1 convolution: write it in the packed px2 operand
     format instead of fp32; "both" -- several consumers, ONE of them such a convolution: fp32 result plus a packed twin that
-    this convolution and its weight gradient pick up (training BatchNorm only; plain fp32 otherwise).  pack_dy: see _BnAct."""
+    this convolution and its weight gradient pick up (training BatchNorm only; plain fp32 otherwise).  The packed forms do
+    not depend on the width; at W % 4 != 0 the twin's reader gets an fp32 gradient (_pack_dy_ok) and takes the fp32 tensor
+    for its weight gradient (_Conv3d.backward), the forward still reads the twin.  pack_dy: see _BnAct."""
     momentum = 0.1 if bn.momentum is None else bn.momentum
     training = bn.training or bn.running_mean is None
     if _lp_dtype() is not None:
@@ -1289,7 +1296,11 @@ def convbn3d(x, conv, bn, slope=1.0, res_pre=None, res_post=None, x2=None, alias
     batch statistics -> apply, each with a HIP backward.
     pack_out: the caller promises that the result has ONE consumer and that it is a 3x3x3 stride-1 convolution through this
     function: in training the BatchNorm apply pass then writes the packed px2 operand format (csrc/dca_common.h) instead
-    of fp32 (never with residuals; silently fp32 wherever the packed form does not apply)."""
+    of fp32 (never with residuals); "both": fp32 plus a packed twin for the one such convolution among several consumers
+    (bn_act; residuals allowed).  Silently fp32
+    wherever the packed form does not apply: eval / no-grad, channel counts that are not multiples of 8, DCA_PACK=0 or
+    another kernel family.  Any width works: an operand that cannot be paired in the f16x2 weight-gradient kernel (an fp32
+    tensor or gradient at W % 4 != 0 beside a packed one) is read as fp32 by the kernel that serves that width."""
     transposed = isinstance(conv, torch.nn.ConvTranspose3d)
     stride = conv.stride[0]
     if alias:

@@ -1,0 +1,599 @@
+"""The hot path at quarter-res widths that are NOT multiples of four (W4 % 4 == 2, odd eighth-res width).
+
+The reference model takes any image whose width is a multiple of 8, so such a W4 is a legal input, but ops.py picks a
+kernel for every convolution, weight gradient, volume and BatchNorm pass from predicates on the innermost extent
+(`W % 4`, `Wo % 4`, `S % 4`, `maxdisp % 4`): the fast kernels serve the aligned side, the other side falls back to
+single-voxel staging or the generic fp32 MFMA kernels.  This module runs the unaligned side end to end (train step,
+eval forward eager / frozen / graphed / inference_mode), through layer chains with packed px2 operands, and kernel by
+kernel, each against the CPU oracle / PyTorch in fp64.
+
+Shapes (features (B, 320[+12], H4, W4); quarter-res extents even -- the model's stride-2 backward needs that):
+
+    id   B  H4  W4  maxdisp   reaches
+    u22  2  10  22  48        D4 = 12; eighth-res 6 x 5 x 11 (S % 4 == 2): 1x1x1 convs / logit head off the bf16x3 and
+                              fused-wgrad kernels, deconv off deconv3d_x3, volume off the fused builder (width alone)
+    u26  1   6  26  40        D4 = 10 (unaligned too); eighth-res 5 x 3 x 13 (odd S); two 16-wide conv tiles, 2nd partial
+    u18  1  10  18  64        D4 = 16; eighth-res 8 x 5 x 9: S % 4 == 0 again at an odd width
+    a24  2  10  24  48        aligned control for u22 (same seed tags), fused volume builder
+
+Seeds: every tensor is `seeded_tensor(f"unal.{SEED_TAG[id]}.<name>", shape)`; SEED_TAG below is the record of the chosen
+seed suffixes.  Reference stability (tests/test_unaligned_reference_cpu.py checks it without a GPU, and every test here
+re-checks it on the data it uses): the context injection takes an arg-max over predictions, so the fp32 oracle must agree
+with the fp64 oracle to a quarter of each forward gate and give the identical arg-max maps k*; a seed that does not is
+replaced, never the gate.
+
+Gates.  Forward heads / eval outputs: the project's gates of test_gpu_configs.py (2e-5 x max(1, |ref|max) for the
+softmax heads and prob_volume2, 2.5e-4 for pred4_q, 1e-3 for pred_dca3) against the fp64 oracle.  BatchNorm running
+statistics, per buffer on relative L2 against the fp64 oracle: `err_gpu <= 4 x err_oracle32 + 1e-5`, where err_oracle32
+is the fp32 CPU oracle's own distance to the fp64 oracle at the same shape and seeds (factor 4 = two bits: f16x2 operands
+carry 22 bits against fp32's 24; 1e-5 = the project's kernel-level rel-L2 gate).
+
+Gradients: the same yardstick was meant to gate every gradient tensor, but the aligned control a24 misses it (table
+below: ratio up to 56 for G, ~6000 for GC), so the yardstick is wrong, not the width, and the gradients of all four shapes
+are held to the project's absolute gates instead (test_train_step_d192_row_crop_all_gradients: median over the tensors
+<= 3e-3, every tensor <= 8e-3, relative L2 against the fp64 oracle).  The yardstick is still printed per tensor.  Why it
+fails: the step is discontinuous not only in the arg-max but in the sign of every (leaky-)ReLU input.  An input within
+rounding distance of zero changes sign between two fp32-grade implementations, the gradient loses or gains that
+element, and every gradient upstream moves by about 1 / sqrt(elements) ~ 1e-3.  The errors are accordingly bimodal --
+~2e-6 (the fp32 oracle's own level) where no sign differs, ~1e-3 where one does -- and which case a run falls into
+changes with the kernel family at the same shape.  The fp32 oracle has such events of its own: at u22 GC exactly one
+activation input (of 42240 in that layer) has the other sign than in fp64 and the oracle's error jumps from 3e-6 to
+1.7e-3; the GPU run shares that event to four digits (8.691e-4 on dres1.2.0.weight in both).  The GPU has its own:
+at a24 GC two of the 184320 inputs of classif0's ReLU (|input| 4e-7) have the other sign than in the fp64 oracle, and
+classif0.0.0.weight, the worst tensor of the table, is 7.8e-3 off (97 % of the gate: the kernels are deterministic, so
+the figure is stable); at u22 G one of 168960 in classif1 (classif1.0.0.weight 2.0e-3); at u26 G none (max 4.6e-6).
+Tensors whose reference norm is below 1e-6 are skipped; their share is asserted to stay <= 5 %.
+
+Measured on an MI355X (median / max over the 150 gradient tensors of err_gpu, err_oracle32 and err_gpu / err_oracle32;
+the same table is kept in profiles/unaligned_gradients.txt):
+
+    shape     err_gpu                 err_oracle32            ratio
+    u22 g     3.515e-06 / 2.019e-03   1.801e-06 / 5.226e-06   1.18 / 1602.66
+    u22 gc    3.186e-06 / 1.745e-03   2.913e-06 / 1.745e-03   1.00 / 1.80
+    u26 g     1.841e-06 / 4.641e-06   1.406e-06 / 3.496e-06   1.34 / 2.96
+    u26 gc    1.939e-06 / 4.919e-06   1.487e-06 / 3.636e-06   1.30 / 2.51
+    u18 g     6.967e-04 / 4.373e-03   1.287e-06 / 3.247e-06   327.68 / 3623.11
+    u18 gc    1.857e-06 / 4.715e-06   1.446e-06 / 3.654e-06   1.34 / 2.22
+    a24 g     1.080e-05 / 1.489e-04   1.820e-06 / 4.408e-06   6.20 / 56.09
+    a24 gc    8.188e-04 / 7.762e-03   1.021e-04 / 1.043e-03   11.00 / 5966.38
+
+Running statistics at all eight: err_gpu <= 1.4e-07, err_oracle32 <= 8.8e-08, ratio <= 2.0.
+"""
+import functools
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import dcanet_oracle as O
+from oracle.seeded import seeded_tensor
+from test_gpu_configs import load_seeded, rel_l2
+from test_gpu_parity import (_GradProbe, _bn_ref, _chan_err, _family, _unpack_px2, close, close_l2, cpu_leaf, gpu)
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+SHAPES = {            # id: (B, H4, W4, maxdisp)
+    "u22": (2, 10, 22, 48),
+    "u26": (1, 6, 26, 40),
+    "u18": (1, 10, 18, 64),
+    "a24": (2, 10, 24, 48),
+}
+SEED_TAG = {"u22": "s22", "u26": "s26", "u18": "s18", "a24": "s22"}      # a24 = the control of u22: same seed tags
+UNALIGNED = ["u22", "u26", "u18"]
+HEADS = ["pred0", "pred_dca1", "pred_dca2", "pred1", "pred2", "pred_dca3", "pred4_q"]
+EVAL_OUT = ["pred4_q", "prob_volume2"]
+
+
+def head_tol(key, ref):
+    if key == "pred_dca3":
+        return 1e-3
+    if key == "pred4_q":
+        return 2.5e-4
+    return 2e-5 * max(1.0, ref.abs().max().item())
+
+
+def features(sid, concat):
+    B, h, w, _ = SHAPES[sid]
+    C = 320 + (12 if concat else 0)
+    tag = f"unal.{SEED_TAG[sid]}"
+    return seeded_tensor(f"{tag}.fL", (B, C, h, w)), seeded_tensor(f"{tag}.fR", (B, C, h, w))
+
+
+def split(a, b, concat):
+    """the arguments of hot_path: (gwc_left, gwc_right[, concat_left, concat_right])"""
+    if concat:
+        return a[:, :320], b[:, :320], a[:, 320:], b[:, 320:]
+    return a, b
+
+
+def seeded_loss(r, sid, dtype=torch.float32):
+    """the seven-head seeded loss of test_train_step_d192_row_crop_all_gradients"""
+    loss = 0
+    for i, k in enumerate(HEADS):
+        g = seeded_tensor(f"unal.{SEED_TAG[sid]}.g{i}", r[k].shape).to(dtype)
+        loss = loss + (r[k] * g.to(r[k].device)).sum()
+    return loss
+
+
+def _kstar(r):
+    """the arg-max maps of the three context injections (oracle.context_inject: softmax, then argmax over the bins)"""
+    return [F.softmax(r[f"prob_volume{i}"].squeeze(1), dim=1).argmax(1) for i in (1, 2, 3)]
+
+
+def _oracle_hot(sd, a, b, sid, concat, training):
+    args = split(a, b, concat)
+    return O.hot_path(sd, args[0], args[1], SHAPES[sid][3], training, 40, *(args[2:] if concat else (None, None)))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_train(sid, concat, dtype):
+    """one train-mode step of the CPU oracle in `dtype`: heads, gradients of both feature maps and of every parameter
+    tensor, running statistics after the step, k* maps"""
+    sd = O.clone_sd(O.seeded_state_dict(O.hot_path_shapes(concat)), dtype)
+    names = [k for k, v in sd.items() if v.is_floating_point() and "running" not in k]
+    for k in names:
+        sd[k].requires_grad_()
+    fL, fR = features(sid, concat)
+    a, b = fL.to(dtype).requires_grad_(), fR.to(dtype).requires_grad_()
+    r = _oracle_hot(sd, a, b, sid, concat, True)
+    grads = torch.autograd.grad(seeded_loss(r, sid, dtype), [a, b] + [sd[k] for k in names])
+    return dict(heads={k: r[k].detach() for k in HEADS}, names=["fL", "fR"] + names, grads=[g.detach() for g in grads],
+                stats={k: v.detach() for k, v in sd.items() if "running" in k}, kstar=_kstar(r))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_eval(sid, concat, dtype):
+    sd = O.clone_sd(O.seeded_state_dict(O.hot_path_shapes(concat)), dtype)
+    fL, fR = features(sid, concat)
+    with torch.no_grad():
+        r = _oracle_hot(sd, fL.to(dtype), fR.to(dtype), sid, concat, False)
+    return dict(out={k: r[k] for k in EVAL_OUT}, kstar=_kstar(r))
+
+
+def reference_stability(sid, concat):
+    """the condition on the REFERENCE (no GPU involved): fp32 oracle within a quarter of each forward gate of the fp64
+    oracle, identical k* maps, train step and eval forward.  Returns the list of violations."""
+    bad = []
+    for mode, fn, field in (("train", oracle_train, "heads"), ("eval", oracle_eval, "out")):
+        r64, r32 = fn(sid, concat, torch.float64), fn(sid, concat, torch.float32)
+        for k, ref in r64[field].items():
+            err = (r32[field][k].double() - ref).abs().max().item()
+            tol = head_tol(k, ref) / 4
+            if not err <= tol:
+                bad.append(f"{sid} {'gc' if concat else 'g'} {mode} {k}: |o32 - o64| = {err:.3e} > {tol:.1e}")
+        for i, (k64, k32) in enumerate(zip(r64["kstar"], r32["kstar"])):
+            if not torch.equal(k64, k32):
+                bad.append(f"{sid} {'gc' if concat else 'g'} {mode} k* of cva{i + 1}: {(k64 != k32).sum().item()} pixels differ")
+    return bad
+
+
+def yardstick_rows(names, got, r64, r32):
+    """[(name, err_gpu, err_oracle32, |ref|)] on relative L2 against the fp64 oracle"""
+    return [(n, rel_l2(g, a), rel_l2(b, a), a.norm().item()) for n, g, a, b in zip(names, got, r64, r32)]
+
+
+def _live(rows, what):
+    """tensors with |ref| < 1e-6 are skipped, at most 5 % of them"""
+    live = [r for r in rows if r[3] >= 1e-6]
+    assert len(rows) - len(live) <= 0.05 * len(rows), f"{what}: {len(rows) - len(live)} of {len(rows)} tensors skipped"
+    return live
+
+
+def check_yardstick(rows, what):
+    """err_gpu <= 4 x err_oracle32 + 1e-5 per tensor"""
+    bad = [(n, f"{eg:.3e}", f"{eo:.3e}") for n, eg, eo, _ in _live(rows, what) if not eg <= 4.0 * eo + 1e-5]
+    assert not bad, f"{what}: err_gpu > 4 x err_oracle32 + 1e-5 for {bad}"
+
+
+def check_absolute(rows, what):
+    """the gradient gates of test_train_step_d192_row_crop_all_gradients: median <= 3e-3, every tensor <= 8e-3"""
+    live = _live(rows, what)
+    errs = sorted(eg for _, eg, _, _ in live)
+    assert errs[len(errs) // 2] <= 3e-3, f"{what}: median per-tensor gradient error {errs[len(errs) // 2]:.3e}"
+    bad = [(n, f"{eg:.3e}") for n, eg, _, _ in live if not eg <= 8e-3]
+    assert not bad, f"{what}: {bad}"
+
+
+def summary(rows):
+    live = [r for r in rows if r[3] >= 1e-6]
+    eg, eo = sorted(r[1] for r in live), sorted(r[2] for r in live)
+    ratio = sorted(r[1] / max(r[2], 1e-30) for r in live)
+    med = lambda v: v[len(v) // 2]
+    return (f"err_gpu {med(eg):.3e} / {eg[-1]:.3e}   err_oracle32 {med(eo):.3e} / {eo[-1]:.3e}   "
+            f"ratio {med(ratio):.2f} / {ratio[-1]:.2f}   tensors {len(live)}")
+
+
+# ------------------------------------------------------------------------------------- (a) train step
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("variant", ["g", "gc"])
+@pytest.mark.parametrize("sid", UNALIGNED + ["a24"])
+def test_train_step_unaligned_width_all_gradients(sid, variant, capsys):
+    """GwcNet.hot_path in train mode at the shapes of the module docstring: all seven heads, the gradient of both feature
+    maps and of EVERY parameter tensor, and the BatchNorm running statistics after the step, against the fp64 oracle (gates:
+    module docstring).  a24 is the aligned control.  The fp32-oracle yardstick is printed per tensor beside the error but
+    not asserted for the gradients: the control misses it (module docstring), so the absolute gates hold for all four
+    shapes."""
+    from dcanet_amd.models.gwcnet_dca_g import GwcNet
+    concat = variant == "gc"
+    assert not reference_stability(sid, concat), reference_stability(sid, concat)
+    B, h, w, D = SHAPES[sid]
+    r64, r32 = oracle_train(sid, concat, torch.float64), oracle_train(sid, concat, torch.float32)
+    m = load_seeded(GwcNet(D, use_concat_volume=concat)).to(DEV).train()
+    fL, fR = features(sid, concat)
+    ag, bg = fL.to(DEV).requires_grad_(), fR.to(DEV).requires_grad_()
+    got = m.hot_path(*split(ag, bg, concat))
+    params = dict(m.named_parameters())
+    got_g = torch.autograd.grad(seeded_loss(got, sid), [ag, bg] + [params[k] for k in r64["names"][2:]])
+    torch.cuda.synchronize()
+    for k in HEADS:
+        ref = r64["heads"][k]
+        err = (got[k].detach().cpu().double() - ref).abs().max().item()
+        assert err <= head_tol(k, ref), f"{k}: max err {err:.3e} > {head_tol(k, ref):.1e}"
+    rows = yardstick_rows(r64["names"], got_g, r64["grads"], r32["grads"])
+    state = m.state_dict()
+    snames = sorted(r64["stats"])
+    srows = yardstick_rows(snames, [state[k] for k in snames], [r64["stats"][k] for k in snames],
+                           [r32["stats"][k] for k in snames])
+    with capsys.disabled():
+        print(f"\n[{sid} {variant}] per-tensor gradient rel-L2 vs the fp64 oracle ({B}x{fL.shape[1]}x{h}x{w}, D={D}):")
+        for n, eg, eo, nr in sorted(rows, key=lambda t: -t[1])[:12]:
+            print(f"   {n:60s} gpu {eg:.3e}   oracle32 {eo:.3e}   |ref| {nr:.3e}")
+        print(f"   GRADIENTS {sid} {variant}: {summary(rows)}")
+        print(f"   RUNNING-STATS {sid} {variant}: {summary(srows)}")
+    check_absolute(rows, f"{sid} {variant} gradients")
+    check_yardstick(srows, f"{sid} {variant} running statistics")
+    for k, v in state.items():
+        if k.endswith("num_batches_tracked") and k.split(".")[0] in ("dres0", "dres1", "cva1", "cva2", "cva3", "classif0",
+                                                                      "classif1", "classif2", "classif3"):
+            assert int(v) == 1, k
+
+
+def test_train_step_unaligned_width_is_reproducible_and_prepack_plan_is_exact():
+    """u22 (G): two train steps on the same inputs are bitwise equal (the fallback kernels of this width have order-fixed
+    sums too), and a step inside ops.PrepackPlan.active() -- at this width the plan holds the fp32 MFMA layouts of the
+    stride-2, transposed and 1x1x1 convolutions as well -- is bitwise equal to per-call packing"""
+    from dcanet_amd import ops
+    from dcanet_amd.models.gwcnet_dca_g import GwcNet
+    sid = "u22"
+    m = load_seeded(GwcNet(SHAPES[sid][3], use_concat_volume=False)).to(DEV).train()
+    fL, fR = features(sid, False)
+    ag, bg = fL.to(DEV).requires_grad_(), fR.to(DEV).requires_grad_()
+    names = [k for k, _ in m.named_parameters() if k.split(".")[0] in ("dres0", "dres1", "cva1", "cva2", "cva3", "classif0",
+                                                                       "classif1", "classif2", "classif3")]
+    params = dict(m.named_parameters())
+
+    def step():
+        r = m.hot_path(ag, bg)
+        g = torch.autograd.grad(seeded_loss(r, sid), [ag, bg] + [params[k] for k in names])
+        return [r[k].detach().clone() for k in HEADS] + [t.clone() for t in g]
+    ref, again = step(), step()
+    assert all(torch.equal(a, b) for a, b in zip(ref, again)), "two eager steps differ"
+    plan = ops.PrepackPlan()
+    with plan.recording():
+        step()
+    plan.finalize()
+    assert plan.n >= 3 * 4, plan.n          # per cva block at least: cost_agg.conv1, conv3, redir and fuse layouts
+    plan.refresh()
+    with plan.active():
+        planned = step()
+    assert all(torch.equal(a, b) for a, b in zip(ref, planned)), "PrepackPlan changes the step"
+
+
+# ------------------------------------------------------------------------------------- (b) eval forward
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("variant", ["g", "gc"])
+@pytest.mark.parametrize("sid", UNALIGNED + ["a24"])
+def test_eval_forward_unaligned_width(sid, variant):
+    """eval forward at the same shapes: pred4_q and prob_volume2 against the fp64 oracle; frozen_weights(), a GraphedHotPath
+    replay and torch.inference_mode() bitwise equal to the eager no_grad run; and the producer-emitted operand maxima
+    (conv3d_fused_inference(..., emit_amax=True) -> ops.AMAX_STATS["tagged"]) are really used at this width"""
+    from dcanet_amd import ops
+    from dcanet_amd.graph import GraphedHotPath
+    from dcanet_amd.models.gwcnet_dca_g import GwcNet
+    concat = variant == "gc"
+    assert not reference_stability(sid, concat), reference_stability(sid, concat)
+    D = SHAPES[sid][3]
+    ref = oracle_eval(sid, concat, torch.float64)["out"]
+    m = load_seeded(GwcNet(D, use_concat_volume=concat)).to(DEV).eval()
+    fL, fR = features(sid, concat)
+    args = tuple(t.contiguous() for t in split(fL.to(DEV), fR.to(DEV), concat))
+    before = dict(ops.AMAX_STATS)
+    with torch.no_grad():
+        got = m.hot_path(*args)
+        eager = {k: got[k].clone() for k in EVAL_OUT}
+        tagged = ops.AMAX_STATS["tagged"] - before["tagged"]
+        with ops.frozen_weights():
+            frozen = {k: v.clone() for k, v in m.hot_path(*args).items()}
+    assert tagged >= 1, "no convolution took its operand scales from producer-emitted maxima: a read-pass test only"
+    for k in EVAL_OUT:
+        err = (eager[k].cpu().double() - ref[k]).abs().max().item()
+        assert err <= head_tol(k, ref[k]), f"{k}: max err {err:.3e} > {head_tol(k, ref[k]):.1e}"
+    assert ref["pred4_q"].std() > 0.1, "degenerate test: flat disparity map"
+    g = GraphedHotPath(m, *args)
+    replay = g(*args)
+    with torch.inference_mode():
+        imode = {k: v.clone() for k, v in m.hot_path(*args).items()}
+    for k in EVAL_OUT:
+        assert torch.equal(frozen[k], eager[k]), f"{k}: pre-packed weights change the result"
+        assert torch.equal(replay[k], eager[k]), f"{k}: graph replay differs by {(replay[k] - eager[k]).abs().max().item():.3e}"
+        assert torch.equal(imode[k], eager[k]), f"{k}: inference_mode differs from no_grad"
+
+
+# ------------------------------------------------------------------------------------- (c) layer chains
+@pytest.mark.parametrize("both", [False, True], ids=["packed-only", "fp32+twin"])
+@pytest.mark.parametrize("W", [22, 18])
+def test_packed_training_chain_unaligned_width(W, both, monkeypatch):
+    """test_packed_training_chain_matches_fp32_chain at W % 4 == 2.  fp32+twin is the case of ADVICE r3 finding 1:
+    2x32x6x10x22 through convbn3d(..., pack_out="both"), then a 3x3x3 reader (the twin) and an fp32 reader.  An fp32 tensor
+    of such a width cannot be paired with a packed gradient (`_pack_dy_ok`), so the reader's gradient stays fp32 and its
+    weight gradient must take the fp32 tensor, not the twin; the forward still reads the twin."""
+    from dcanet_amd import ops
+    import torch.nn as nn
+    _family(monkeypatch, ops, "f16x2")
+    c1 = nn.Conv3d(40, 32, 3, 1, 1, bias=False).to(DEV); b1 = nn.BatchNorm3d(32).to(DEV)
+    c2 = nn.Conv3d(32, 32, 3, 1, 1, bias=False).to(DEV); b2 = nn.BatchNorm3d(32).to(DEV)
+    c3 = nn.Conv3d(32, 32, 3, 1, 1, bias=False).to(DEV)
+    with torch.no_grad():
+        for i, c in enumerate((c1, c2, c3)):
+            c.weight.copy_(seeded_tensor(f"uch.w{i}", c.weight.shape) * (1.5 / (27 * 32)) ** 0.5)
+    x = seeded_tensor("uch.x", (2, 40, 6, 10, W)).to(DEV)
+    r = seeded_tensor("uch.r", (2, 32, 6, 10, W)).to(DEV)
+    gz = seeded_tensor("uch.g", (2, 32, 6, 10, W)).to(DEV) * 1e-3
+    res = {}
+    for pack in (True, False):
+        monkeypatch.setattr(ops, "PACK", pack)
+        for b in (b1, b2):
+            b.reset_running_stats()
+        before = dict(ops.AMAX_STATS)
+        xx = x.clone().requires_grad_()
+        if both:
+            z1 = ops.convbn3d(xx, c1, b1, 0.0, pack_out="both")
+            assert tuple(z1.shape) == (2, 32, 6, 10, W) and not ops._is_packed(z1)
+            assert ops._pack_dy_ok(z1, None, c2, False, 1, None) is False       # fp32 operand, W % 4 != 0: dy2 stays fp32
+            z2 = ops.convbn3d(z1, c2, b2, 1.0, res_post=z1, pack_out="both")
+            if pack:
+                assert ops._twin_of(z1) is not None and ops._twin_of(z2) is not None and not ops._is_packed(z2)
+                for t in (z1, z2):
+                    tw = ops._twin_of(t)
+                    assert ops._is_packed(tw)
+                    err = _chan_err(_unpack_px2(tw, tw._dca_px2[0]), t)
+                    assert err.max() <= 2.0 ** -21, err.max().item()
+            else:
+                assert ops._twin_of(z1) is None and ops._twin_of(z2) is None
+            z = ops.conv3d(z2, c3.weight, 1, False) + z2            # a 3x3x3 reader (twin) and an fp32 reader of z2
+        else:
+            z1 = ops.convbn3d(xx, c1, b1, 0.0, pack_out=True)
+            assert ops._is_packed(z1) == pack
+            assert ops._pack_dy_ok(z1, None, c2, False, 1, None) is pack        # a packed operand pairs with a packed dy
+            z = ops.convbn3d(z1, c2, b2, 1.0, res_post=r)
+        g = torch.autograd.grad((z * gz).sum(), [xx, c1.weight, c2.weight, b1.weight, b1.bias] + ([c3.weight] if both else []))
+        res[pack] = [z.detach()] + [t.detach() for t in g]
+        npacked = ops.AMAX_STATS["packed"] - before["packed"]
+        # packed-only: conv2 forward (z1) and conv2 backward-data (dy2); fp32+twin: conv2 and conv3 forward (the twins)
+        assert npacked >= 2 if pack else npacked == 0, npacked
+    m = nn.Sequential(nn.Conv3d(40, 32, 3, 1, 1, bias=False), nn.BatchNorm3d(32), nn.ReLU(), nn.Conv3d(32, 32, 3, 1, 1, bias=False),
+                      nn.BatchNorm3d(32)).double()
+    m[0].weight.data.copy_(c1.weight.detach().cpu()); m[3].weight.data.copy_(c2.weight.detach().cpu())
+    w3 = c3.weight.detach().cpu().double().requires_grad_()
+    xr = x.cpu().double().requires_grad_()
+    if both:
+        z1r = m[2](m[1](m[0](xr)))
+        z2r = m[4](m[3](z1r)) + z1r
+        zr = F.conv3d(z2r, w3, None, 1, 1) + z2r
+    else:
+        zr = m(xr) + r.cpu().double()
+    gr = torch.autograd.grad((zr * gz.cpu().double()).sum(), [xr, m[0].weight, m[3].weight, m[1].weight, m[1].bias] +
+                             ([w3] if both else []))
+    for i, (a, b, ref) in enumerate(zip(res[True], res[False], [zr] + list(gr))):
+        ea, eb = rel_l2(a, ref), rel_l2(b, ref)
+        assert ea <= 2.0 * eb + 2e-6, (i, ea, eb)
+        assert eb <= 1e-4, (i, eb)           # the fp32-operand chain itself against fp64: the single-op gradient gate of test_gpu_parity.py
+
+
+# ------------------------------------------------------------------------------------- (d) kernel level
+def _conv_vs_fp64(ops, x, w, stride, transposed, x2=None, tag="k"):
+    """ops.conv3d forward, backward-data and weight gradient against PyTorch in fp64, at the tolerances of test_conv3d"""
+    k = w.shape[2]
+    xs = [x] if x2 is None else [x, x2]
+    xd, wd = [t.double().requires_grad_() for t in xs], w.double().requires_grad_()
+    xin = xd[0] if x2 is None else torch.cat(xd, 1)
+    yr = F.conv_transpose3d(xin, wd, None, 2, 1, 1) if transposed else F.conv3d(xin, wd, None, stride, k // 2)
+    gy = seeded_tensor(f"{tag}.gy", yr.shape)
+    gr = torch.autograd.grad((yr * gy.double()).sum(), xd + [wd])
+    xg, wg = [gpu(t, True) for t in xs], gpu(w, True)
+    y = ops.conv3d(xg[0], wg, stride, transposed, x2=None if x2 is None else xg[1])
+    gg = torch.autograd.grad((y * gy.to(DEV)).sum(), xg + [wg])
+    close(y, yr, 1e-5, "fwd")
+    for a, b in zip(gg[:-1], gr[:-1]):
+        close(a, b, 1e-5, "dx"); close_l2(a, b, 1e-5, "dx")
+    close_l2(gg[-1], gr[-1], 1e-5, "dw"); close(gg[-1], gr[-1], 2e-5, "dw")
+
+
+S2_ROWS = [   # N, fine dims: W in {10, 22, 26} leaves all three f16x2 stride-2 kernels; 12: forward stays, Wo = 6 does not; 24: all stay
+    (1, (4, 6, 10)), (2, (12, 10, 22)), (1, (10, 6, 26)), (1, (4, 6, 12)), (2, (12, 10, 24)),
+]
+
+
+@pytest.mark.parametrize("case", S2_ROWS, ids=str)
+def test_conv3d_stride2_both_sides_of_the_width_predicates(case, monkeypatch):
+    """Conv3d(32, 64, 3, stride 2) under the f16x2 family: forward (`_s2x2_eligible`: W % 4), backward-data (the transposed
+    kernel over the coarse tensor: `_dx3_eligible`, Wo % 4 -- 64 channels: generic either way) and weight gradient (`_wgrad`
+    stride-2 branch: W % 4 and Wo % 4) against fp64"""
+    from dcanet_amd import ops
+    _family(monkeypatch, ops, "f16x2")
+    N, dims = case
+    x = seeded_tensor(f"us2.x{case}", (N, 32) + dims)
+    w = seeded_tensor(f"us2.w{case}", (64, 32, 3, 3, 3)) * (1.0 / (32 * 27)) ** 0.5
+    assert ops._s2x2_eligible(gpu(x), None, 3, 2, False, 32, 64, None, None, 1.0) == (dims[2] % 4 == 0)
+    _conv_vs_fp64(ops, x, w, 2, False, tag=f"us2{case}")
+
+
+DECONV_ROWS = [   # N, coarse dims: W in {5, 11, 13} leaves deconv3d_x3 (and 2W % 4 == 2 the stride-2 kernels of its backward); 12 stays
+    (1, (2, 3, 5)), (2, (6, 5, 11)), (1, (5, 3, 13)), (2, (6, 5, 12)),
+]
+
+
+@pytest.mark.parametrize("case", DECONV_ROWS, ids=str)
+def test_deconv3d_both_sides_of_the_width_predicates(case, monkeypatch):
+    """ConvTranspose3d(64, 32, 3, s2, p1, op1) (cost_agg.conv3) under the f16x2 family: forward (`_dx3_eligible`: coarse
+    W % 4), backward-data (a stride-2 convolution of the fine gradient: `_s2x2_eligible`) and weight gradient (`_wgrad`
+    stride-2 branch with the roles exchanged) against fp64"""
+    from dcanet_amd import ops
+    _family(monkeypatch, ops, "f16x2")
+    N, dims = case
+    x = seeded_tensor(f"udc.x{case}", (N, 64) + dims)
+    w = seeded_tensor(f"udc.w{case}", (64, 32, 3, 3, 3)) * (1.0 / (64 * 27 / 8)) ** 0.5
+    assert ops._dx3_eligible(gpu(x), None, 3, 2, True, 64, 32) == (dims[2] % 4 == 0)
+    _conv_vs_fp64(ops, x, w, 2, True, tag=f"udc{case}")
+
+
+C1X1_ROWS = [   # N, dims: S = 195 (odd), 330 (S % 4 == 2) leave conv1_x3; 360 stays
+    (1, (5, 3, 13)), (2, (6, 5, 11)), (2, (6, 5, 12)),
+]
+
+
+@pytest.mark.parametrize("two", [False, True], ids=["x", "x+x2"])
+@pytest.mark.parametrize("case", C1X1_ROWS, ids=str)
+def test_conv1x1_both_sides_of_the_voxel_count_predicate(case, two, monkeypatch):
+    """the 1x1x1 convolution (32 -> 32, and the `fuse` form 32 + 32 -> 32 over two inputs), forward / backward-data / weight
+    gradient against fp64 (`_c1x3_eligible`: S % 4)"""
+    from dcanet_amd import ops
+    _family(monkeypatch, ops, "f16x2")
+    N, dims = case
+    S = dims[0] * dims[1] * dims[2]
+    x = seeded_tensor(f"u11.x{case}", (N, 32) + dims)
+    x2 = seeded_tensor(f"u11.x2{case}", (N, 32) + dims) if two else None
+    cin = 64 if two else 32
+    w = seeded_tensor(f"u11.w{case}{two}", (32, cin, 1, 1, 1)) * (1.0 / cin) ** 0.5
+    y = torch.empty((N, 32) + dims, device=DEV)
+    assert ops._c1x3_eligible(gpu(x), None if x2 is None else gpu(x2), 1, cin, 32, y) == (S % 4 == 0)
+    _conv_vs_fp64(ops, x, w, 1, False, x2=x2, tag=f"u11{case}{two}")
+
+
+C1HEAD_ROWS = [   # N, C, dims: W = 11, 22 leave dca_conv3d_c1_wgrad (expand + generic weight gradient); 12 stays
+    (2, 32, (6, 5, 11)), (1, 32, (12, 10, 22)), (1, 64, (3, 4, 11)), (2, 32, (6, 5, 12)),
+]
+
+
+@pytest.mark.parametrize("case", C1HEAD_ROWS, ids=str)
+def test_c1_head_both_sides_of_the_width_predicate(case, monkeypatch):
+    """the logit head Conv3d(C, 1, 3) (`_Conv3dC1`): forward, backward-data and weight gradient against fp64; at W % 4 != 0
+    the weight gradient leaves the fused kernel for the 27-plane expansion + generic kernel"""
+    from dcanet_amd import ops
+    _family(monkeypatch, ops, "f16x2")
+    N, C, dims = case
+    x = seeded_tensor(f"uc1.x{case}", (N, C) + dims)
+    w = seeded_tensor(f"uc1.w{case}", (1, C, 3, 3, 3)) * 0.05
+    _conv_vs_fp64(ops, x, w, 1, False, tag=f"uc1{case}")
+
+
+EPI_ROWS = [   # kind, cin, cout, input dims, N   (c3 / s2 / dc / c1 / c1x2 as in STATS_CASES; every W or S off the aligned side)
+    ("c3", 32, 40, (5, 9, 22), 2),
+    ("c3", 32, 32, (3, 5, 26), 1),
+    ("s2", 32, 64, (4, 6, 10), 1),
+    ("dc", 64, 32, (3, 5, 11), 2),
+    ("c1", 32, 32, (5, 3, 13), 1),
+    ("c1x2", 64, 32, (6, 5, 11), 2),
+]
+
+
+@pytest.mark.parametrize("case", EPI_ROWS, ids=str)
+def test_fused_inference_epilogue_unaligned_width(case, monkeypatch):
+    """ops.conv3d_fused_inference (eval path: y = act(conv * scale + shift + res_pre) + res_post in one launch) against fp64
+    where test_conv3d_bf16x3_fused_epilogue / test_deconv3d_bf16x3 are aligned only; for the f16x2 3x3x3 kernel also the
+    per-channel max |y| slots its single-voxel form emits for the next convolution (exact, like the quad form's)"""
+    from dcanet_amd import ops
+    _family(monkeypatch, ops, "f16x2")
+    kind, cin, cout, dims, N = case
+    k = 1 if kind.startswith("c1") else 3
+    stride, transposed = {"c3": (1, False), "s2": (2, False), "dc": (2, True), "c1": (1, False), "c1x2": (1, False)}[kind]
+    x = seeded_tensor(f"uep.x{case}", (N, cin) + dims)
+    w = seeded_tensor(f"uep.w{case}", (cin, cout, 3, 3, 3) if transposed else (cout, cin, k, k, k)) * (1.0 / (cin * k ** 3)) ** 0.5
+    xd, wd = x.double(), w.double()
+    conv = F.conv_transpose3d(xd, wd, None, 2, 1, 1) if transposed else F.conv3d(xd, wd, None, stride, k // 2)
+    sc, sh = seeded_tensor(f"uep.s{case}", (cout,)).abs() + 0.5, seeded_tensor(f"uep.b{case}", (cout,))
+    rp = None if kind == "s2" else seeded_tensor(f"uep.p{case}", conv.shape)
+    rq = seeded_tensor(f"uep.q{case}", conv.shape)
+    pre = conv * sc.double().view(1, -1, 1, 1, 1) + sh.double().view(1, -1, 1, 1, 1) + (0 if rp is None else rp.double())
+    ref = F.leaky_relu(pre, 0.1) + rq.double()
+    xg = x.to(DEV)
+    x1, x2 = (xg[:, :32].contiguous(), xg[:, 32:].contiguous()) if kind == "c1x2" else (xg, None)
+    y = ops.conv3d_fused_inference(x1, w.to(DEV), stride, transposed, sc.to(DEV), sh.to(DEV), 0.1,
+                                   None if rp is None else rp.to(DEV), rq.to(DEV), x2)
+    close(y, ref, 1e-5, "fused")
+    if kind == "c3":
+        slots, nslots, _ = y._dca_cmax
+        got = slots.view(torch.float32).view(cout, ops.CSLOTS)[:, :nslots].amax(1)
+        assert torch.equal(got, y.abs().amax((0, 2, 3, 4))), (got, y.abs().amax((0, 2, 3, 4)))
+
+
+@pytest.mark.parametrize("slope", [0.0, 0.1, 1.0])
+def test_bn_pack_kernels_unaligned_width(slope, monkeypatch):
+    """test_bn_pack_kernels_match_fp32_kernels at (4, 6, 22) (S % 4 == 0 from D alone, rows not 16-byte aligned) and at
+    (3, 5, 22) (S % 4 == 2: the single-voxel forms): packed output / packed gradient unpack to what the fp32 kernels write
+    within 2^-21 of the channel's maximum, nothing overflows f16, and the fp32 kernels themselves match fp64"""
+    from dcanet_amd import ops
+    import torch.nn as nn
+    _family(monkeypatch, ops, "f16x2")
+    for dims in ((4, 6, 22), (3, 5, 22)):
+        N, C = 2, 32
+        bn = nn.BatchNorm3d(C).to(DEV)
+        with torch.no_grad():
+            bn.weight.copy_(seeded_tensor("ubnp.g", (C,)).abs() + 0.5); bn.bias.copy_(seeded_tensor("ubnp.b", (C,)))
+        y = (seeded_tensor("ubnp.y", (N, C) + dims) * 3 + 1).to(DEV)
+        dz = (seeded_tensor("ubnp.dz", (N, C) + dims) * torch.exp2(-(torch.arange(C) % 9).float()).view(1, C, 1, 1, 1)).to(DEV)
+        outs = {}
+        for pack in (False, True):
+            bn.reset_running_stats()
+            yy = y.clone().requires_grad_()
+            z = ops.bn_act(_GradProbe.apply(yy), bn, slope, pack_out=pack, pack_dy=pack)
+            zz = z
+            if pack:
+                assert ops._is_packed(z)
+                zz = _unpack_px2(z, z._dca_px2[0]).float().to(DEV)
+                raw = z.detach().cpu().view(torch.int16).view(torch.float16)
+                assert torch.isfinite(raw).all() and raw.abs().max() < 2.0 ** 15
+            z.backward(dz)
+            g = _GradProbe.seen.pop("g")
+            if pack:
+                tag = getattr(g, "_dca_px2", None)
+                assert tag is not None, "packed gradient expected"
+                raw = g.detach().cpu().view(torch.int16).view(torch.float16)
+                assert torch.isfinite(raw).all() and raw.abs().max() < 2.0 ** 15
+                g = _unpack_px2(g, tag[0]).float().to(DEV)
+            outs[pack] = (zz.detach(), g.detach(), bn.weight.grad.clone(), bn.bias.grad.clone())
+            bn.weight.grad = bn.bias.grad = None
+        for name, a, b in zip(("z", "dy", "dgamma", "dbeta"), outs[True], outs[False]):
+            if a.dim() == 5:
+                e = _chan_err(a, b)
+                assert e.max() <= 2.0 ** -21, (name, slope, dims, e.max().item())
+            else:
+                assert torch.equal(a, b), (name, dims)
+        # the fp32 kernels against fp64 (tolerances of test_bn_act)
+        yc, gc, bc = (cpu_leaf(t.detach().cpu().double()) for t in (y, bn.weight, bn.bias))
+        zr = _bn_ref(yc, gc, bc, torch.zeros(C, dtype=torch.float64), torch.ones(C, dtype=torch.float64), True, slope, None, None)
+        gr = torch.autograd.grad((zr * dz.cpu().double()).sum(), [yc, gc, bc])
+        close(outs[False][0], zr, 1e-5, "z")
+        for a, b, nm in zip(outs[False][1:], gr, ("dy", "dgamma", "dbeta")):
+            close(a, b, 2e-5, nm)
+
+
+# ------------------------------------------------------------------------------------- (e) reduced precision
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+def test_reduced_precision_refuses_unaligned_width_before_any_launch(dtype, monkeypatch):
+    """ops.reduced_precision has no kernels for W % 4 != 0: a u22 eval forward raises from Python, naming the requirement,
+    before the library is asked for a single launch"""
+    from dcanet_amd import ops
+    from dcanet_amd.models.gwcnet_dca_g import GwcNet
+    m = load_seeded(GwcNet(SHAPES["u22"][3], use_concat_volume=False)).to(DEV).eval()
+    fL, fR = features("u22", False)
+    a, b = fL.to(DEV), fR.to(DEV)
+    torch.cuda.synchronize()
+
+    def no_launch():
+        raise AssertionError("a kernel launch was requested before the width check")
+    monkeypatch.setattr(ops, "_L", no_launch)
+    with torch.no_grad(), ops.reduced_precision(dtype):
+        with pytest.raises(RuntimeError, match=r"W % 4 == 0"):
+            m.hot_path(a, b)
