@@ -101,6 +101,10 @@ SIGNATURES = {
     "dca_region_confusion": (_i, [_p] * 5 + [_i] * 7 + [_p]),
     "dca_eval_state_len": (_l, [_i]),
     "dca_eval_accumulate": (_i, [_p, _p, _p] + [_i] * 5 + [_p]),
+    "dca_frame_hist": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "dca_frame_lut": (_i, [_p, _l, _p, _p, _p]),
+    "dca_frame_apply": (_i, [_p] * 5 + [_i] * 9 + [_p]),
+    "dca_disp_export": (_i, [_p, _p, _p] + [_i] * 5 + [_f, _p]),
 }
 
 _lib = None

@@ -4,8 +4,14 @@ zero padding to a fixed 384x1248 frame (:71-87), `model(left, right)` in eval mo
 and the uint16 x256 PNG (:110) -- with the 3D part replayed as ONE hipGraph (dcanet_amd.graph.GraphedHotPath).
 
 The reference's script calls `.squeeze()` on the model's return value although eval `forward` returns a tuple
-(gwcnet_dca_g.py:282); the disparity is element 0."""
+(gwcnet_dca_g.py:282); the disparity is element 0.
+
+`KittiInference(..., device_io=True)` moves the arithmetic around the model call to the GPU (csrc/frame_io.hip): the
+uint8 pair is uploaded as it is, normalised through a histogram-built table, placed in the frame, and the cropped
+float32 / uint16 disparity is read back -- two copies are all that is left on the host."""
 from __future__ import annotations
+
+import collections
 
 import numpy as np
 import torch
@@ -55,14 +61,90 @@ def disparity_png(path: str, disp: np.ndarray) -> None:
     Image.fromarray((disp * 256).astype("uint16")).save(path, format="PNG")
 
 
+def lut_from_histogram(hist: np.ndarray, n: int):
+    """numpy restatement of the `frame_lut` kernel, operation for operation: hist (..., 256) counts of the byte values of a
+    plane of n pixels -> (lut (..., 256) float32, stats (..., 2) float64 = mean, population std), with
+    lut[v] = float32((v - mean) / std) -- the value `normalize_pair` gives a pixel of value v.  The mean is exact (integer
+    sum, one division); the variance is summed over v = 0..255 in that order (np.cumsum is sequential)."""
+    hist = np.asarray(hist)
+    assert hist.shape[-1] == 256 and n > 0
+    h = hist.astype(np.int64)
+    v = np.arange(256, dtype=np.int64)
+    mean = (h * v).sum(-1).astype(np.float64) / np.float64(n)
+    d = v.astype(np.float64) - mean[..., None]
+    var = np.cumsum(h.astype(np.float64) * (d * d), axis=-1)[..., -1] / np.float64(n)
+    std = np.sqrt(var)
+    with np.errstate(divide="ignore", invalid="ignore"):      # a constant plane: NaN, as on the host path
+        lut = (d / std[..., None]).astype(np.float32)
+    return lut, np.stack([mean, std], -1)
+
+
+def placement(h: int, w: int, crop_height: int = 384, crop_width: int = 1248):
+    """`pad_or_crop` as a window: (src_y0, dst_y0, rows, cols) -- rows x cols pixels from source row src_y0, column 0,
+    land at frame row dst_y0, column 0; the rest of the frame is zero.  An image larger than the frame in one direction
+    and smaller in the other gives a mis-shaped frame on the host path and is refused here."""
+    if h <= 0 or w <= 0:
+        raise ValueError(f"empty image {h} x {w}")
+    if h <= crop_height and w <= crop_width:
+        return 0, crop_height - h, h, w
+    if h >= crop_height and w >= crop_width:
+        return int((h - crop_height) / 2), 0, crop_height, crop_width
+    raise ValueError(f"a {h} x {w} image neither fits into the {crop_height} x {crop_width} frame nor covers it")
+
+
+def imagenet_lut() -> torch.Tensor:
+    """The fixed table of the training loaders (dataloader/data_io.py:11-12, 27-35: ToTensor, then Normalize with the
+    ImageNet statistics) in the (2,3,256) form `ops.frame_apply` takes: the same float32 torch operations applied to the
+    256 byte values, repeated for both images."""
+    mean = torch.tensor([0.485, 0.456, 0.406], dtype=torch.float32).view(3, 1)
+    std = torch.tensor([0.229, 0.224, 0.225], dtype=torch.float32).view(3, 1)
+    v = torch.arange(256, dtype=torch.uint8).view(1, 256).expand(3, 256)
+    lut = v.float().div(255).sub(mean).div(std)
+    return torch.stack([lut, lut]).contiguous()
+
+
+class _Slot:
+    """Buffers and events of one frame in flight (device I/O): pinned + device uint8 inputs that grow on demand, device +
+    pinned outputs of the frame's size, allocated when their format (float32 / uint16) is first asked for."""
+
+    def __init__(self, device, crop_height, crop_width):
+        self.device = device
+        self.in_pin = self.in_dev = None
+        self.out_len = crop_height * crop_width
+        self.out = {}                # dtype -> (device, pinned)
+        self.uploaded, self.computed, self.done = (torch.cuda.Event() for _ in range(3))
+        self.meta = None             # (h, w, c, placement, offset of the right image) of the frame in the slot
+        self.as_uint16 = False
+
+    def reserve_input(self, nbytes):
+        """room for two images of nbytes each, the second at the next multiple of 16 (vector loads); returns its offset"""
+        off = (nbytes + 15) & ~15
+        if self.in_pin is None or self.in_pin.numel() < off + nbytes:
+            torch.cuda.synchronize(self.device)          # rare: nothing in flight may still use the old buffers
+            self.in_pin = torch.empty(off + nbytes, dtype=torch.uint8).pin_memory()
+            self.in_dev = torch.empty(off + nbytes, device=self.device, dtype=torch.uint8)
+        return off
+
+    def output(self, as_uint16):
+        dtype = torch.uint16 if as_uint16 else torch.float32
+        if dtype not in self.out:
+            self.out[dtype] = (torch.empty(self.out_len, device=self.device, dtype=dtype),
+                               torch.empty(self.out_len, dtype=dtype).pin_memory())
+        return self.out[dtype]
+
+
 class KittiInference:
     """`disp = KittiInference(model)(left_rgb, right_rgb)`: my_img.py:89-110 `my()` without the file I/O.
 
     `model` is a GwcNet (or the nn.DataParallel wrapper the reference builds, my_img.py:37) already on the GPU with its
     weights loaded.  The 2D networks run as ordinary PyTorch-ROCm launches; the cost-volume path (volume -> dres0/1 ->
-    3 x cva -> classif3 -> soft-argmin) is captured once for the fixed frame size and replayed (`graph=False`: eager)."""
+    3 x cva -> classif3 -> soft-argmin) is captured once for the fixed frame size and replayed (`graph=False`: eager).
 
-    def __init__(self, model, crop_height: int = 384, crop_width: int = 1248, graph: bool = True, dtype=None):
+    `device_io=True`: normalisation, padding, crop and the uint16 conversion run as HIP kernels; the host only copies the
+    uint8 pair into pinned memory and the result out of it.  `stream(pairs)` pipelines successive frames."""
+
+    def __init__(self, model, crop_height: int = 384, crop_width: int = 1248, graph: bool = True, dtype=None,
+                 device_io: bool = False):
         """dtype: None (fp32) or torch.float16 / torch.bfloat16 -- the reduced-precision path of BASELINE config 5
         ("fp16, hipGraph-captured 3D hourglass"): the captured hot path runs under ops.reduced_precision(dtype)."""
         self.net = model.module if isinstance(model, torch.nn.DataParallel) else model
@@ -70,6 +152,10 @@ class KittiInference:
         self.graph = graph
         self.dtype = dtype
         self._graphed = None
+        self.device_io = device_io
+        self._frames = None          # (2,3,Hc,Wc): the network's inputs, rewritten whole by every frame
+        self._slots = []
+        self._copy_stream = None
         self.net.eval()
 
     @torch.no_grad()
@@ -93,8 +179,127 @@ class KittiInference:
                 r = net.hot_path(*args)
         return net.prop(guidance, r["pred4_q"])
 
-    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray) -> np.ndarray:
+    # ---- device I/O: three stages per frame, each enqueued on the stream it is given --------------------------------
+    def _slot(self, i):
+        dev = next(self.net.parameters()).device
+        if self._frames is None:
+            self._frames = torch.empty((2, 3, self.crop_height, self.crop_width), device=dev, dtype=torch.float32)
+        while len(self._slots) <= i:
+            self._slots.append(_Slot(dev, self.crop_height, self.crop_width))
+        return self._slots[i]
+
+    def _upload(self, s, left_rgb, right_rgb, copy):
+        """host: the pair into the slot's pinned buffer; `copy` stream: pinned -> device"""
+        left_rgb, right_rgb = np.ascontiguousarray(left_rgb), np.ascontiguousarray(right_rgb)
+        if left_rgb.dtype != np.uint8 or right_rgb.dtype != np.uint8 or left_rgb.ndim != 3 \
+                or left_rgb.shape[2] not in (3, 4) or left_rgb.shape != right_rgb.shape:
+            raise ValueError(f"device_io takes two (H,W,3) or (H,W,4) uint8 images of one shape, got {left_rgb.dtype} "
+                             f"{left_rgb.shape} and {right_rgb.dtype} {right_rgb.shape}")
+        h, w, c = left_rgb.shape
+        place = placement(h, w, self.crop_height, self.crop_width)
+        n = h * w * c
+        off = s.reserve_input(n)
+        s.uploaded.synchronize()                     # the previous copy out of the pinned buffer
+        pin = s.in_pin.numpy()
+        pin[:n] = left_rgb.reshape(-1)
+        pin[off:off + n] = right_rgb.reshape(-1)
+        with torch.cuda.stream(copy):
+            copy.wait_event(s.computed)              # the previous frame of this slot has read its input
+            s.in_dev[:off + n].copy_(s.in_pin[:off + n], non_blocking=True)      # one copy for the pair
+            s.uploaded.record(copy)
+        s.meta = (h, w, c, place, off)
+
+    @torch.no_grad()
+    def _compute(self, s, compute, as_uint16):
+        """`compute` stream: histogram -> table -> frames -> model -> export into the slot's device output"""
+        from . import ops
+        h, w, c, (src_y0, dst_y0, rows, cols), off = s.meta
+        n = h * w * c
+        with torch.cuda.stream(compute):
+            compute.wait_event(s.uploaded)
+            compute.wait_event(s.done)               # the previous read-back of this slot's output
+            left, right = s.in_dev[:n].view(h, w, c), s.in_dev[off:off + n].view(h, w, c)
+            lut, _ = ops.frame_lut(ops.frame_histogram(left, right), h * w)
+            fl, fr = ops.frame_apply(left, right, lut, (self.crop_height, self.crop_width), src_y0, dst_y0, rows, cols,
+                                     out=self._frames)
+            disp = self.forward_frame(fl, fr)
+            out = s.output(as_uint16)[0][:rows * cols].view(rows, cols)
+            if as_uint16:
+                ops.disp_export(disp, dst_y0, rows, cols, f32=False, u16=True, out_u16=out)
+            else:
+                ops.disp_export(disp, dst_y0, rows, cols, out_f32=out)
+            s.computed.record(compute)
+        s.as_uint16 = as_uint16
+
+    def _readback(self, s, copy):
+        """`copy` stream: device output -> pinned"""
+        rows, cols = s.meta[3][2:]
+        dev, pin = s.output(s.as_uint16)
+        with torch.cuda.stream(copy):
+            copy.wait_event(s.computed)
+            pin[:rows * cols].copy_(dev[:rows * cols], non_blocking=True)
+            s.done.record(copy)
+
+    def _result(self, s):
+        """host: the one synchronisation of a frame, then the result out of the pinned buffer"""
+        rows, cols = s.meta[3][2:]
+        s.done.synchronize()
+        pin = s.output(s.as_uint16)[1]
+        return pin[:rows * cols].numpy().reshape(rows, cols).copy()
+
+    def _call_device(self, left_rgb, right_rgb, as_uint16):
+        dev = next(self.net.parameters()).device
+        cur = torch.cuda.current_stream(dev)
+        s = self._slot(0)
+        self._upload(s, left_rgb, right_rgb, cur)
+        self._compute(s, cur, as_uint16)
+        self._readback(s, cur)
+        return self._result(s)
+
+    def stream(self, pairs, depth: int = 2, as_uint16: bool = False):
+        """Generator over an iterable of (left_rgb, right_rgb) uint8 pairs (sizes may differ as long as each fits the
+        frame): yields the disparities in input order, `depth` frames in flight.  A copy stream beside the compute
+        stream carries the upload of frame i+1 and the read-back of frame i-1 while frame i computes."""
+        if not self.device_io:
+            raise RuntimeError("stream() needs KittiInference(..., device_io=True)")
+        if depth < 1:
+            raise ValueError("depth >= 1")
+        dev = next(self.net.parameters()).device
+        compute = torch.cuda.current_stream(dev)
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(dev)
+        copy = self._copy_stream
+        copy.wait_stream(compute)
+        inflight = collections.deque()               # slots in input order; [slot, read-back enqueued]
+        try:
+            for i, (left_rgb, right_rgb) in enumerate(pairs):
+                if len(inflight) == depth:               # slot i % depth is the oldest frame's: hand that frame out first
+                    old = inflight.popleft()
+                    if not old[1]:
+                        self._readback(old[0], copy)
+                    yield self._result(old[0])
+                s = self._slot(i % depth)
+                self._upload(s, left_rgb, right_rgb, copy)
+                self._compute(s, compute, as_uint16)
+                # the read-back of the frame before goes behind this upload on the copy stream: it waits for that frame's
+                # compute, and an upload queued behind it would wait too
+                if inflight and not inflight[-1][1]:
+                    self._readback(inflight[-1][0], copy)
+                    inflight[-1][1] = True
+                inflight.append([s, False])
+            while inflight:
+                old = inflight.popleft()
+                if not old[1]:
+                    self._readback(old[0], copy)
+                yield self._result(old[0])
+        finally:
+            compute.wait_stream(copy)                # later work on the compute stream may reuse slot 0 (`__call__`)
+
+    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray, as_uint16: bool = False) -> np.ndarray:
+        if self.device_io:
+            return self._call_device(left_rgb, right_rgb, as_uint16)
         left, right, h, w = pad_or_crop(normalize_pair(left_rgb, right_rgb), self.crop_height, self.crop_width)
         dev = next(self.net.parameters()).device
         disp = self.forward_frame(left.to(dev), right.to(dev))
-        return crop_back(disp.squeeze().cpu().numpy(), h, w, self.crop_height, self.crop_width)
+        disp = crop_back(disp.squeeze().cpu().numpy(), h, w, self.crop_height, self.crop_width)
+        return (disp * 256).astype("uint16") if as_uint16 else disp           # my_img.py:110

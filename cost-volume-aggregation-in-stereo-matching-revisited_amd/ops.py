@@ -1883,3 +1883,102 @@ def eval_accumulate(state, rec, cm, gt_shape):
         _chk(_L().dca_eval_accumulate(_ptr(rec), _ptr(cm), _ptr(state), rec.shape[0], nvol, C, int(gt_shape[-2]),
                                       int(gt_shape[-1]), _stream()), "dca_eval_accumulate")
     return state
+
+
+# ------------------------------------------------------------------------------------------------
+# Inference frame I/O (my_img.py:47-110 around the model call): per-plane normalisation as histogram -> table -> look-up,
+# placement in the zero-padded frame, export of the cropped disparity (csrc/frame_io.hip).  No launch synchronises.
+# ------------------------------------------------------------------------------------------------
+def _req_dev(t, name, what, dtype, shape=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name}: {what} must be on the ROCm device; there is no CPU fallback")
+    if t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError(f"{name}: {what} must be a contiguous {dtype} tensor, got {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{name}: {what} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _req_u8_pair(left, right, name):
+    _req_dev(left, name, "the left image", torch.uint8)
+    _req_dev(right, name, "the right image", torch.uint8)
+    if left.dim() != 3 or left.shape[2] not in (3, 4) or left.shape != right.shape or left.numel() == 0:
+        raise RuntimeError(f"{name}: expected two (H,W,3) or (H,W,4) uint8 images of one shape, got {tuple(left.shape)} and "
+                           f"{tuple(right.shape)}")
+    if left.shape[0] * left.shape[1] >= 1 << 31:
+        raise RuntimeError(f"{name}: H * W must stay below 2^31")
+    return tuple(int(s) for s in left.shape)
+
+
+def frame_histogram(left_u8, right_u8):
+    """Histograms of the colour planes of two interleaved (H,W,C) uint8 images, C = 3 or 4 (a fourth channel is ignored).
+    Returns (2,3,256) int32 counts (image, plane, value); bitwise reproducible."""
+    H, W, C = _req_u8_pair(left_u8, right_u8, "frame_histogram")
+    hist = torch.empty((2, 3, 256), device=left_u8.device, dtype=torch.int32)
+    with torch.cuda.device_of(left_u8):
+        _chk(_L().dca_frame_hist(_ptr(left_u8), _ptr(right_u8), _ptr(hist), H, W, C, _stream()), "dca_frame_hist")
+    return hist
+
+
+def frame_lut(hist, n_pixels):
+    """hist of `frame_histogram` and the pixel count H*W -> (lut (2,3,256) float32, stats (2,3,2) float64 = mean, std):
+    lut[i,c,v] = float32((v - mean) / std) in fp64 with the population std (my_img.py:59-68);
+    inference.lut_from_histogram is its numpy restatement, equal bit for bit."""
+    _req_dev(hist, "frame_lut", "hist", torch.int32, (2, 3, 256))
+    if not 0 < int(n_pixels) < 1 << 31:
+        raise RuntimeError("frame_lut: 0 < n_pixels < 2^31")
+    lut = torch.empty((2, 3, 256), device=hist.device, dtype=torch.float32)
+    stats = torch.empty((2, 3, 2), device=hist.device, dtype=torch.float64)
+    with torch.cuda.device_of(hist):
+        _chk(_L().dca_frame_lut(_ptr(hist), int(n_pixels), _ptr(lut), _ptr(stats), _stream()), "dca_frame_lut")
+    return lut, stats
+
+
+def frame_apply(left_u8, right_u8, lut, frame_hw, src_y0, dst_y0, rows, cols, out=None):
+    """Table look-up and placement: the rows x cols window of the (H,W,C) uint8 images starting at source row src_y0,
+    column 0, goes through lut (2,3,256) into the planar frames at row dst_y0, column 0; every other frame element
+    becomes +0.0.  out: (2,3,Hc,Wc) float32, written whole (allocated when None).  Returns the (1,3,Hc,Wc) views
+    (left, right) of it, the tensors `GwcNet.forward` takes."""
+    H, W, C = _req_u8_pair(left_u8, right_u8, "frame_apply")
+    Hc, Wc = int(frame_hw[0]), int(frame_hw[1])
+    _req_dev(lut, "frame_apply", "lut", torch.float32, (2, 3, 256))
+    src_y0, dst_y0, rows, cols = int(src_y0), int(dst_y0), int(rows), int(cols)
+    if Hc <= 0 or Wc <= 0 or min(src_y0, dst_y0, rows, cols) < 0 or src_y0 + rows > H or cols > W or dst_y0 + rows > Hc \
+            or cols > Wc:
+        raise RuntimeError(f"frame_apply: the {rows} x {cols} window (source row {src_y0}, frame row {dst_y0}) does not fit "
+                           f"the {H} x {W} source or the {Hc} x {Wc} frame")
+    if out is None:
+        out = torch.empty((2, 3, Hc, Wc), device=left_u8.device, dtype=torch.float32)
+    _req_dev(out, "frame_apply", "out", torch.float32, (2, 3, Hc, Wc))
+    with torch.cuda.device_of(left_u8):
+        _chk(_L().dca_frame_apply(_ptr(left_u8), _ptr(right_u8), _ptr(lut), _ptr(out[0]), _ptr(out[1]), H, W, C, Hc, Wc,
+                                  src_y0, dst_y0, rows, cols, _stream()), "dca_frame_apply")
+    return out[0:1], out[1:2]
+
+
+def disp_export(pred, y0, h, w, scale=256.0, f32=True, u16=False, out_f32=None, out_u16=None):
+    """The h x w window of the prediction (Hc,Wc) / (1,1,Hc,Wc) starting at row y0, column 0 (my_img.py:105-108), as
+    float32 (bit copy) and / or uint16(pred * scale) (my_img.py:110; truncated, saturated to [0, 65535], NaN -> 0).
+    Returns (float32 (h,w) or None, uint16 (h,w) or None); out_f32 / out_u16: buffers of that shape to write into."""
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda:
+        raise RuntimeError("disp_export: the prediction must be on the ROCm device; there is no CPU fallback")
+    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.dim() < 2 or pred.numel() == 0 \
+            or pred.numel() != pred.shape[-2] * pred.shape[-1]:
+        raise RuntimeError(f"disp_export: expected a contiguous float32 (Hc,Wc) prediction, got {pred.dtype} {tuple(pred.shape)}")
+    Hc, Wc = int(pred.shape[-2]), int(pred.shape[-1])
+    y0, h, w = int(y0), int(h), int(w)
+    if y0 < 0 or h <= 0 or w <= 0 or y0 + h > Hc or w > Wc or Hc * Wc >= 1 << 31:
+        raise RuntimeError(f"disp_export: the {h} x {w} window at row {y0} does not fit the {Hc} x {Wc} prediction")
+    if not (f32 or u16):
+        raise RuntimeError("disp_export: nothing to export (f32 and u16 are both off)")
+    of = ou = None
+    if f32:
+        of = torch.empty((h, w), device=pred.device, dtype=torch.float32) if out_f32 is None else \
+            _req_dev(out_f32, "disp_export", "out_f32", torch.float32, (h, w))
+    if u16:
+        ou = torch.empty((h, w), device=pred.device, dtype=torch.uint16) if out_u16 is None else \
+            _req_dev(out_u16, "disp_export", "out_u16", torch.uint16, (h, w))
+    with torch.cuda.device_of(pred):
+        _chk(_L().dca_disp_export(_ptr(pred), _ptr(of), _ptr(ou), Hc, Wc, y0, h, w, float(scale), _stream()),
+             "dca_disp_export")
+    return of, ou

@@ -466,6 +466,33 @@ long dca_eval_state_len(int C);
 int dca_eval_accumulate(const double* rec, const long long* cm, double* state, int B, int nvol, int C, int H, int W,
                         hipStream_t stream);
 
+/* ---- inference frame I/O (frame_io.hip): my_img.py:47-110 around the model call, without host arithmetic ----------------
+ * The normalisation of my_img.py:59-68 is per image and colour plane (p - mean) / std with the population std in fp64.  A
+ * uint8 plane has 256 distinct values, so it is done as histogram -> 256-entry table -> look-up.  Integer atomics only:
+ * every result is bitwise reproducible.
+ *
+ * dca_frame_hist: left, right (H,W,C) interleaved uint8, C = 3 or 4 (a fourth channel is ignored), H W < 2^31 ->
+ * hist[2][3][256] counts (zeroed by the launcher). */
+int dca_frame_hist(const unsigned char* left, const unsigned char* right, unsigned* hist, int H, int W, int C,
+                   hipStream_t stream);
+/* dca_frame_lut: hist and the pixel count n = H W -> lut[2][3][256] fp32 and stats[2][3][2] fp64 (mean, std), in this
+ * operation order, without fused multiply-adds:  S = sum h[v] v (64-bit integers);  mean = double(S) / double(n);
+ * var = (sum over v = 0..255 in this order of double(h[v]) * ((v - mean) * (v - mean))) / n;  std = sqrt(var);
+ * lut[v] = float((double(v) - mean) / std).  A constant plane gives std = 0 and NaN at its value (0/0), as numpy does. */
+int dca_frame_lut(const unsigned* hist, long n_pixels, float* lut, double* stats, hipStream_t stream);
+/* dca_frame_apply: the rows x cols window of the source images that starts at row src_y0, column 0, looked up in
+ * lut[2][3][256] (any table: dca_frame_lut's, or a fixed one) and written into the planar fp32 frames out_left,
+ * out_right (3,Hc,Wc) at row dst_y0, column 0.  Every other frame element is written as +0.0: the frames need no
+ * memset.  The window must fit the source (src_y0 + rows <= H, cols <= W) and the frame. */
+int dca_frame_apply(const unsigned char* left, const unsigned char* right, const float* lut, float* out_left,
+                    float* out_right, int H, int W, int C, int Hc, int Wc, int src_y0, int dst_y0, int rows, int cols,
+                    hipStream_t stream);
+/* dca_disp_export: the h x w window of pred (Hc,Wc) fp32 that starts at row y0, column 0 (my_img.py:105-108), as fp32
+ * (bit copy) and / or as uint16(pred * scale) (my_img.py:110 with scale 256: fp32 product, truncated toward zero,
+ * saturated to [0, 65535], NaN -> 0).  Either output may be NULL, not both. */
+int dca_disp_export(const float* pred, float* out_f32, unsigned short* out_u16, int Hc, int Wc, int y0, int h, int w,
+                    float scale, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
