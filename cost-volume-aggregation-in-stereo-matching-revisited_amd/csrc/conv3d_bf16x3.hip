@@ -463,18 +463,19 @@ extern "C" int dca_conv3d_x3_prep_weight(const float* w, void* wx, int A, int B,
 
 namespace {
 
-int x3_grid(long tiles, int cblks) {
-  // persistent: one workgroup per CU (the LDS footprint allows no more), each looping over its share of the tiles
-  int ncu = 256;   // per device, so not cached in a static
-  {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      ncu = v;
-  }
-  int gx = ncu / cblks > 0 ? ncu / cblks : 1;
-  if (gx > tiles) gx = (int)tiles;
-  return gx;
+// launch geometry: persistent, one workgroup per CU (the LDS footprint allows no more; gx per block of 32 output channels),
+// each looping over its share of the tiles; gx is also the number of statistics partials per channel
+struct X3Geom {
+  int nTD, nTH, nTW, cblks, gx;
+  long tiles;
+};
+X3Geom x3_geometry(int N, int Cout, int D, int H, int W) {
+  X3Geom g;
+  g.nTD = cdiv(D, TD); g.nTH = cdiv(H, TH); g.nTW = cdiv(W, TW);
+  g.tiles = (long)N * g.nTD * g.nTH * g.nTW;
+  g.cblks = (Cout + 31) / 32;
+  g.gx = dca_persistent_grid(g.tiles, g.cblks);
+  return g;
 }
 
 int x3_launch(const float* x, const void* wx, float* y, const float* scale, const float* shift, const float* res_pre,
@@ -489,10 +490,10 @@ int x3_launch(const float* x, const void* wx, float* y, const float* scale, cons
   a.scale = scale; a.shift = shift; a.res_pre = res_pre; a.res_post = res_post; a.slope = slope;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.NCH = (Cin + 15) / 16;
   a.D = D; a.H = H; a.W = W;
-  a.nTD = cdiv(D, TD); a.nTH = cdiv(H, TH); a.nTW = cdiv(W, TW);
+  const X3Geom g = x3_geometry(N, Cout, D, H, W);
+  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW;
   a.stat_part = stat_part;
-  const long tiles = (long)N * a.nTD * a.nTH * a.nTW;
-  DCA_REQUIRE(tiles < 0x7fffffffL && (Cout + 31) / 32 <= 65535);
+  DCA_REQUIRE(g.tiles < 0x7fffffffL && g.cblks <= 65535);
   const bool vec = (W % 4 == 0) && ((((uintptr_t)x) & 15) == 0);
   const bool stats = stat_part != nullptr;
   auto kern = stats ? (vec ? conv3_bf16x3_kernel<true, true> : conv3_bf16x3_kernel<false, true>)
@@ -500,8 +501,7 @@ int x3_launch(const float* x, const void* wx, float* y, const float* scale, cons
   const int lds = LDS_BYTES + (stats ? STAT_LDS : 0);
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return (int)e;
-  const int cblks = (Cout + 31) / 32;
-  hipLaunchKernelGGL(kern, dim3(x3_grid(tiles, cblks), cblks), dim3(512), lds, stream, a);
+  hipLaunchKernelGGL(kern, dim3(g.gx, g.cblks), dim3(512), lds, stream, a);
   return dca_launch_status();
 }
 
@@ -516,8 +516,7 @@ extern "C" int dca_conv3d_x3_forward(const float* x, const void* wx, float* y, c
 // nchunk of the statistics dca_conv3d_x3_forward_stats produces (one partial per workgroup of the launch it will make)
 extern "C" long dca_conv3d_x3_stats_chunks(int N, int Cout, int D, int H, int W) {
   if (N <= 0 || Cout <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-  const long tiles = (long)N * cdiv(D, TD) * cdiv(H, TH) * cdiv(W, TW);
-  return x3_grid(tiles, (Cout + 31) / 32);
+  return x3_geometry(N, Cout, D, H, W).gx;
 }
 
 // y = conv(x, w) (no epilogue) plus the BatchNorm batch statistics of y: part (Cout * nchunk * 4 doubles, nchunk =

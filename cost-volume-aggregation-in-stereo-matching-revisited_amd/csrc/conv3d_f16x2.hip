@@ -585,8 +585,9 @@ __global__ __launch_bounds__(512) void conv3_f16x2_kernel(X2Args a) {
 // Weight packing, once per launch (it needs the exponents of the operand the convolution is about to read).  One workgroup
 // per block of 32 output channels:
 //   1. xexps[k]: given, or (slots != null) derived here from the operand's per-channel maxima and written out for the
-//      weight-gradient kernel that reads the same operand later;
-//   2. f_o = 14 - max over (k, tap) of (exponent of w[o][k][tap]) - xexps[k]: the row's largest scaled entry in [2^14, 2^15);
+//      weight-gradient kernel that reads the same operand later (x2_prep_exps, dca_frag.h);
+//   2. f_o = 14 - max over (k, tap) of (exponent of w[o][k][tap]) - xexps[k]: the row's largest scaled entry in [2^14, 2^15)
+//      (x2_prep_row_scale, dca_frag.h);
 //   3. wx[cblk][chunk of 8 channels][tap pair p][term][lane][j] (f16): lane (r = lane & 31, h = lane >> 5) holds
 //      A[row = output channel cblk*32 + r][k = (input channel chunk*8 + j, tap 2p + h)] = w 2^(f_o - xexps[channel]), split
 //      into term 0/1 = h/l; zero padded (channels beyond Cin, the 28th tap);  f_o goes behind the images (ofo[cblk*32 + r]).
@@ -599,49 +600,9 @@ __global__ __launch_bounds__(512) void x2_prep_weight_kernel(const float* __rest
   __shared__ int xe[MAX_CIN];
   __shared__ int rowmax[PREP_ROWS][2];
   const int tid = threadIdx.x, cblk = blockIdx.x / (32 / PREP_ROWS), r0 = (blockIdx.x % (32 / PREP_ROWS)) * PREP_ROWS;
-  if (slots && !xexps_given) {     // 16 threads per channel, 32 channels per round; every workgroup derives its own copy
-    for (int c0 = 0; c0 < A; c0 += 32) {
-      const int c = c0 + (tid >> 4), l = tid & 15;
-      unsigned v = 0;
-      if (c < A)
-        for (int i = l; i < nslots; i += 16) { const unsigned u = slots[(long)c * DCA_AMAX_CSLOTS + i]; v = v > u ? v : u; }
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) { const unsigned u = (unsigned)__shfl_xor((int)v, o, 64); v = v > u ? v : u; }
-      if (c < A && l == 0) {
-        const int e = x2_scale_exp(v);
-        xe[c] = e;
-        if (blockIdx.x == 0) xexps[c] = e;
-      }
-    }
-  } else {
-    for (int c = tid; c < A; c += 512) xe[c] = dca_coherent_loadi(xexps + c);
-  }
+  x2_prep_exps(xe, A, slots, nslots, xexps, xexps_given);
   __syncthreads();
-  // row r = tid >> 7 (128 threads = 2 waves per output channel): exponent of the largest |w 2^-xexps[k]| of the row
-  {
-    const int r = tid >> 7, l = tid & 127, bi = cblk * 32 + r0 + r;
-    int m = -100000;
-    if (bi < Bn) {
-      for (int i = l; i < A * 27; i += 128) {
-        const int ai = i / 27, tap = i - ai * 27;
-        const float v = src_ab ? src[((long)ai * Bn + bi) * 27 + tap] : src[((long)bi * A + ai) * 27 + tap];
-        const int be = (int)((__float_as_uint(v) >> 23) & 255);      // biased exponent; 0: zero / denormal -> ignored
-        const int e = be == 0 ? -100000 : be - 127 - xe[ai];
-        m = m > e ? m : e;
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_xor(m, o, 64); m = m > u ? m : u; }
-    if ((l & 63) == 0) rowmax[r][l >> 6] = m;
-  }
-  __syncthreads();
-  if (tid < PREP_ROWS) {
-    const int m = rowmax[tid][0] > rowmax[tid][1] ? rowmax[tid][0] : rowmax[tid][1];
-    const int fo = m <= -100000 ? 0 : 14 - m;
-    rowmax[tid][0] = fo;
-    ofo[cblk * 32 + r0 + tid] = fo;
-  }
-  __syncthreads();
+  x2_prep_row_scale<32>(src, A, Bn, src_ab, xe, rowmax, cblk, r0, ofo);
   // items (chunk of 8 channels, tap pair, k half = tap of the pair, row): the 8 input channels of one lane's fragment,
   // both terms: two 16-byte stores
   const int nitems = NCH * NPAIR * 2 * PREP_ROWS;
@@ -700,19 +661,20 @@ extern "C" void dca_x2_debug_set_stamps(unsigned long long* p) { g_stamps = p; }
 
 namespace {
 
-int x2_grid(long tiles, int cblks) {
-  // persistent: one workgroup per CU, each looping over its share of the tiles
-  int ncu = 256;   // per device, so not cached in a static
-  {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      ncu = v;
-  }
-  int gx = ncu / cblks > 0 ? ncu / cblks : 1;
-  if (gx > tiles) gx = (int)tiles;
-  if (gx > DCA_AMAX_CSLOTS) gx = DCA_AMAX_CSLOTS;      // a workgroup index is also a slot of the per-channel output maxima
-  return gx;
+// launch geometry: persistent, one workgroup per CU (gx per block of 32 output channels), each looping over its share of the
+// tiles; gx is also the number of statistics partials and of y_cmax slots per channel
+struct X2Geom {
+  int nTD, nTH, nTW, cblks, gx;
+  long tiles;
+};
+X2Geom x2_geometry(int N, int Cout, int D, int H, int W) {
+  X2Geom g;
+  g.nTD = cdiv(D, TD); g.nTH = cdiv(H, TH); g.nTW = cdiv(W, TW);
+  g.tiles = (long)N * g.nTD * g.nTH * g.nTW;
+  g.cblks = (Cout + 31) / 32;
+  g.gx = dca_persistent_grid(g.tiles, g.cblks);
+  if (g.gx > DCA_AMAX_CSLOTS) g.gx = DCA_AMAX_CSLOTS;  // a workgroup index is also a slot of the per-channel output maxima
+  return g;
 }
 
 template <bool VEC, bool STATS, int EPI, bool PIN>
@@ -737,24 +699,23 @@ int x2_launch(const void* x, int packed, const int* xexps, const void* wx, float
   a.scale = scale; a.shift = shift; a.res_pre = res_pre; a.res_post = res_post; a.slope = slope;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.NCH = (Cin + 7) / 8;
   a.D = D; a.H = H; a.W = W;
-  a.nTD = cdiv(D, TD); a.nTH = cdiv(H, TH); a.nTW = cdiv(W, TW);
+  const X2Geom g = x2_geometry(N, Cout, D, H, W);
+  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW;
   a.stat_part = stat_part;
   a.xexps = xexps;
   a.y_cmax = y_cmax;
 #if X2_STAMP
   a.stamps = g_stamps;
 #endif
-  const int cblks = (Cout + 31) / 32;
+  const int cblks = g.cblks, gx = g.gx;
   a.ofo = (const int*)((const char*)wx + (long)cblks * a.NCH * A_CHUNK);
-  const long tiles = (long)N * a.nTD * a.nTH * a.nTW;
-  DCA_REQUIRE(tiles < 0x7fffffffL && cblks <= 65535);
+  DCA_REQUIRE(g.tiles < 0x7fffffffL && cblks <= 65535);
   const bool vec = (W % 4 == 0) && ((((uintptr_t)x) & 15) == 0);
   const bool stats = stat_part != nullptr;
   const bool full = scale != nullptr || res_pre != nullptr || slope != 1.f || y_cmax != nullptr;
   const int epi = full ? 1 : (res_post != nullptr ? 2 : 0);
   DCA_REQUIRE(!(stats && epi));    // the statistics are those of the raw convolution output
   const int lds = LDS_BYTES + TAB_BYTES + (stats ? STAT_LDS : 0);
-  const int gx = x2_grid(tiles, cblks);
   if (packed) {
     DCA_REQUIRE(epi != 1);         // the packed operand exists in training only (BatchNorm kernels write it)
     if (stats) return x2_go<true, true, 0, true>(a, gx, cblks, lds, stream);
@@ -785,8 +746,7 @@ extern "C" int dca_conv3d_x2_forward(const void* x, int packed, const int* xexps
 // also the number of y_cmax slots per channel dca_conv3d_x2_forward fills
 extern "C" long dca_conv3d_x2_stats_chunks(int N, int Cout, int D, int H, int W) {
   if (N <= 0 || Cout <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-  const long tiles = (long)N * cdiv(D, TD) * cdiv(H, TH) * cdiv(W, TW);
-  return x2_grid(tiles, (Cout + 31) / 32);
+  return x2_geometry(N, Cout, D, H, W).gx;
 }
 
 // y = conv(x, w) (no epilogue) plus the BatchNorm batch statistics of y: part (Cout * nchunk * 4 doubles, nchunk =

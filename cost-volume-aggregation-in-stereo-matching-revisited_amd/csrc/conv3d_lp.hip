@@ -539,15 +539,7 @@ extern "C" int dca_conv3d_lp_forward(const void* x, const void* wx, void* y, con
   DCA_REQUIRE(tiles < 0x7fffffffL && (Cout + 31) / 32 <= 65535);
   const bool vec = (W % 4 == 0) && ((((uintptr_t)x) & (in_f32 ? 15 : 7)) == 0);
   const int cblks = (Cout + 31) / 32;
-  int ncu = 256;
-  {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      ncu = v;
-  }
-  int gx = ncu / cblks > 0 ? ncu / cblks : 1;
-  if (gx > tiles) gx = (int)tiles;
+  const int gx = dca_persistent_grid(tiles, cblks);
   if (dtype == DCA_BF16) {
     if (in_f32) return out_f32 ? launch_lp<__bf16, true, true>(a, vec, gx, cblks, stream)
                                : launch_lp<__bf16, true, false>(a, vec, gx, cblks, stream);

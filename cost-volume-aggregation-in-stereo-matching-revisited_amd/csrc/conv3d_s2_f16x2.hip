@@ -374,48 +374,9 @@ __global__ __launch_bounds__(512) void s2x2_prep_weight_kernel(const float* __re
   __shared__ int xe[MAX_CIN];
   __shared__ int rowmax[PREP_ROWS][2];
   const int tid = threadIdx.x, cblk = blockIdx.x / (64 / PREP_ROWS), r0 = (blockIdx.x % (64 / PREP_ROWS)) * PREP_ROWS;
-  if (slots && !xexps_given) {
-    for (int c0 = 0; c0 < A; c0 += 32) {
-      const int c = c0 + (tid >> 4), l = tid & 15;
-      unsigned v = 0;
-      if (c < A)
-        for (int i = l; i < nslots; i += 16) { const unsigned u = slots[(long)c * DCA_AMAX_CSLOTS + i]; v = v > u ? v : u; }
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) { const unsigned u = (unsigned)__shfl_xor((int)v, o, 64); v = v > u ? v : u; }
-      if (c < A && l == 0) {
-        const int e = x2_scale_exp(v);
-        xe[c] = e;
-        if (blockIdx.x == 0) xexps[c] = e;
-      }
-    }
-  } else {
-    for (int c = tid; c < A; c += 512) xe[c] = dca_coherent_loadi(xexps + c);
-  }
+  x2_prep_exps(xe, A, slots, nslots, xexps, xexps_given);
   __syncthreads();
-  {
-    const int r = tid >> 7, l = tid & 127, bi = cblk * 64 + r0 + r;
-    int m = -100000;
-    if (bi < Bn) {
-      for (int i = l; i < A * 27; i += 128) {
-        const int ai = i / 27, tap = i - ai * 27;
-        const float v = src_ab ? src[((long)ai * Bn + bi) * 27 + tap] : src[((long)bi * A + ai) * 27 + tap];
-        const int be = (int)((__float_as_uint(v) >> 23) & 255);
-        const int e = be == 0 ? -100000 : be - 127 - xe[ai];
-        m = m > e ? m : e;
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_xor(m, o, 64); m = m > u ? m : u; }
-    if ((l & 63) == 0) rowmax[r][l >> 6] = m;
-  }
-  __syncthreads();
-  if (tid < PREP_ROWS) {
-    const int m = rowmax[tid][0] > rowmax[tid][1] ? rowmax[tid][0] : rowmax[tid][1];
-    const int fo = m <= -100000 ? 0 : 14 - m;
-    rowmax[tid][0] = fo;
-    ofo[cblk * 64 + r0 + tid] = fo;
-  }
-  __syncthreads();
+  x2_prep_row_scale<64>(src, A, Bn, src_ab, xe, rowmax, cblk, r0, ofo);
   const int nitems = NC4 * NSTEP * 2 * PREP_ROWS;
   unsigned short* out = dst + (long)cblk * NC4 * (A_CHUNK / 2);
   for (int it = tid; it < nitems; it += 512) {
@@ -464,20 +425,28 @@ extern "C" int dca_conv3d_s2x2_prep_weight(const float* w, void* wx, int A, int 
   return dca_launch_status();
 }
 
+// launch geometry from the input dims: persistent, one workgroup per CU (gx per block of 64 output channels), each looping
+// over its share of the tiles; gx is also the number of y_cmax slots per channel
+namespace {
+struct S2Geom {
+  int Do, Ho, Wo, nTD, nTH, nTW, cblks, gx;
+  long tiles;
+};
+S2Geom s2x2_geometry(int N, int Cout, int Di, int Hi, int Wi) {
+  S2Geom g;
+  g.Do = (Di + 1) / 2; g.Ho = (Hi + 1) / 2; g.Wo = (Wi + 1) / 2;
+  g.nTD = cdiv(g.Do, TD); g.nTH = cdiv(g.Ho, TH); g.nTW = cdiv(g.Wo, TW);
+  g.tiles = (long)N * g.nTD * g.nTH * g.nTW;
+  g.cblks = (Cout + 63) / 64;
+  g.gx = dca_persistent_grid(g.tiles, g.cblks);
+  return g;
+}
+}  // namespace
+
 // slots per channel that dca_conv3d_s2x2_forward fills in y_cmax (= its workgroups per block of 64 output channels)
 extern "C" long dca_conv3d_s2x2_out_slots(int N, int Cout, int Di, int Hi, int Wi) {
   if (N <= 0 || Cout <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0) return 0;
-  const long tiles = (long)N * cdiv((Di + 1) / 2, TD) * cdiv((Hi + 1) / 2, TH) * cdiv((Wi + 1) / 2, TW);
-  int ncu = 256;
-  {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-        v > 0)
-      ncu = v;
-  }
-  const int cblks = (Cout + 63) / 64;
-  long gx = ncu / cblks > 0 ? ncu / cblks : 1;
-  return gx < tiles ? gx : tiles;
+  return s2x2_geometry(N, Cout, Di, Hi, Wi).gx;
 }
 
 // y = act(conv3d(x, w, stride 2, padding 1) * scale[c] + shift[c]) + res_post (scale / shift / res_post may be null, slope 1 =
@@ -495,29 +464,19 @@ extern "C" int dca_conv3d_s2x2_forward(const float* x, const int* xexps, const v
   a.scale = scale; a.shift = shift; a.slope = slope; a.y_cmax = y_cmax;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.NC4 = (Cin + 3) / 4;
   a.Di = Di; a.Hi = Hi; a.Wi = Wi;
-  a.Do = (Di + 1) / 2; a.Ho = (Hi + 1) / 2; a.Wo = (Wi + 1) / 2;
+  const S2Geom g = s2x2_geometry(N, Cout, Di, Hi, Wi);
+  a.Do = g.Do; a.Ho = g.Ho; a.Wo = g.Wo;
   DCA_REQUIRE((long)(Cin + 3) * Di * Hi * Wi * 4 < 0x7ffffff0L && (long)(Cout + 63) * a.Do * a.Ho * a.Wo * 4 < 0x7ffffff0L);
-  a.nTD = cdiv(a.Do, TD); a.nTH = cdiv(a.Ho, TH); a.nTW = cdiv(a.Wo, TW);
+  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW;
   a.xexps = xexps;
-  const int cblks = (Cout + 63) / 64;
-  a.ofo = (const int*)((const char*)wx + (long)cblks * a.NC4 * A_CHUNK);
-  const long tiles = (long)N * a.nTD * a.nTH * a.nTW;
-  DCA_REQUIRE(tiles < 0x7fffffffL && cblks <= 65535);
-  int ncu = 256;
-  {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-        v > 0)
-      ncu = v;
-  }
-  int gx = ncu / cblks > 0 ? ncu / cblks : 1;
-  if (gx > tiles) gx = (int)tiles;
+  a.ofo = (const int*)((const char*)wx + (long)g.cblks * a.NC4 * A_CHUNK);
+  DCA_REQUIRE(g.tiles < 0x7fffffffL && g.cblks <= 65535);
   const int lds = LDS_BYTES + TAB_BYTES;
   const bool epi = scale != nullptr || slope != 1.f || y_cmax != nullptr;
-  DCA_REQUIRE(y_cmax == nullptr || gx <= DCA_AMAX_CSLOTS);
+  DCA_REQUIRE(y_cmax == nullptr || g.gx <= DCA_AMAX_CSLOTS);
   auto kern = epi ? conv3s2_f16x2_kernel<true> : conv3s2_f16x2_kernel<false>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, dim3(gx, cblks), dim3(512), lds, stream, a);
+  hipLaunchKernelGGL(kern, dim3(g.gx, g.cblks), dim3(512), lds, stream, a);
   return dca_launch_status();
 }

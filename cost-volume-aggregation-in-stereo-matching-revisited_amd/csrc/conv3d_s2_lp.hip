@@ -268,13 +268,6 @@ extern "C" int dca_conv3d_s2_lp_forward(const void* x, const void* wx, float* y,
   a.nTD = cdiv(a.Do, TD); a.nTH = cdiv(a.Ho, TH); a.nTW = cdiv(a.Wo, TW);
   const long tiles = (long)N * a.nTD * a.nTH * a.nTW;
   DCA_REQUIRE(tiles < 0x7fffffffL);
-  int ncu = 256;
-  {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      ncu = v;
-  }
-  const int gx = (int)(tiles < ncu ? tiles : ncu);
+  const int gx = dca_persistent_grid(tiles, 1);
   return dtype == DCA_BF16 ? launch_s2<__bf16>(a, gx, stream) : launch_s2<_Float16>(a, gx, stream);
 }

@@ -366,7 +366,7 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const float* __restr
   }
 }
 
-// shared with conv3d_wgrad_bf16x3.hip (same slab format)
+// shared with the split weight-gradient kernels (same slab format); declared in dca_common.h
 int dca_internal_wgrad_reduce(const float* part, float* dw, int nblk, int nCxT, int nCT, int K, int Cy, int Cx,
                               long s_cy, long s_cx, hipStream_t stream) {
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv((long)nCT * K * 1024, 64)), dim3(1024), 0, stream, part, dw, nblk,
@@ -374,6 +374,7 @@ int dca_internal_wgrad_reduce(const float* part, float* dw, int nblk, int nCxT, 
   return dca_launch_status();
 }
 
+// the constant 256, not dca_num_cus(): asking the device would change the grids on a partitioned device
 static int wg_workers(int ntiles, int nCT, int per_cu = 1) {
   int w = 256 * per_cu / nCT;
   if (w < 1) w = 1;
@@ -385,27 +386,34 @@ static int wg_tile_w(int ksize, int stride, int Wo) {
   return (cdiv(Wo, 16) * 16 < cdiv(Wo, 32) * 32) ? 16 : 32;
 }
 
-static void wg_geometry(int ksize, int stride, int N, int Do, int Ho, int Wo, int* nTD, int* nTH, int* nTW,
-                        long* ntiles) {
+// launch geometry: nblk workgroups per channel-tile pair (nCT of them), each writing one slab of K * 1024 floats
+struct WgGeom {
+  int nTD, nTH, nTW, nCxT, nCT, K, nblk;
+  long ntiles, part_floats;
+};
+static WgGeom wg_geometry(int ksize, int stride, int N, int Cx, int Cy, int Do, int Ho, int Wo) {
+  WgGeom g;
   if (ksize == 1) {
     const long DHW = (long)Do * Ho * Wo;
-    *nTD = *nTH = *nTW = 1;
-    *ntiles = (long)N * ((DHW + 255) / 256);
-    return;
+    g.nTD = g.nTH = g.nTW = 1;
+    g.ntiles = (long)N * ((DHW + 255) / 256);
+  } else {
+    const int TW = wg_tile_w(ksize, stride, Wo);
+    const int TD = stride == 1 ? 2 : 1, TH = stride == 1 ? (TW == 32 ? 4 : 8) : 2;
+    g.nTD = cdiv(Do, TD); g.nTH = cdiv(Ho, TH); g.nTW = cdiv(Wo, TW);
+    g.ntiles = (long)N * g.nTD * g.nTH * g.nTW;
   }
-  const int TW = wg_tile_w(ksize, stride, Wo);
-  const int TD = stride == 1 ? 2 : 1, TH = stride == 1 ? (TW == 32 ? 4 : 8) : 2;
-  *nTD = cdiv(Do, TD); *nTH = cdiv(Ho, TH); *nTW = cdiv(Wo, TW);
-  *ntiles = (long)N * *nTD * *nTH * *nTW;
+  g.nCxT = cdiv(Cx, 32);
+  g.nCT = g.nCxT * cdiv(Cy, 32);
+  g.K = ksize == 1 ? 1 : 27;
+  g.nblk = wg_workers((int)(g.ntiles < 65535 ? g.ntiles : 65535), g.nCT, ksize == 1 ? 2 : 1);
+  g.part_floats = (long)g.nblk * g.nCT * g.K * 1024;
+  return g;
 }
 
 // number of floats of scratch `part` needed by dca_conv3d_wgrad for this problem
 extern "C" long dca_conv3d_wgrad_workspace(int N, int Cx, int Cy, int Do, int Ho, int Wo, int ksize, int stride) {
-  int nTD, nTH, nTW; long ntiles;
-  wg_geometry(ksize, stride, N, Do, Ho, Wo, &nTD, &nTH, &nTW, &ntiles);
-  const int nCT = cdiv(Cx, 32) * cdiv(Cy, 32);
-  const int K = ksize == 1 ? 1 : 27;
-  return (long)wg_workers((int)(ntiles < 65535 ? ntiles : 65535), nCT, ksize == 1 ? 2 : 1) * nCT * K * 1024;
+  return wg_geometry(ksize, stride, N, Cx, Cy, Do, Ho, Wo).part_floats;
 }
 
 extern "C" int dca_conv3d_wgrad(const float* x, const float* dy, float* part, float* dw, int N, int Cx, int Cy, int Di,
@@ -419,16 +427,12 @@ extern "C" int dca_conv3d_wgrad(const float* x, const float* dy, float* part, fl
   WgArgs a;
   a.x = x; a.dy = dy; a.part = part; a.N = N; a.Cx = Cx; a.Cy = Cy;
   a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Do = Do; a.Ho = Ho; a.Wo = Wo;
-  long ntiles;
-  wg_geometry(ksize, stride, N, Do, Ho, Wo, &a.nTD, &a.nTH, &a.nTW, &ntiles);
-  DCA_REQUIRE(ntiles < (1L << 31));
-  a.ntiles = (int)ntiles;
+  const WgGeom g = wg_geometry(ksize, stride, N, Cx, Cy, Do, Ho, Wo);
+  DCA_REQUIRE(g.ntiles < (1L << 31));
+  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW; a.nCxT = g.nCxT;
+  a.ntiles = (int)g.ntiles;
   a.small_offsets = ((long)N * Cx * Di * Hi * Wi * 4 < 0x7ffffff0L) && ((long)N * Cy * Do * Ho * Wo * 4 < 0x7ffffff0L);
-  a.nCxT = cdiv(Cx, 32);
-  const int nCT = a.nCxT * cdiv(Cy, 32);
-  const int K = ksize == 1 ? 1 : 27;
-  const int nblk = wg_workers((int)(ntiles < 65535 ? ntiles : 65535), nCT, ksize == 1 ? 2 : 1);
-  const dim3 grid(nblk, nCT);
+  const dim3 grid(g.nblk, g.nCT);
   if (ksize == 1) {
     const long DHW = (long)Do * Ho * Wo;
     a.vecx = a.vecy = (DHW % 4 == 0) && ((((uintptr_t)x | (uintptr_t)dy) & 15) == 0);
@@ -461,9 +465,7 @@ extern "C" int dca_conv3d_wgrad(const float* x, const float* dy, float* part, fl
   }
   int st = dca_launch_status();
   if (st) return st;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv((long)nCT * K * 1024, 64)), dim3(1024), 0, stream, part, dw, nblk,
-                     a.nCxT, nCT, K, Cy, Cx, s_cy, s_cx);
-  return dca_launch_status();
+  return dca_internal_wgrad_reduce(part, dw, g.nblk, g.nCxT, g.nCT, g.K, Cy, Cx, s_cy, s_cx, stream);
 }
 
 // Weight gradient of the 32 -> 1 logit heads (nn.Conv3d(C, 1, 3, padding=1, bias=False): `classif*.2`
@@ -478,21 +480,16 @@ extern "C" int dca_conv3d_c1_wgrad(const float* x, const float* dy, float* part,
   WgArgs a;
   a.x = x; a.dy = dy; a.part = part; a.N = N; a.Cx = C; a.Cy = 27;
   a.Di = a.Do = D; a.Hi = a.Ho = H; a.Wi = a.Wo = W;
-  long ntiles;
-  wg_geometry(1, 1, N, D, H, W, &a.nTD, &a.nTH, &a.nTW, &ntiles);
-  DCA_REQUIRE(ntiles < (1L << 31));
-  a.ntiles = (int)ntiles;
+  const WgGeom g = wg_geometry(1, 1, N, C, 27, D, H, W);    // the 27 taps are the dy "channels": one block of 32
+  DCA_REQUIRE(g.ntiles < (1L << 31));
+  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW; a.nCxT = g.nCxT;
+  a.ntiles = (int)g.ntiles;
   a.small_offsets = 1; a.vecx = a.vecy = 1;
-  a.nCxT = cdiv(C, 32);
-  const int nCT = a.nCxT;
-  const int nblk = wg_workers((int)(ntiles < 65535 ? ntiles : 65535), nCT, 2);
   const size_t lds = (size_t)2 * 32 * 257 * 4;
   hipError_t e = hipFuncSetAttribute((const void*)wgrad1_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(wgrad1_kernel<true>, dim3(nblk, nCT), dim3(256), lds, stream, a);
+  hipLaunchKernelGGL(wgrad1_kernel<true>, dim3(g.nblk, g.nCT), dim3(256), lds, stream, a);
   int st = dca_launch_status();
   if (st) return st;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv((long)nCT * 1024, 64)), dim3(1024), 0, stream, part, dw, nblk, a.nCxT,
-                     nCT, 1, 27, C, 1L, 27L);
-  return dca_launch_status();
+  return dca_internal_wgrad_reduce(part, dw, g.nblk, g.nCxT, g.nCT, 1, 27, C, 1L, 27L, stream);
 }

@@ -24,9 +24,6 @@
 #include "dca_frag.h"
 #include <type_traits>
 
-int dca_internal_wgrad_reduce(const float* part, float* dw, int nblk, int nCxT, int nCT, int K, int Cy, int Cx,
-                              long s_cy, long s_cx, hipStream_t stream);  // conv3d_wgrad.hip
-
 // WX3_STAMP (debug build, tools/wx3_stamps.py): `part` is followed by an unsigned long long stamp buffer (the tool
 // allocates it) that receives s_memtime stamps of the first 64 tiles of workgroup 0, waves 0 and 3
 #ifndef WX3_STAMP
@@ -281,15 +278,20 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
   }
 }
 
-int workers(long ntiles, int nCT) {
-  int ncu = 256;
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-      v > 0)
-    ncu = v;
-  long w = ncu / nCT;
-  if (w < 1) w = 1;
-  return (int)(ntiles < w ? ntiles : w);
+// launch geometry: nblk persistent workgroups per channel-tile pair, each writing one slab of 27 * 1024 floats
+struct WX3Geom {
+  int nTD, nTH, nTW, nCxT, nCT, nblk;
+  long ntiles, part_floats;
+};
+WX3Geom wx3_geometry(int N, int Cx, int Cy, int D, int H, int W) {
+  WX3Geom g;
+  g.nTD = cdiv(D, TD); g.nTH = cdiv(H, TH); g.nTW = cdiv(W, TW);
+  g.ntiles = (long)N * g.nTD * g.nTH * g.nTW;
+  g.nCxT = cdiv(Cx, 32);
+  g.nCT = g.nCxT * cdiv(Cy, 32);
+  g.nblk = dca_persistent_grid(g.ntiles, g.nCT);
+  g.part_floats = (long)g.nblk * g.nCT * 27 * 1024;
+  return g;
 }
 
 }  // namespace
@@ -297,9 +299,7 @@ int workers(long ntiles, int nCT) {
 // floats of scratch `part` dca_conv3d_wgrad_x3 needs
 extern "C" long dca_conv3d_wgrad_x3_workspace(int N, int Cx, int Cy, int D, int H, int W) {
   if (N <= 0 || Cx <= 0 || Cy <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-  const long ntiles = (long)N * cdiv(D, TD) * cdiv(H, TH) * cdiv(W, TW);
-  const int nCT = cdiv(Cx, 32) * cdiv(Cy, 32);
-  return (long)workers(ntiles, nCT) * nCT * 27 * 1024;
+  return wx3_geometry(N, Cx, Cy, D, H, W).part_floats;
 }
 
 // dw[cy*s_cy + cx*s_cx + tap] = sum dy[cy] * x[cx] shifted by the tap (3x3x3, stride 1, pad 1); x (N,Cx,D,H,W),
@@ -311,17 +311,14 @@ extern "C" int dca_conv3d_wgrad_x3(const float* x, const float* dy, float* part,
   DCA_REQUIRE((long)Cx * D * H * W * 4 < 0x7ffffff0L && (long)Cy * D * H * W * 4 < 0x7ffffff0L);
   WX3Args a;
   a.x = x; a.dy = dy; a.part = part; a.N = N; a.Cx = Cx; a.Cy = Cy; a.D = D; a.H = H; a.W = W;
-  a.nTD = cdiv(D, TD); a.nTH = cdiv(H, TH); a.nTW = cdiv(W, TW); a.nCxT = cdiv(Cx, 32);
-  const long ntiles = (long)N * a.nTD * a.nTH * a.nTW;
-  DCA_REQUIRE(ntiles < 0x7fffffffL);
-  const int nCT = a.nCxT * cdiv(Cy, 32);
-  DCA_REQUIRE(nCT <= 65535);
-  const int nblk = workers(ntiles, nCT);
+  const WX3Geom g = wx3_geometry(N, Cx, Cy, D, H, W);
+  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW; a.nCxT = g.nCxT;
+  DCA_REQUIRE(g.ntiles < 0x7fffffffL && g.nCT <= 65535);
   hipError_t e = hipFuncSetAttribute((const void*)wgrad3_bf16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      LDS_BYTES);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(wgrad3_bf16x3_kernel, dim3(nblk, nCT), dim3(512), LDS_BYTES, stream, a);
+  hipLaunchKernelGGL(wgrad3_bf16x3_kernel, dim3(g.nblk, g.nCT), dim3(512), LDS_BYTES, stream, a);
   int st = dca_launch_status();
   if (st) return st;
-  return dca_internal_wgrad_reduce(part, dw, nblk, a.nCxT, nCT, 27, Cy, Cx, s_cy, s_cx, stream);
+  return dca_internal_wgrad_reduce(part, dw, g.nblk, g.nCxT, g.nCT, 27, Cy, Cx, s_cy, s_cx, stream);
 }

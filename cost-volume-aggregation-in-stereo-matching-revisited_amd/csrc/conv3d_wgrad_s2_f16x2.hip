@@ -27,9 +27,6 @@
 #include "dca_frag.h"
 #include <type_traits>
 
-int dca_internal_wgrad_reduce(const float* part, float* dw, int nblk, int nCxT, int nCT, int K, int Cy, int Cx,
-                              long s_cy, long s_cx, hipStream_t stream);  // conv3d_wgrad.hip
-
 namespace {
 
 constexpr int NT = 2;                                 // terms per operand
@@ -270,15 +267,23 @@ __global__ __launch_bounds__(512) void wgrad3s2_f16x2_kernel(WS2Args a) {
   }
 }
 
-int workers(long ntiles, int nCT) {
-  int ncu = 256;
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-      v > 0)
-    ncu = v;
-  long w = ncu / nCT;
-  if (w < 1) w = 1;
-  return (int)(ntiles < w ? ntiles : w);
+// launch geometry from the FINE dims D, H, W: nblk persistent workgroups per (32 x channels, 64 dy channels) block pair, each
+// writing its two slabs of 27 * 1024 floats per 32 x 32 channel tile (nCT of them)
+struct WS2Geom {
+  int Do, Ho, Wo, nTD, nTH, nTW, nCxT, nCyP, nWG, nCT, nblk;
+  long ntiles, part_floats;
+};
+WS2Geom ws2_geometry(int N, int Cx, int Cy, int D, int H, int W) {
+  WS2Geom g;
+  g.Do = (D + 1) / 2; g.Ho = (H + 1) / 2; g.Wo = (W + 1) / 2;
+  g.nTD = g.Do; g.nTH = cdiv(g.Ho, TH); g.nTW = cdiv(g.Wo, TW);
+  g.ntiles = (long)N * g.nTD * g.nTH * g.nTW;
+  g.nCxT = cdiv(Cx, 32); g.nCyP = cdiv(Cy, 64);
+  g.nWG = g.nCxT * g.nCyP;
+  g.nCT = g.nCxT * cdiv(Cy, 32);
+  g.nblk = dca_persistent_grid(g.ntiles, g.nWG);
+  g.part_floats = (long)g.nblk * g.nCT * 27 * 1024;
+  return g;
 }
 
 }  // namespace
@@ -286,10 +291,7 @@ int workers(long ntiles, int nCT) {
 // floats of scratch `part` dca_conv3d_wgrad_s2_x2 needs; D, H, W = FINE dims
 extern "C" long dca_conv3d_wgrad_s2_x2_workspace(int N, int Cx, int Cy, int D, int H, int W) {
   if (N <= 0 || Cx <= 0 || Cy <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-  const int Do = (D + 1) / 2, Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-  const long ntiles = (long)N * Do * cdiv(Ho, TH) * cdiv(Wo, TW);
-  const int nWG = cdiv(Cx, 32) * cdiv(Cy, 64);
-  return (long)workers(ntiles, nWG) * cdiv(Cx, 32) * cdiv(Cy, 32) * 27 * 1024;
+  return ws2_geometry(N, Cx, Cy, D, H, W).part_floats;
 }
 
 // dw[cy*s_cy + cx*s_cx + tap] = sum_{n, o} c[n][cy][o] * f[n][cx][2 o + tap - 1] (3x3x3, stride 2, pad 1); f (N,Cx,D,H,W),
@@ -302,20 +304,17 @@ extern "C" int dca_conv3d_wgrad_s2_x2(const float* f, const int* f_exps, const f
   WS2Args a;
   a.x = f; a.dy = c; a.part = part; a.xexps = f_exps; a.yexps = c_exps;
   a.N = N; a.Cx = Cx; a.Cy = Cy; a.D = D; a.H = H; a.W = W;
-  a.Do = (D + 1) / 2; a.Ho = (H + 1) / 2; a.Wo = (W + 1) / 2;
+  const WS2Geom g = ws2_geometry(N, Cx, Cy, D, H, W);
+  a.Do = g.Do; a.Ho = g.Ho; a.Wo = g.Wo;
   DCA_REQUIRE(W % 4 == 0 && a.Wo % 4 == 0 && ((((uintptr_t)f | (uintptr_t)c) & 15) == 0));
   DCA_REQUIRE((long)Cx * D * H * W * 4 < 0x7ffffff0L && (long)Cy * a.Do * a.Ho * a.Wo * 4 < 0x7ffffff0L);
-  a.nTD = a.Do; a.nTH = cdiv(a.Ho, TH); a.nTW = cdiv(a.Wo, TW); a.nCxT = cdiv(Cx, 32); a.nCyP = cdiv(Cy, 64);
-  const long ntiles = (long)N * a.nTD * a.nTH * a.nTW;
-  DCA_REQUIRE(ntiles < 0x7fffffffL);
-  const int nWG = a.nCxT * a.nCyP, nCT = a.nCxT * cdiv(Cy, 32);
-  DCA_REQUIRE(nWG <= 65535);
-  const int nblk = workers(ntiles, nWG);
+  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW; a.nCxT = g.nCxT; a.nCyP = g.nCyP;
+  DCA_REQUIRE(g.ntiles < 0x7fffffffL && g.nWG <= 65535);
   const int lds = LDS_BYTES + 96 * 4;      // + the exponents of the block's channels
   hipError_t e = hipFuncSetAttribute((const void*)wgrad3s2_f16x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(wgrad3s2_f16x2_kernel, dim3(nblk, nWG), dim3(512), lds, stream, a);
+  hipLaunchKernelGGL(wgrad3s2_f16x2_kernel, dim3(g.nblk, g.nWG), dim3(512), lds, stream, a);
   int st = dca_launch_status();
   if (st) return st;
-  return dca_internal_wgrad_reduce(part, dw, nblk, a.nCxT, nCT, 27, Cy, Cx, s_cy, s_cx, stream);
+  return dca_internal_wgrad_reduce(part, dw, g.nblk, g.nCxT, g.nCT, 27, Cy, Cx, s_cy, s_cx, stream);
 }

@@ -19,6 +19,28 @@ static inline int dca_launch_status() { return (int)hipGetLastError(); }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// ---- launch geometry (host) ---------------------------------------------------------------------------------------------
+// A kernel whose launch sizes a caller-allocated buffer (statistics partials, y_cmax slots, weight-gradient slabs) has ONE
+// static function that fills a small geometry record from the problem dimensions; its extern "C" size query and its
+// launcher both call that function and nothing else.
+// CUs of the current device, 256 if it cannot be asked.  Per device, so not cached in a static.
+static inline int dca_num_cus() {
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+      v > 0)
+    return v;
+  return 256;
+}
+// persistent grid: the workgroups along x of a launch whose `share` grid rows (channel blocks) divide the CUs among them,
+// each workgroup looping over its part of the tiles
+static inline int dca_persistent_grid(long tiles, int share) {
+  const int ncu = dca_num_cus(), g = ncu > share ? ncu / share : 1;
+  return (int)(tiles < g ? tiles : g);
+}
+// sums the weight-gradient slabs part[blk][ct][tap][32 x 32] of nblk workgroups into dw (conv3d_wgrad.hip)
+int dca_internal_wgrad_reduce(const float* part, float* dw, int nblk, int nCxT, int nCT, int K, int Cy, int Cx, long s_cy,
+                              long s_cx, hipStream_t stream);
+
 // Blocks are dealt round-robin over the 8 XCDs (private L2 each): give every XCD a contiguous
 // chunk of the logical tile space so neighbouring tiles (which share halos) hit the same L2.
 // Bijective for any grid size (cdna_hip_programming.md, T1).

@@ -57,6 +57,67 @@ __device__ __forceinline__ void x2_split(float v, int e, _Float16& h, _Float16& 
   h = (_Float16)u;
   l = (_Float16)(u - (float)h);   // the residual is exact in fp32
 }
+
+// The scales of an f16x2 weight image (x2_prep_weight_kernel, s2x2_prep_weight_kernel: workgroups of 512 threads, each
+// packing 4 output channels of a block of CBLK): entry (o, k, tap) is stored as w 2^(f_o - xexps[k]), so these two rules are
+// a contract with the forward kernels (ofo) and with the weight-gradient kernels that read xexps later.
+// 1. xe[k] (LDS, k < A) = the operand's per-channel exponents: loaded from xexps when given, else derived from the
+//    operand's per-channel maxima slots[k * DCA_AMAX_CSLOTS + s], s < nslots (16 threads per channel, 32 channels per round;
+//    every workgroup derives its own copy) and written to xexps by workgroup 0.  The caller syncs before reading xe.
+__device__ __forceinline__ void x2_prep_exps(int* xe, int A, const unsigned* __restrict__ slots, int nslots,
+                                             int* __restrict__ xexps, int xexps_given) {
+  const int tid = threadIdx.x;
+  if (slots && !xexps_given) {
+    for (int c0 = 0; c0 < A; c0 += 32) {
+      const int c = c0 + (tid >> 4), l = tid & 15;
+      unsigned v = 0;
+      if (c < A)
+        for (int i = l; i < nslots; i += 16) { const unsigned u = slots[(long)c * DCA_AMAX_CSLOTS + i]; v = v > u ? v : u; }
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) { const unsigned u = (unsigned)__shfl_xor((int)v, o, 64); v = v > u ? v : u; }
+      if (c < A && l == 0) {
+        const int e = x2_scale_exp(v);
+        xe[c] = e;
+        if (blockIdx.x == 0) xexps[c] = e;
+      }
+    }
+  } else {
+    for (int c = tid; c < A; c += 512) xe[c] = dca_coherent_loadi(xexps + c);
+  }
+}
+// 2. f_o = 14 - max over (k, tap) of (exponent of w[o][k][tap]) - xe[k]: the row's largest scaled entry lands in
+//    [2^14, 2^15); 0 for an all-zero row.  Row r = tid >> 7 (128 threads = 2 waves per output channel) is output channel
+//    cblk * CBLK + r0 + r; f_o is left in rowmax[r][0] (LDS, synced) and written to ofo.
+template <int CBLK>
+__device__ __forceinline__ void x2_prep_row_scale(const float* __restrict__ src, int A, int Bn, int src_ab, const int* xe,
+                                                  int (*rowmax)[2], int cblk, int r0, int* __restrict__ ofo) {
+  const int tid = threadIdx.x;
+  {
+    const int r = tid >> 7, l = tid & 127, bi = cblk * CBLK + r0 + r;
+    int m = -100000;
+    if (bi < Bn) {
+      for (int i = l; i < A * 27; i += 128) {
+        const int ai = i / 27, tap = i - ai * 27;
+        const float v = src_ab ? src[((long)ai * Bn + bi) * 27 + tap] : src[((long)bi * A + ai) * 27 + tap];
+        const int be = (int)((__float_as_uint(v) >> 23) & 255);      // biased exponent; 0: zero / denormal -> ignored
+        const int e = be == 0 ? -100000 : be - 127 - xe[ai];
+        m = m > e ? m : e;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_xor(m, o, 64); m = m > u ? m : u; }
+    if ((l & 63) == 0) rowmax[r][l >> 6] = m;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    const int m = rowmax[tid][0] > rowmax[tid][1] ? rowmax[tid][0] : rowmax[tid][1];
+    const int fo = m <= -100000 ? 0 : 14 - m;
+    rowmax[tid][0] = fo;
+    ofo[cblk * CBLK + r0 + tid] = fo;
+  }
+  __syncthreads();
+}
+
 // bf16x3: v = h + m + l
 __device__ __forceinline__ void x3_split(float v, __bf16& h, __bf16& m, __bf16& l) {
   h = (__bf16)v;

@@ -305,13 +305,6 @@ extern "C" int dca_deconv3d_lp_forward(const float* x, const void* wx, void* y, 
   const long tiles = (long)N * a.nTD * a.nTH * a.nTW;
   DCA_REQUIRE(tiles < 0x7fffffffL);
   const bool vec = (Wi % 4 == 0) && ((((uintptr_t)x) & 15) == 0);
-  int ncu = 256;
-  {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      ncu = v;
-  }
-  const int gx = (int)(tiles < ncu ? tiles : ncu);
+  const int gx = dca_persistent_grid(tiles, 1);
   return dtype == DCA_BF16 ? launch_dl<__bf16>(a, vec, gx, stream) : launch_dl<_Float16>(a, vec, gx, stream);
 }

@@ -481,19 +481,18 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
   if constexpr (STATS) flush_stats();
 }
 
-}  // namespace
-
-namespace {
-
-int dx_grid(long tiles) {
-  int ncu = 256;
-  {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      ncu = v;
-  }
-  return (int)(tiles < ncu ? tiles : ncu);
+// launch geometry (Di, Hi, Wi = input dims): persistent, one workgroup per CU; gx is also the number of statistics partials
+// per channel
+struct DxGeom {
+  int nTD, nTH, nTW, gx;
+  long tiles;
+};
+DxGeom dx_geometry(int N, int Di, int Hi, int Wi) {
+  DxGeom g;
+  g.nTD = cdiv(Di, TD); g.nTH = cdiv(Hi, TH); g.nTW = cdiv(Wi, TW);
+  g.tiles = (long)N * g.nTD * g.nTH * g.nTW;
+  g.gx = dca_persistent_grid(g.tiles, 1);
+  return g;
 }
 
 int dx_launch(const float* x, const void* wx, float* y, const float* scale, const float* shift, const float* res_pre,
@@ -509,16 +508,16 @@ int dx_launch(const float* x, const void* wx, float* y, const float* scale, cons
   a.res_pre = res_pre; a.res_post = res_post; a.slope = slope;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.NCH = (Cin + 15) / 16;
   a.Di = Di; a.Hi = Hi; a.Wi = Wi;
-  a.nTD = cdiv(Di, TD); a.nTH = cdiv(Hi, TH); a.nTW = cdiv(Wi, TW);
+  const DxGeom g = dx_geometry(N, Di, Hi, Wi);
+  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW;
   a.stat_part = stat_part;
-  const long tiles = (long)N * a.nTD * a.nTH * a.nTW;
-  DCA_REQUIRE(tiles < 0x7fffffffL);
+  DCA_REQUIRE(g.tiles < 0x7fffffffL);
   const bool stats = stat_part != nullptr;
   auto kern = stats ? deconv3_bf16x3_kernel<true> : deconv3_bf16x3_kernel<false>;
   const int lds = LDS_BYTES + (stats ? STAT_LDS : 0);
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, dim3(dx_grid(tiles)), dim3(512), lds, stream, a);
+  hipLaunchKernelGGL(kern, dim3(g.gx), dim3(512), lds, stream, a);
   return dca_launch_status();
 }
 
@@ -534,7 +533,7 @@ extern "C" int dca_deconv3d_x3_forward(const float* x, const void* wx, float* y,
 // nchunk of the statistics dca_deconv3d_x3_forward_stats produces (one partial per workgroup of the launch it will make)
 extern "C" long dca_deconv3d_x3_stats_chunks(int N, int Di, int Hi, int Wi) {
   if (N <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0) return 0;
-  return dx_grid((long)N * cdiv(Di, TD) * cdiv(Hi, TH) * cdiv(Wi, TW));
+  return dx_geometry(N, Di, Hi, Wi).gx;
 }
 
 // y = deconv(x, w) (no epilogue) plus the BatchNorm batch statistics of y: part (Cout * nchunk * 4 doubles) = one

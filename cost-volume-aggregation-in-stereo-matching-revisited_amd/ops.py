@@ -493,6 +493,38 @@ def _prep_weight(w_src, A, B, K, src_ab, flip, ksize, stride, transposed, b_off=
                  (0, A, Bn, Apad, Bpad, K, int(src_ab), int(flip), B, b_off)), Apad
 
 
+def _x2_weights(prefix, x, w_src, A, B, src_ab, flip, cached_key):
+    """(wx, xexps) for ONE launch of the f16x2-family convolution `prefix` ("dca_conv3d_x2" / "dca_conv3d_s2x2") over operand
+    x.  The weights are packed per launch: the image folds the operand's per-channel exponents in (dca_hip.h).  Exponents x
+    already carries are used (counted under AMAX_STATS[cached_key]); otherwise the packing kernel derives them from the
+    operand's slots on the way and they stay on the tensor for later users (the weight gradient of this convolution, other
+    convolutions over the same tensor)."""
+    lib = _L()
+    wx = torch.empty((getattr(lib, prefix + "_weight_bytes")(A, B) // 2,), device=x.device, dtype=torch.int16)
+    xexps = _exps_cached(x)
+    if xexps is not None:
+        AMAX_STATS[cached_key] += 1
+        slots, nslots = None, 0
+    else:
+        slots, nslots = _slots_of(x)
+        xexps = torch.empty((A,), device=x.device, dtype=torch.int32)
+    _chk(getattr(lib, prefix + "_prep_weight")(_ptr(w_src), _ptr(wx), A, B, int(src_ab), int(flip), _ptr(slots), nslots,
+                                               _ptr(xexps), _stream()), prefix + "_prep_weight")
+    if slots is not None:
+        x._dca_exps = (xexps, _ver(x))
+    return wx, xexps
+
+
+def _x3_weights(w_src, A, B, src_ab, flip):
+    """the bf16x3 fragments of a 3x3x3 weight (conv3d_bf16x3.hip and deconv3d_x3.hip read the same image), memoised"""
+    def build():
+        w3 = torch.empty((_L().dca_conv3d_x3_weight_bytes(A, B) // 2,), device=w_src.device, dtype=torch.int16)
+        _chk(_L().dca_conv3d_x3_prep_weight(_ptr(w_src), _ptr(w3), A, B, int(src_ab), int(flip), _stream()),
+             "dca_conv3d_x3_prep_weight")
+        return w3
+    return _memo(("x3prep", A, B, int(src_ab), int(flip)), (w_src,), build, (1, A, B, 0, 0, 27, int(src_ab), int(flip), B, 0))
+
+
 def _out_dims(dims, ksize, stride, transposed):
     if ksize == 1 or stride == 1:
         return tuple(dims)
@@ -528,21 +560,7 @@ def _conv_sliced_impl(x, x2, w_src, A, B, K, src_ab, flip, ksize, stride, transp
     width = _slice_width(ksize, stride, transposed, B)
     lib = _L()
     if CONV_X2 and _x3_eligible(x, x2, ksize, stride, transposed, A, B):
-        # the weights are packed per launch: the image folds the operand's per-channel exponents in (dca_hip.h); the
-        # packing kernel derives them from the operand's slots on the way and leaves them on the tensor for later users
-        # (the weight gradient of this convolution, other convolutions over the same tensor)
-        wx = torch.empty((lib.dca_conv3d_x2_weight_bytes(A, B) // 2,), device=x.device, dtype=torch.int16)
-        xexps = _exps_cached(x)
-        if xexps is not None:
-            AMAX_STATS["packed" if packed else "tagged"] += 1
-            slots, nslots = None, 0
-        else:
-            slots, nslots = _slots_of(x)
-            xexps = torch.empty((A,), device=x.device, dtype=torch.int32)
-        _chk(lib.dca_conv3d_x2_prep_weight(_ptr(w_src), _ptr(wx), A, B, int(src_ab), int(flip), _ptr(slots), nslots,
-                                           _ptr(xexps), _stream()), "dca_conv3d_x2_prep_weight")
-        if slots is not None:
-            x._dca_exps = (xexps, _ver(x))
+        wx, xexps = _x2_weights("dca_conv3d_x2", x, w_src, A, B, src_ab, flip, "packed" if packed else "tagged")
         if want_stats:
             nchunk = lib.dca_conv3d_x2_stats_chunks(N, B, Di, Hi, Wi)
             part = torch.empty((B * nchunk * 4,), device=x.device, dtype=torch.float64)
@@ -556,13 +574,7 @@ def _conv_sliced_impl(x, x2, w_src, A, B, K, src_ab, flip, ksize, stride, transp
         _tag_cmax(y, ycm, lib.dca_conv3d_x2_stats_chunks(N, B, Di, Hi, Wi))
         return y, None
     if _x3_eligible(x, x2, ksize, stride, transposed, A, B):
-        def build_x3():
-            w3 = torch.empty((lib.dca_conv3d_x3_weight_bytes(A, B) // 2,), device=x.device, dtype=torch.int16)
-            _chk(lib.dca_conv3d_x3_prep_weight(_ptr(w_src), _ptr(w3), A, B, int(src_ab), int(flip), _stream()),
-                 "dca_conv3d_x3_prep_weight")
-            return w3
-        wx = _memo(("x3prep", A, B, int(src_ab), int(flip)), (w_src,), build_x3,
-                   (1, A, B, 0, 0, 27, int(src_ab), int(flip), B, 0))
+        wx = _x3_weights(w_src, A, B, src_ab, flip)
         if want_stats:
             nchunk = lib.dca_conv3d_x3_stats_chunks(N, B, Di, Hi, Wi)
             part = torch.empty((B * nchunk * 4,), device=x.device, dtype=torch.float64)
@@ -574,18 +586,7 @@ def _conv_sliced_impl(x, x2, w_src, A, B, K, src_ab, flip, ksize, stride, transp
              "dca_conv3d_x3_forward")
         return y, None
     if _s2x2_eligible(x, x2, ksize, stride, transposed, A, B, scale, res_pre, slope):
-        wx = torch.empty((lib.dca_conv3d_s2x2_weight_bytes(A, B) // 2,), device=x.device, dtype=torch.int16)
-        xexps = _exps_cached(x)
-        if xexps is not None:
-            AMAX_STATS["tagged"] += 1
-            slots, nslots = None, 0
-        else:
-            slots, nslots = _slots_of(x)
-            xexps = torch.empty((A,), device=x.device, dtype=torch.int32)
-        _chk(lib.dca_conv3d_s2x2_prep_weight(_ptr(w_src), _ptr(wx), A, B, int(src_ab), int(flip), _ptr(slots), nslots,
-                                             _ptr(xexps), _stream()), "dca_conv3d_s2x2_prep_weight")
-        if slots is not None:
-            x._dca_exps = (xexps, _ver(x))
+        wx, xexps = _x2_weights("dca_conv3d_s2x2", x, w_src, A, B, src_ab, flip, "tagged")
         nsl = lib.dca_conv3d_s2x2_out_slots(N, B, Di, Hi, Wi)
         ycm = _cslots(B, x.device) if (emit_amax and nsl <= CSLOTS) else None
         _chk(lib.dca_conv3d_s2x2_forward(_ptr(x), _ptr(xexps), _ptr(wx), _ptr(y), _ptr(scale), _ptr(shift), float(slope),
@@ -594,13 +595,7 @@ def _conv_sliced_impl(x, x2, w_src, A, B, K, src_ab, flip, ksize, stride, transp
             _tag_cmax(y, ycm, nsl)
         return y, None
     if _dx3_eligible(x, x2, ksize, stride, transposed, A, B):
-        def build_dx3():
-            w3 = torch.empty((lib.dca_conv3d_x3_weight_bytes(A, B) // 2,), device=x.device, dtype=torch.int16)
-            _chk(lib.dca_conv3d_x3_prep_weight(_ptr(w_src), _ptr(w3), A, B, int(src_ab), int(flip), _stream()),
-                 "dca_conv3d_x3_prep_weight")
-            return w3
-        wx = _memo(("x3prep", A, B, int(src_ab), int(flip)), (w_src,), build_dx3,
-                   (1, A, B, 0, 0, 27, int(src_ab), int(flip), B, 0))
+        wx = _x3_weights(w_src, A, B, src_ab, flip)
         if want_stats:
             nchunk = lib.dca_deconv3d_x3_stats_chunks(N, Di, Hi, Wi)
             part = torch.empty((B * nchunk * 4,), device=x.device, dtype=torch.float64)

@@ -33,6 +33,90 @@ def test_capi_argument_counts_match_header():
         assert len([a for a in m.group(1).split(",") if a.strip() and a.strip() != "void"]) == len(args), name
 
 
+# Every size query of the C ABI at shapes that are no tile multiples and sit on both sides of each clip (tiles below and
+# above the workgroups the grid rule allows, more channel blocks than CUs, the slot and block caps), on a 256-CU device --
+# also what a query assumes when no device can be asked.  Recorded from the library before the queries and the launchers
+# were given one geometry function each: a caller allocates with these, the launch indexes with them.
+SIZE_QUERIES = {
+    "dca_conv3d_x2_stats_chunks": {
+        (1, 32, 5, 9, 20): 8,
+        (2, 32, 48, 136, 240): 256,
+        (2, 64, 48, 136, 240): 128,
+        (3, 32, 20, 40, 64): 256,
+        (1, 96, 5, 9, 20): 8,
+        (1, 8224, 5, 9, 20): 1,
+        (8, 8, 48, 136, 240): 256,
+    },
+    "dca_conv3d_x3_stats_chunks": {
+        (1, 32, 5, 9, 20): 8,
+        (3, 32, 20, 40, 64): 256,
+        (2, 64, 48, 136, 240): 128,
+        (1, 8224, 5, 9, 20): 1,
+    },
+    "dca_conv3d_s2x2_out_slots": {
+        (1, 64, 6, 10, 24): 4,
+        (4, 64, 48, 136, 240): 256,
+        (2, 64, 38, 76, 132): 256,
+        (1, 128, 12, 20, 72): 18,
+        (2, 128, 38, 76, 132): 128,
+    },
+    "dca_deconv3d_x3_stats_chunks": {
+        (1, 3, 5, 12): 2,
+        (2, 19, 38, 68): 256,
+        (1, 9, 17, 36): 45,
+    },
+    "dca_conv1_x3_stats_chunks": {
+        (1, 900): 2,
+        (1, 4): 1,
+        (3, 349184): 2046,
+        (3, 349568): 2048,
+        (2, 130948): 512,
+    },
+    "dca_conv3d_wgrad_x2_workspace": {
+        (1, 32, 32, 5, 9, 20): 497664,
+        (2, 32, 32, 18, 32, 64): 7077888,
+        (1, 40, 72, 5, 9, 20): 2985984,
+        (2, 64, 64, 18, 32, 64): 7077888,
+        (1, 512, 544, 3, 5, 20): 7520256,
+    },
+    "dca_conv3d_wgrad_x3_workspace": {
+        (1, 32, 32, 5, 9, 20): 497664,
+        (2, 32, 32, 18, 32, 64): 7077888,
+        (1, 40, 72, 5, 9, 20): 2985984,
+        (2, 64, 64, 18, 32, 64): 7077888,
+        (1, 512, 544, 3, 5, 20): 7520256,
+    },
+    "dca_conv3d_wgrad_s2_x2_workspace": {
+        (1, 32, 64, 6, 10, 24): 331776,
+        (2, 32, 64, 36, 64, 128): 14155776,
+        (1, 40, 72, 6, 10, 24): 995328,
+        (2, 64, 128, 36, 64, 128): 14155776,
+    },
+    "dca_conv3d_wgrad_workspace": {
+        (1, 32, 32, 5, 9, 20, 3, 1): 248832,
+        (2, 32, 32, 18, 32, 64, 3, 1): 7077888,
+        (1, 32, 64, 3, 5, 12, 3, 2): 497664,
+        (1, 32, 32, 5, 9, 20, 1, 1): 4096,
+        (1, 32, 32, 5, 9, 48, 3, 1): 497664,
+        (1, 40, 72, 5, 9, 20, 3, 1): 1492992,
+        (2, 32, 64, 18, 32, 64, 3, 2): 7077888,
+        (2, 64, 32, 18, 32, 64, 1, 1): 524288,
+        (1, 32, 27, 5, 9, 20, 1, 1): 4096,
+        (4, 32, 27, 48, 136, 240, 1, 1): 524288,
+        (1, 512, 544, 3, 5, 20, 3, 1): 7520256,
+    },
+}
+
+
+def test_size_queries_are_pinned():
+    from dcanet_amd import _lib
+    if torch.cuda.is_available() and torch.cuda.get_device_properties(0).multi_processor_count != 256:
+        pytest.skip("the table holds for 256 CUs")
+    lib = _lib.load()
+    got = {name: {args: getattr(lib, name)(*args) for args in cases} for name, cases in SIZE_QUERIES.items()}
+    assert got == SIZE_QUERIES
+
+
 @pytest.mark.parametrize("variant", ["g", "gc"])
 def test_state_dict_matches_reference(variant):
     """tests/golden/state_dict_keys.json was dumped from the reference model (oracle/make_golden.py)."""
