@@ -145,10 +145,9 @@ class _CostVolume(torch.autograd.Function):
         with torch.cuda.device_of(vol):
             _chk(_L().dca_cost_volume_fwd(rp, tp, sc, nseg, _ptr(cref), _ptr(ctgt), Cc, _ptr(vol), B, H, W, maxdisp,
                                           num_groups, code, _ptr(vmax), _stream()), "dca_cost_volume_fwd")
-        _tls.last_vmax = (vmax, B * H)       # the caller tags the tensor it hands out (cost_volume below)
         ctx.save_for_backward(*refs, *tgts)
         ctx.meta = (maxdisp, num_groups, nseg, segC, Cc, (B, H, W))
-        return vol
+        return _tag_cmax(vol, vmax, B * H)   # no read pass in front of dres0's first convolution
 
     @staticmethod
     def backward(ctx, gvol):
@@ -193,12 +192,7 @@ def cost_volume(ref, tgt, maxdisp, num_groups, cref=None, ctgt=None, out_dtype=t
         vol = gwc_volume(r1, t1, maxdisp, num_groups)
         return vol if cref is None else torch.cat((vol, concat_volume(cref, ctgt, maxdisp)), 1)
     extra = () if cref is None else (cref, ctgt)
-    vol = _CostVolume.apply(int(maxdisp), int(num_groups), out_dtype, len(refs), cref is not None, *refs, *tgts, *extra)
-    vmax, nslots = getattr(_tls, "last_vmax", (None, 0))
-    _tls.last_vmax = (None, 0)
-    if vmax is not None:
-        _tag_cmax(vol, vmax, nslots)         # per-channel maxima from the builder: no read pass in front of dres0's first convolution
-    return vol
+    return _CostVolume.apply(int(maxdisp), int(num_groups), out_dtype, len(refs), cref is not None, *refs, *tgts, *extra)
 
 
 def concat_volume(ref, tgt, maxdisp):
@@ -319,8 +313,12 @@ _X3_MIN_WORKGROUPS = 1
 #                 kernel of the first convolution over t does, on the way).
 #   t._dca_px2  = (exps,): t is NOT fp32 data but the packed px2 image of an fp32 tensor of t's shape (the two scaled f16
 #                 terms, [term][C/8][D][H][W][8]), written by a BatchNorm kernel for the f16x2 convolution that consumes it.
-# `version` = t._version at tagging time: an in-place change of t invalidates the tag.  Tensors without a tag get one read
-# pass (dca_cmax_f32).
+#   t._dca_twin = (twin, version): the packed px2 image of the fp32 tensor t, written beside t by its BatchNorm
+#                 (pack_out="both"); it lives exactly as long as t.
+# `version` = t._version at tagging time: an in-place change of t invalidates the tag (_tag_ok is the one statement of that
+# rule).  Tags are attached by the autograd Function that launches the producing kernel, inside its forward / backward -- an
+# attribute set on an output there is still on what apply() returns -- and only through the four _tag_* setters.  Tensors
+# without a tag get one read pass (dca_cmax_f32).
 AMAX_STATS = {"tagged": 0, "computed": 0, "packed": 0}
 CSLOTS = 1024                                              # DCA_AMAX_CSLOTS of include/dca_hip.h
 AMAX_EMIT = os.environ.get("DCA_AMAX_EMIT", "1") != "0"    # 0: no producer-side maxima, every operand gets its read pass (A/B)
@@ -351,12 +349,31 @@ def _tag_px2(t, exps):
     return t
 
 
+def _tag_exps(t, exps):
+    t._dca_exps = (exps, _ver(t))
+
+
+def _tag_twin(t, twin):
+    t._dca_twin = (twin, _ver(t))
+
+
+def _tag_ok(t, name):
+    """the versioned tag `name` of t if it is valid -- stamped with t's current version, payload on t's device -- else None"""
+    tag = getattr(t, name, None)
+    if tag is not None and tag[-1] == _ver(t) and tag[0].device == t.device:
+        return tag
+    return None
+
+
 def _copy_tags(src, dst):
-    """the operand tags of src on dst, a view of the same values (the alias output of _Conv3d)"""
-    for k in ("_dca_cmax", "_dca_exps", "_dca_twin"):
-        v = getattr(src, k, None)
-        if v is not None:
-            setattr(dst, k, v[:-1] + (_ver(dst),))
+    """the valid operand tags of src on dst, a view of the same values (the alias output of _Conv3d)"""
+    cmax, exps, twin = _tag_ok(src, "_dca_cmax"), _tag_ok(src, "_dca_exps"), _tag_ok(src, "_dca_twin")
+    if cmax is not None:
+        _tag_cmax(dst, cmax[0], cmax[1])
+    if exps is not None:
+        _tag_exps(dst, exps[0])
+    if twin is not None:
+        _tag_twin(dst, twin[0])
 
 
 def _is_packed(t):
@@ -365,16 +382,14 @@ def _is_packed(t):
 
 def _twin_of(t):
     """the packed px2 twin of the fp32 tensor t (written together with t by the BatchNorm apply pass), or None"""
-    tw = getattr(t, "_dca_twin", None)
-    if tw is not None and tw[0] is not None and tw[1] == _ver(t) and tw[0].device == t.device:
-        return tw[0]
-    return None
+    tag = _tag_ok(t, "_dca_twin")
+    return None if tag is None else tag[0]
 
 
 def _slots_of(t):
     """(slots, nslots) of the fp32 tensor t (N, C, ...): the producer's if t carries valid ones, else one read pass"""
-    tag = getattr(t, "_dca_cmax", None)
-    if tag is not None and tag[2] == _ver(t) and tag[0].device == t.device:
+    tag = _tag_ok(t, "_dca_cmax")
+    if tag is not None:
         AMAX_STATS["tagged"] += 1
         return tag[0], tag[1]
     AMAX_STATS["computed"] += 1
@@ -384,17 +399,15 @@ def _slots_of(t):
     lib = _L()
     _chk(lib.dca_cmax_f32(_ptr(t), N, C, S, _ptr(slots), _stream()), "dca_cmax_f32")
     nslots = lib.dca_bn_num_chunks(C, S)
-    t._dca_cmax = (slots, nslots, _ver(t))
+    _tag_cmax(t, slots, nslots)
     return slots, nslots
 
 
 def _exps_cached(t):
     if _is_packed(t):
         return t._dca_px2[0]
-    tag = getattr(t, "_dca_exps", None)
-    if tag is not None and tag[1] == _ver(t) and tag[0].device == t.device:
-        return tag[0]
-    return None
+    tag = _tag_ok(t, "_dca_exps")
+    return None if tag is None else tag[0]
 
 
 def _exps_of(t):
@@ -406,7 +419,7 @@ def _exps_of(t):
     C = t.shape[1]
     ex = torch.empty((C,), device=t.device, dtype=torch.int32)
     _chk(_L().dca_cmax_exps(_ptr(slots), nslots, C, _ptr(ex), _stream()), "dca_cmax_exps")
-    t._dca_exps = (ex, _ver(t))
+    _tag_exps(t, ex)
     return ex
 
 
@@ -511,7 +524,7 @@ def _x2_weights(prefix, x, w_src, A, B, src_ab, flip, cached_key):
     _chk(getattr(lib, prefix + "_prep_weight")(_ptr(w_src), _ptr(wx), A, B, int(src_ab), int(flip), _ptr(slots), nslots,
                                                _ptr(xexps), _stream()), prefix + "_prep_weight")
     if slots is not None:
-        x._dca_exps = (xexps, _ver(x))
+        _tag_exps(x, xexps)
     return wx, xexps
 
 
@@ -783,24 +796,17 @@ class _Conv3d(torch.autograd.Function):
         ctx.x_twin = xt
         xin = x if xt is None else xt
         with torch.cuda.device_of(x):
-            if not want_stats:
-                y = _conv_forward_impl(xin, x2, weight, stride, transposed)
-                ctx.x_exps = _exps_cached(xin)         # forward and weight gradient scale x by the same exponents
-                if alias:
-                    xa = x.view_as(x)
-                    _copy_tags(x, xa)
-                    return y, xa
-                return y
-            y, part = _conv_forward_impl(xin, x2, weight, stride, transposed, want_stats=True)
-            ctx.x_exps = _exps_cached(xin)
-        if part is None:
-            part = torch.empty((0,), device=x.device, dtype=torch.float64)
-        ctx.mark_non_differentiable(part)
+            out = _conv_forward_impl(xin, x2, weight, stride, transposed, want_stats=want_stats)   # y, or (y, part)
+            ctx.x_exps = _exps_cached(xin)             # forward and weight gradient scale x by the same exponents
+        if want_stats:
+            part = out[1] if out[1] is not None else torch.empty((0,), device=x.device, dtype=torch.float64)
+            ctx.mark_non_differentiable(part)
+            out = (out[0], part)
         if alias:
             xa = x.view_as(x)
             _copy_tags(x, xa)
-            return y, part, xa
-        return y, part
+            out = (out + (xa,)) if want_stats else (out, xa)
+        return out
 
     @staticmethod
     def backward(ctx, dy, *rest):
@@ -809,9 +815,9 @@ class _Conv3d(torch.autograd.Function):
         if ctx.x_twin is not None:
             xw = ctx.x_twin                         # (tagged px2 when it was written)
         elif ctx.x_px2 is not None:
-            x._dca_px2 = ctx.x_px2
+            _tag_px2(x, ctx.x_px2[0])
         elif ctx.x_exps is not None and _exps_cached(x) is None:
-            x._dca_exps = (ctx.x_exps, _ver(x))
+            _tag_exps(x, ctx.x_exps)
         stride, transposed = ctx.meta
         g_alias = _opt(rest[-1], "conv3d.backward") if (ctx.alias and rest) else None
         if dy is None:       # y was not used: nothing flows through the convolution, only past it (alias)
@@ -1009,7 +1015,7 @@ class _BnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, gamma, beta, running_mean, running_var, training, momentum, eps, slope, res_pre, res_post,
                 part=None, zmax=None, pack_z=False, pack_dy=False):
-        """zmax: per-channel slot words that receive max |z| (see _cslots); the caller tags z with them"""
+        """zmax: per-channel slot words that receive max |z| (see _cslots); z is tagged with them here"""
         y = _req(y, "batch_norm")
         res_pre, res_post = _opt(res_pre, "res_pre"), _opt(res_post, "res_post")
         N, C = y.shape[0], y.shape[1]
@@ -1024,23 +1030,22 @@ class _BnAct(torch.autograd.Function):
             stats = bn_stats_vector(y, gamma, beta, running_mean, running_var, training, momentum, eps, part, zexps, rpre, rpost)
             ymax = torch.empty((C * CSLOTS,), device=y.device, dtype=torch.int32) if pack_dy else None
             z = torch.empty_like(y)
-            _tls.last_twin = None
             if pack_z:
                 zp = z if pack_z == 1 else torch.empty_like(y)
                 _chk(lib.dca_bn_apply_pack(_ptr(y), _ptr(stats), _ptr(zexps), _ptr(zp), N, C, S, float(slope), _ptr(ymax),
                                            _ptr(res_pre), _ptr(res_post), _ptr(z) if pack_z == 2 else None,
                                            _ptr(zmax) if pack_z == 2 else None, _stream()), "dca_bn_apply_pack")
                 ymax_slots = lib.dca_bn_pack_chunks(C, S)
+                _tag_px2(zp, zexps)
                 if pack_z == 2:
-                    _tls.last_twin = _tag_px2(zp, zexps)
+                    _tag_twin(z, zp)
             else:
                 _chk(lib.dca_bn_apply(_ptr(y), _ptr(stats), _ptr(res_pre), _ptr(res_post), _ptr(z), N, C, S, float(slope),
                                       _ptr(zmax), _ptr(ymax), _stream()), "dca_bn_apply")
                 ymax_slots = lib.dca_bn_num_chunks(C, S)
         ctx.save_for_backward(y, stats, res_pre if slope != 1.0 else None, ymax)
         ctx.meta = (training, slope, res_pre is not None, res_post is not None, pack_dy, ymax_slots)
-        _tls.last_zexps = zexps       # picked up by bn_act right after apply() (same thread, synchronous)
-        return z
+        return z if pack_z == 1 else _tag_cmax(z, zmax, ymax_slots)    # max |z| sits in as many slots as max |y| would
 
     @staticmethod
     def backward(ctx, dz):
@@ -1230,13 +1235,6 @@ def bn_act(y, bn, slope=1.0, res_pre=None, res_post=None, stats_part=None, pack_
     zm = _cslots(C, y.device) if (CONV_X2 and pack_z != 1) else None    # per-channel max |z|: the next convolution's operand scales
     z = _BnAct.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps, float(slope),
                      res_pre, res_post, stats_part if training else None, zm, pack_z, pack_dy)
-    if pack_z == 1:
-        _tag_px2(z, _tls.last_zexps)
-    elif pack_z == 2:
-        z._dca_twin = (_tls.last_twin, _ver(z))
-        _tag_cmax(z, zm, _L().dca_bn_pack_chunks(C, y[0, 0].numel()))
-    elif zm is not None:
-        _tag_cmax(z, zm, _L().dca_bn_num_chunks(C, y[0, 0].numel()))
     if bn.training and bn.num_batches_tracked is not None:
         pending = getattr(_tls, "pending", None)
         if pending is not None:

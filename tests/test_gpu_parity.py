@@ -813,6 +813,114 @@ def test_packed_training_chain_matches_fp32_chain(both, monkeypatch):
         assert ea <= 2.0 * eb + 2e-6, (i, ea, eb)
 
 
+# ------------------------------------------------------------------------------------- operand tags: attached by the producer
+TAG_SHAPE = (1, 8, 2, 4, 8)     # C % 8 == 0 (the packed forms), 64 values per channel
+
+
+def _tag_setup(monkeypatch, ops):
+    _family(monkeypatch, ops, "f16x2")
+    for flag in ("PACK", "AMAX_EMIT"):
+        monkeypatch.setattr(ops, flag, True)
+
+
+def _slot_max(ops, t):
+    """per-channel maximum over the slots of t's valid _dca_cmax tag, read as float bits, and the tag's slot count"""
+    tag = ops._tag_ok(t, "_dca_cmax")
+    assert tag is not None, "no valid _dca_cmax"
+    slots, nslots, _ = t._dca_cmax
+    return slots.view(torch.float32).view(t.shape[1], ops.CSLOTS)[:, :nslots].amax(1), nslots
+
+
+def test_packed_twin_lives_as_long_as_its_fp32_tensor(monkeypatch):
+    """pack_out="both": the twin rides on z and on nothing else -- dropping z frees it"""
+    import gc
+    import weakref
+    import torch.nn as nn
+    _, ops = _mods()
+    _tag_setup(monkeypatch, ops)
+    bn = nn.BatchNorm3d(8).to(DEV).train()
+    y = seeded_tensor("tag.y", TAG_SHAPE).to(DEV).requires_grad_()
+    z = ops.bn_act(y, bn, 0.0, pack_out="both")
+    tw = ops._twin_of(z)
+    assert tw is not None and ops._is_packed(tw)
+    ref = weakref.ref(tw)
+    del tw
+    assert ref() is not None
+    del z
+    gc.collect()
+    assert ref() is None
+
+
+def test_bn_act_tags_each_output_form(monkeypatch):
+    """the three forms of a training BatchNorm's result carry the tags their readers expect: packed -> its exponents and no
+    maxima; fp32 + twin / fp32 -> per-channel maxima in as many slots as the kernel that wrote them uses, equal to max |z|"""
+    import torch.nn as nn
+    _, ops = _mods()
+    _tag_setup(monkeypatch, ops)
+    bn = nn.BatchNorm3d(8).to(DEV).train()
+    y = seeded_tensor("tag.y", TAG_SHAPE).to(DEV).requires_grad_()
+    lib = ops._L()
+    z = ops.bn_act(y, bn, 0.0, pack_out=True)
+    ex = z._dca_px2[0]
+    assert ex.shape == (8,) and ex.dtype == torch.int32 and not hasattr(z, "_dca_cmax")
+    for pack_out, want_slots in (("both", lib.dca_bn_pack_chunks(8, 64)), (False, lib.dca_bn_num_chunks(8, 64))):
+        z = ops.bn_act(y, bn, 0.0, pack_out=pack_out)
+        assert not ops._is_packed(z)
+        tw = ops._twin_of(z)
+        assert (tw is not None and ops._is_packed(tw) and ops._tag_ok(z, "_dca_twin") is not None) if pack_out else tw is None
+        got, nslots = _slot_max(ops, z)
+        assert nslots == want_slots, (pack_out, nslots, want_slots)
+        assert torch.equal(got, z.detach().abs().amax((0, 2, 3, 4))), pack_out
+
+
+def test_cost_volume_tags_its_result(monkeypatch):
+    """the fused volume builder's fp32 result carries its per-channel maxima (one slot per image row)"""
+    _, ops = _mods()
+    _tag_setup(monkeypatch, ops)
+    fl = seeded_tensor("tag.fl", (1, 320, 4, 8)).to(DEV).requires_grad_()
+    fr = seeded_tensor("tag.fr", (1, 320, 4, 8)).to(DEV).requires_grad_()
+    vol = ops.cost_volume(fl, fr, 8, 40)
+    assert vol.shape == (1, 40, 8, 4, 8)
+    got, nslots = _slot_max(ops, vol)
+    assert nslots == 4
+    assert torch.equal(got, vol.detach().abs().amax((0, 2, 3, 4)))
+
+
+def test_bn_act_packed_results_keep_their_own_exponents_across_threads(monkeypatch):
+    """two threads run packed BatchNorms side by side; the two results differ in scale by 2^6 (gamma), so a result that
+    picked up the other thread's exponents would be off by that factor.  Each unpacks to the fp32 kernel's result of its own
+    input to 2^-21 of the channel's maximum: two f16 terms hold 22 bits of every element (test_px2_pack_roundtrip...), the
+    fp32 arithmetic in front of the split is the same in both kernels up to a rounding."""
+    import threading
+    import torch.nn as nn
+    _, ops = _mods()
+    _tag_setup(monkeypatch, ops)
+    jobs = []
+    for i, gamma in enumerate((1.0, 64.0)):
+        bn = nn.BatchNorm3d(8).to(DEV).train()
+        with torch.no_grad():
+            bn.weight.fill_(gamma)
+            bn.bias.copy_(seeded_tensor(f"tag.thr.b{i}", (8,)).to(DEV) * gamma)
+        y = seeded_tensor(f"tag.thr.y{i}", TAG_SHAPE).to(DEV).requires_grad_()
+        jobs.append((bn, y, ops.bn_act(y, bn, 0.0, pack_out=False).detach(), []))
+    assert jobs[1][2].abs().max() > 16 * jobs[0][2].abs().max()
+
+    def run(bn, y, _ref, out):
+        for _ in range(20):
+            out.append(ops.bn_act(y, bn, 0.0, pack_out=True))
+    threads = [threading.Thread(target=run, args=j) for j in jobs]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    for bn, y, ref, out in jobs:
+        assert len(out) == 20
+        for z in out:
+            assert ops._is_packed(z)
+            err = _chan_err(_unpack_px2(z, z._dca_px2[0]), ref)
+            assert err.max() <= 2.0 ** -21, err.max().item()
+
+
 @pytest.mark.parametrize("fam", ["f16x2", "bf16x3"])
 def test_frozen_weights_cache_is_exact_and_scoped(fam, monkeypatch):
     """ops.frozen_weights(): cached weight re-layouts / BN folds give bit-identical results, are reused inside the

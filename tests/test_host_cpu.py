@@ -309,3 +309,95 @@ def test_kitti_wrapper_host_logic(tmp_path):
     disparity_png(png, disp)
     back = np.asarray(Image.open(png))
     assert back.dtype == np.uint16 and np.array_equal(back, (disp * 256).astype("uint16"))
+
+
+def test_forward_set_attributes_survive_apply():
+    """The operand tags (ops.py, "operand scales of the f16x2 kernels") are Python attributes that an autograd Function sets
+    on its outputs inside forward().  That rests on one torch property: what apply() returns still carries them, with the
+    version counter the tag was stamped with."""
+    import threading
+
+    class Tagging(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            y, aux, xa = x * 2, x + 1, x.view_as(x)
+            ctx.mark_non_differentiable(aux)
+            for i, t in enumerate((y, aux, xa)):
+                t._tag = (i, None if t.is_inference() else t._version)
+            return y, aux, xa
+
+    def check():
+        x = torch.ones(3, requires_grad=True)
+        for i, t in enumerate(Tagging.apply(x)):
+            assert t._tag == (i, None if t.is_inference() else t._version), (i, t._tag, t._version)
+
+    check()
+    assert Tagging.apply(torch.ones(3, requires_grad=True))[0].grad_fn is not None
+    with torch.no_grad():
+        check()
+    with torch.inference_mode():
+        check()
+    errors = []
+
+    def worker():
+        try:
+            check()
+        except BaseException as e:      # noqa: BLE001 -- handed to the main thread
+            errors.append(e)
+    th = threading.Thread(target=worker)
+    th.start()
+    th.join()
+    assert not errors, errors
+
+
+def test_operand_tag_validity():
+    """One validity rule for the versioned tags (ops._tag_ok: stamped with the tensor's current version, payload on its
+    device): each setter's tag is seen, an in-place update ends it, and _copy_tags hands only valid tags to an alias."""
+    import dcanet_amd  # noqa: F401
+    from dcanet_amd import ops
+    shape = (2, 8, 2, 2, 4)
+
+    def tagged():
+        t = torch.ones(shape)
+        slots, exps, twin = torch.zeros(8 * ops.CSLOTS, dtype=torch.int32), torch.zeros(8, dtype=torch.int32), torch.ones(shape)
+        ops._tag_cmax(t, slots, 3)
+        ops._tag_exps(t, exps)
+        ops._tag_twin(t, ops._tag_px2(twin, exps))
+        return t, slots, exps, twin
+
+    def valid(t):
+        return [k for k in ("_dca_cmax", "_dca_exps", "_dca_twin") if ops._tag_ok(t, k) is not None]
+
+    t, slots, exps, twin = tagged()
+    assert valid(t) == ["_dca_cmax", "_dca_exps", "_dca_twin"]
+    assert t._dca_cmax[0] is slots and t._dca_cmax[1] == 3 and t._dca_cmax[2] == ops._ver(t)
+    assert ops._exps_cached(t) is exps and ops._twin_of(t) is twin
+    assert ops._is_packed(twin) and ops._exps_cached(twin) is exps and twin._dca_px2[0] is exps
+    before = dict(ops.AMAX_STATS)
+    assert ops._slots_of(t) == (slots, 3) and ops.AMAX_STATS["tagged"] == before["tagged"] + 1
+    # a valid source: all three travel to the alias, restamped for it; the px2 mark never does
+    ops._tag_px2(t, exps)
+    ta = t.view_as(t)
+    ops._copy_tags(t, ta)
+    assert valid(ta) == ["_dca_cmax", "_dca_exps", "_dca_twin"] and not ops._is_packed(ta)
+    assert ta._dca_cmax[:2] == (slots, 3) and ta._dca_exps[0] is exps and ops._twin_of(ta) is twin
+    # an in-place update ends every versioned tag
+    t.mul_(2)
+    assert valid(t) == [] and ops._twin_of(t) is None
+    del t._dca_px2
+    assert ops._exps_cached(t) is None
+    # ... and a tag that was already stale on the source does not come back to life on an alias (views share the counter)
+    x, _, _, _ = tagged()
+    x.mul_(1000.)
+    xa = x.view_as(x)
+    ops._copy_tags(x, xa)
+    assert x._dca_cmax[2] != ops._ver(x)
+    assert valid(xa) == [] and ops._exps_cached(xa) is None and ops._twin_of(xa) is None
+    assert not any(hasattr(xa, k) for k in ("_dca_cmax", "_dca_exps", "_dca_twin", "_dca_px2"))
+
+
+def test_no_tag_handoff_state():
+    """The operand tags are attached where they are made; no thread-local hand-off from a Function to its wrapper."""
+    src = open(os.path.join(ROOT, "cost-volume-aggregation-in-stereo-matching-revisited_amd", "ops.py")).read()
+    for name in ("last_vmax", "last_twin", "last_zexps"):
+        assert name not in src, name
