@@ -105,6 +105,11 @@ SIGNATURES = {
     "dca_frame_lut": (_i, [_p, _l, _p, _p, _p]),
     "dca_frame_apply": (_i, [_p] * 5 + [_i] * 9 + [_p]),
     "dca_disp_export": (_i, [_p, _p, _p] + [_i] * 5 + [_f, _p]),
+    "dca_train_luma_sum": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
+    "dca_train_tables": (_i, [_p, _l, _p, _f, _f, _p, _p, _p, _p]),
+    "dca_train_patch_colour": (_i, [_p] * 4 + [_i] * 7 + [_p]),
+    "dca_train_crop_norm": (_i, [_p] * 7 + [_i] * 11 + [_p]),
+    "dca_train_disp_crop": (_i, [_p, _i, _p, _p] + [_i] * 7 + [_f, _i, _f, _p]),
 }
 
 _lib = None

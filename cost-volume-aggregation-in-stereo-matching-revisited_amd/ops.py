@@ -7,6 +7,7 @@ There is no CPU / eager fallback: tensors must be fp32 on a ROCm device and the 
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import threading
 from typing import Optional
@@ -1975,3 +1976,114 @@ def disp_export(pred, y0, h, w, scale=256.0, f32=True, u16=False, out_f32=None, 
         _chk(_L().dca_disp_export(_ptr(pred), _ptr(of), _ptr(ou), Hc, Wc, y0, h, w, float(scale), _stream()),
              "dca_disp_export")
     return of, ou
+
+
+# ------------------------------------------------------------------------------------------------
+# Training inputs (dataloader/datasets.py:221-254, 270-317 after the decode): photometric augmentation as one byte table
+# per image, crop, occlusion patch, normalisation, ground-truth crop and mask (csrc/train_io.hip).  No launch synchronises;
+# dcanet_amd.training holds the numpy restatements and the TrainInput / TrainStep classes built on these.
+# ------------------------------------------------------------------------------------------------
+def _req_window(name, H, W, y1, x1, th, tw):
+    y1, x1, th, tw = int(y1), int(x1), int(th), int(tw)
+    if min(y1, x1) < 0 or min(th, tw) <= 0 or y1 + th > H or x1 + tw > W:
+        raise RuntimeError(f"{name}: the {th} x {tw} window at ({y1}, {x1}) does not fit the {H} x {W} source")
+    return y1, x1, th, tw
+
+
+def train_luma_sum(left_u8, right_u8, bg):
+    """Sum of PIL's convert("L") of each image after its byte table bg (2,256) uint8 (gamma o brightness): (2,) int64,
+    S[i] = sum over pixels of (19595 R' + 38470 G' + 7471 B' + 32768) >> 16 with X' = bg[i][X]."""
+    H, W, C = _req_u8_pair(left_u8, right_u8, "train_luma_sum")
+    _req_dev(bg, "train_luma_sum", "bg", torch.uint8, (2, 256))
+    S = torch.empty(2, device=left_u8.device, dtype=torch.int64)
+    with torch.cuda.device_of(left_u8):
+        _chk(_L().dca_train_luma_sum(_ptr(left_u8), _ptr(right_u8), _ptr(bg), _ptr(S), H, W, C, _stream()),
+             "dca_train_luma_sum")
+    return S
+
+
+def train_tables(S, n_pixels, bg, contrast, norm):
+    """S of `train_luma_sum`, the pixel count, bg (2,256) uint8, the two contrast factors and norm (2,3,256) float32 ->
+    (U (2,256) uint8 = contrast o bg, T (2,3,256) float32 = norm o U); training.contrast_table restates the blend."""
+    _req_dev(S, "train_tables", "S", torch.int64, (2,))
+    _req_dev(bg, "train_tables", "bg", torch.uint8, (2, 256))
+    _req_dev(norm, "train_tables", "norm", torch.float32, (2, 3, 256))
+    f0, f1 = float(contrast[0]), float(contrast[1])
+    if not 0 < int(n_pixels) < 1 << 31 or not (math.isfinite(f0) and math.isfinite(f1)):
+        raise RuntimeError("train_tables: 0 < n_pixels < 2^31 and finite contrast factors")
+    U = torch.empty((2, 256), device=S.device, dtype=torch.uint8)
+    T = torch.empty((2, 3, 256), device=S.device, dtype=torch.float32)
+    with torch.cuda.device_of(S):
+        _chk(_L().dca_train_tables(_ptr(S), int(n_pixels), _ptr(bg), f0, f1, _ptr(norm), _ptr(U), _ptr(T), _stream()),
+             "dca_train_tables")
+    return U, T
+
+
+def train_patch_colour(right_u8, U, y1, x1, th, tw):
+    """Per channel floor(mean of U[1][byte]) over the th x tw window at (y1, x1) of the right image: (3,) uint8, the
+    colour of the occlusion patch (datasets.py:306)."""
+    H, W, C = _req_u8_pair(right_u8, right_u8, "train_patch_colour")
+    _req_dev(U, "train_patch_colour", "U", torch.uint8, (2, 256))
+    y1, x1, th, tw = _req_window("train_patch_colour", H, W, y1, x1, th, tw)
+    sums = torch.empty(3, device=U.device, dtype=torch.int64)
+    colour = torch.empty(3, device=U.device, dtype=torch.uint8)
+    with torch.cuda.device_of(U):
+        _chk(_L().dca_train_patch_colour(_ptr(right_u8), _ptr(U), _ptr(sums), _ptr(colour), H, W, C, y1, x1, th, tw,
+                                         _stream()), "dca_train_patch_colour")
+    return colour
+
+
+def train_crop_norm(left_u8, right_u8, T, y1, x1, out_left, out_right, patch=None, norm=None, colour=None):
+    """The th x tw window at (y1, x1) of both (H,W,C) uint8 images through T (2,3,256) into out_left, out_right
+    (3,th,tw) float32 -- contiguous views, e.g. slot b of a (B,3,th,tw) batch.  patch = (r0, r1, c0, c1): rows r0:r1,
+    columns c0:c1 of the RIGHT crop become norm[1][ch][colour[ch]] (norm (2,3,256), colour (3,) uint8 on the device)."""
+    H, W, C = _req_u8_pair(left_u8, right_u8, "train_crop_norm")
+    _req_dev(T, "train_crop_norm", "T", torch.float32, (2, 3, 256))
+    _req_dev(out_left, "train_crop_norm", "out_left", torch.float32)
+    if out_left.dim() != 3 or out_left.shape[0] != 3:
+        raise RuntimeError(f"train_crop_norm: out_left must be (3,th,tw), got {tuple(out_left.shape)}")
+    th, tw = int(out_left.shape[1]), int(out_left.shape[2])
+    _req_dev(out_right, "train_crop_norm", "out_right", torch.float32, (3, th, tw))
+    y1, x1, th, tw = _req_window("train_crop_norm", H, W, y1, x1, th, tw)
+    py0 = px0 = ph = pw = 0
+    if patch is not None:
+        r0, r1, c0, c1 = (int(v) for v in patch)
+        if not (0 <= r0 <= r1 <= th and 0 <= c0 <= c1 <= tw):
+            raise RuntimeError(f"train_crop_norm: the patch rows {r0}:{r1}, columns {c0}:{c1} leave the {th} x {tw} crop")
+        py0, px0, ph, pw = r0, c0, r1 - r0, c1 - c0
+    if ph > 0 and pw > 0:
+        _req_dev(norm, "train_crop_norm", "norm", torch.float32, (2, 3, 256))
+        _req_dev(colour, "train_crop_norm", "colour", torch.uint8, (3,))
+    else:
+        py0 = px0 = ph = pw = 0
+        norm = colour = None
+    with torch.cuda.device_of(left_u8):
+        _chk(_L().dca_train_crop_norm(_ptr(left_u8), _ptr(right_u8), _ptr(T), _ptr(norm), _ptr(colour), _ptr(out_left),
+                                      _ptr(out_right), H, W, C, y1, x1, th, tw, py0, px0, ph, pw, _stream()),
+             "dca_train_crop_norm")
+    return out_left, out_right
+
+
+def train_disp_crop(disp, y1, x1, maxdisp, out_gt, out_mask, flip_rows=False, scale=1.0, inf_to_zero=False):
+    """disp (H,W) float32 or uint16 on the device -> out_gt (th,tw) float32 = the window at (y1, x1) * scale and out_mask
+    (th,tw) bool = gt > 0 & gt < maxdisp (main_dca.py:127).  flip_rows: the source is a bottom-up PFM payload;
+    inf_to_zero: +inf -> 0 (the Middlebury loaders)."""
+    if not isinstance(disp, torch.Tensor) or not disp.is_cuda:
+        raise RuntimeError("train_disp_crop: the disparity must be on the ROCm device; there is no CPU fallback")
+    if disp.dtype not in (torch.float32, torch.uint16) or disp.dim() != 2 or not disp.is_contiguous() or disp.numel() == 0:
+        raise RuntimeError(f"train_disp_crop: expected a contiguous (H,W) float32 or uint16 disparity, got {disp.dtype} "
+                           f"{tuple(disp.shape)}")
+    H, W = int(disp.shape[0]), int(disp.shape[1])
+    if H * W >= 1 << 31:
+        raise RuntimeError("train_disp_crop: H * W must stay below 2^31")
+    _req_dev(out_gt, "train_disp_crop", "out_gt", torch.float32)
+    if out_gt.dim() != 2:
+        raise RuntimeError(f"train_disp_crop: out_gt must be (th,tw), got {tuple(out_gt.shape)}")
+    th, tw = int(out_gt.shape[0]), int(out_gt.shape[1])
+    _req_dev(out_mask, "train_disp_crop", "out_mask", torch.bool, (th, tw))
+    y1, x1, th, tw = _req_window("train_disp_crop", H, W, y1, x1, th, tw)
+    with torch.cuda.device_of(disp):
+        _chk(_L().dca_train_disp_crop(_ptr(disp), int(disp.dtype == torch.uint16), _ptr(out_gt), _ptr(out_mask), H, W, y1, x1,
+                                      th, tw, int(bool(flip_rows)), float(scale), int(bool(inf_to_zero)), float(maxdisp),
+                                      _stream()), "dca_train_disp_crop")
+    return out_gt, out_mask

@@ -493,6 +493,44 @@ int dca_frame_apply(const unsigned char* left, const unsigned char* right, const
 int dca_disp_export(const float* pred, float* out_f32, unsigned short* out_u16, int Hc, int Wc, int y0, int h, int w,
                     float scale, hipStream_t stream);
 
+/* ---- training inputs (train_io.hip): the loaders' arithmetic after the decode (dataloader/datasets.py:221-254 SceneFlow,
+ * :270-317 KITTI) -- photometric augmentation, crop, occlusion patch, ToTensor + Normalize, ground-truth crop and mask.
+ * Brightness, gamma and contrast each map a byte to a byte, so an image needs ONE 256-entry table; only the contrast
+ * mean depends on the pixels, and it comes from an exact integer sum.  Integer atomics only: bitwise reproducible.  No
+ * host value is needed between the launches: each reads what the one before left in device memory.
+ *
+ * dca_train_luma_sum: left, right (H,W,C) interleaved uint8, C = 3 or 4, H W < 2^31; bg[2][256] the byte table of each
+ * image (gamma o brightness).  S[i] = sum over pixels of (19595 R' + 38470 G' + 7471 B' + 32768) >> 16, X' = bg[i][X]:
+ * the sum of PIL's convert("L") of the image after brightness and gamma.  S is zeroed by the launcher. */
+int dca_train_luma_sum(const unsigned char* left, const unsigned char* right, const unsigned char* bg, long long* S, int H,
+                       int W, int C, hipStream_t stream);
+/* dca_train_tables: S of dca_train_luma_sum, n = H W, bg, the two contrast factors and a normalisation table
+ * norm[2][3][256] -> U[2][256] bytes, U[i][v] = C_i[bg[i][v]], and T[2][3][256] fp32, T[i][ch][v] = norm[i][ch][U[i][v]].
+ * mean_i = int(double(S_i) / double(n) + 0.5);  C_i[v] = blend(mean_i, v, f_i) as PIL's Blend.c: in fp32 without fused
+ * multiply-add t = c + f * (v - c); for 0 <= f <= 1 the result is t truncated, otherwise 0 for t <= 0, 255 for t >= 255
+ * and truncation in between.  Factors that are not finite are refused. */
+int dca_train_tables(const long long* S, long n_pixels, const unsigned char* bg, float f_left, float f_right,
+                     const float* norm, unsigned char* U, float* T, hipStream_t stream);
+/* dca_train_patch_colour: colour[ch] = floor(sum of U[1][byte] over the th x tw window at (y1, x1) of the right image,
+ * channel ch, / (th tw)), 3 bytes: `np.mean(np.mean(right_img, 0), 0)` assigned into a uint8 array (datasets.py:306).
+ * sums: 3 64-bit integers of workspace. */
+int dca_train_patch_colour(const unsigned char* right, const unsigned char* U, long long* sums, unsigned char* colour,
+                           int H, int W, int C, int y1, int x1, int th, int tw, hipStream_t stream);
+/* dca_train_crop_norm: the th x tw window at (y1, x1) of both images, looked up in T[2][3][256] (dca_train_tables', or a
+ * fixed table: the SceneFlow loader), written to the planar fp32 slots out_left, out_right (3,th,tw) -- slot b of a
+ * (B,3,th,tw) batch.  With ph, pw > 0 the rows [py0, py0 + ph) x columns [px0, px0 + pw) of the RIGHT crop are
+ * norm[1][ch][colour[ch]] instead; the rectangle must lie inside the crop.  norm and colour may be NULL without a patch.
+ * 16-byte stores when tw % 4 == 0 and both slots are 16-byte aligned, 4-byte stores otherwise. */
+int dca_train_crop_norm(const unsigned char* left, const unsigned char* right, const float* T, const float* norm,
+                        const unsigned char* colour, float* out_left, float* out_right, int H, int W, int C, int y1, int x1,
+                        int th, int tw, int py0, int px0, int ph, int pw, hipStream_t stream);
+/* dca_train_disp_crop: src (H,W) fp32 (src_u16 = 0) or uint16 (src_u16 = 1) -> gt (th,tw) fp32 = the window at (y1, x1)
+ * times scale (1, or 1/256 for KITTI PNGs: exact; scale 1 copies the bits) and mask (th,tw) bytes = gt > 0 && gt < maxdisp
+ * (main_dca.py:127; NaN gives 0).  flip_rows: the source is stored bottom-up (a PFM payload) and (y1, x1) addresses the
+ * flipped image.  inf_to_zero: +inf becomes 0 (the Middlebury loaders). */
+int dca_train_disp_crop(const void* src, int src_u16, float* gt, unsigned char* mask, int H, int W, int y1, int x1, int th,
+                        int tw, int flip_rows, float scale, int inf_to_zero, float maxdisp, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
