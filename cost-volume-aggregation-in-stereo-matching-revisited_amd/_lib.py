@@ -110,6 +110,9 @@ SIGNATURES = {
     "dca_train_patch_colour": (_i, [_p] * 4 + [_i] * 7 + [_p]),
     "dca_train_crop_norm": (_i, [_p] * 7 + [_i] * 11 + [_p]),
     "dca_train_disp_crop": (_i, [_p, _i, _p, _p] + [_i] * 7 + [_f, _i, _f, _p]),
+    "dca_softargmin_stats": (_i, [_p, _p, _i, _i, _l, _i, _p]),
+    "dca_convex_up4_planes": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "dca_conf_histogram": (_i, [_p, _p, _p, _p, _i, _l, _i, _f, _p]),
 }
 
 _lib = None

@@ -16,20 +16,12 @@
 //    (order-fixed reduction, no atomics).  The estimate handed in by GwcNet is already a
 //    softmax output and is log_softmax-ed again -- reproduced, not fixed.
 #include "dca_common.h"
+#include "dca_softmax.h"
 #include "../../include/dca_hip.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ convex up-sampling
-__device__ __forceinline__ void load_nb(const float* __restrict__ d, int h, int w, int y, int x, float (&nb)[9]) {
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
-    const bool ok = (unsigned)yy < (unsigned)h && (unsigned)xx < (unsigned)w;
-    nb[k] = ok ? 4.f * d[(long)yy * w + xx] : 0.f;     // F.unfold zero padding of 4*disp
-  }
-}
-
 __global__ __launch_bounds__(256) void convex_up4_fwd_kernel(const float* __restrict__ logits,
                                                              const float* __restrict__ disp, float* __restrict__ up,
                                                              int h, int w) {
@@ -37,7 +29,7 @@ __global__ __launch_bounds__(256) void convex_up4_fwd_kernel(const float* __rest
   if (cell >= hw) return;
   const int y = cell / w, x = cell - y * w;
   float nb[9];
-  load_nb(disp + (long)b * hw, h, w, y, x, nb);
+  convex_load_nb(disp + (long)b * hw, h, w, y, x, 4.f, nb);     // F.unfold zero padding of 4*disp
   const float* lg = logits + (long)b * 144 * hw + cell;
   float* o = up + (long)b * 16 * hw + (long)(4 * y) * (4 * w) + 4 * x;
 #pragma unroll
@@ -45,19 +37,10 @@ __global__ __launch_bounds__(256) void convex_up4_fwd_kernel(const float* __rest
     float r[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float v[9], m = -INFINITY;
+      float e[9], acc = 0.f;
+      const float s = convex_weights(lg, hw, i * 4 + j, e);
 #pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        v[k] = lg[(long)(k * 16 + i * 4 + j) * hw];
-        m = fmaxf(m, v[k]);
-      }
-      float s = 0.f, acc = 0.f;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        const float e = expf(v[k] - m);
-        s += e;
-        acc += e * nb[k];
-      }
+      for (int k = 0; k < 9; ++k) acc += e[k] * nb[k];
       r[j] = acc / s;
     }
     *(float4*)(o + (long)i * (4 * w)) = make_float4(r[0], r[1], r[2], r[3]);
@@ -74,7 +57,7 @@ __global__ __launch_bounds__(256) void convex_up4_bwd_kernel(const float* __rest
   if (cell >= hw) return;
   const int y = cell / w, x = cell - y * w;
   float nb[9], wsum[9];
-  load_nb(disp + (long)b * hw, h, w, y, x, nb);
+  convex_load_nb(disp + (long)b * hw, h, w, y, x, 4.f, nb);     // F.unfold zero padding of 4*disp
 #pragma unroll
   for (int k = 0; k < 9; ++k) wsum[k] = 0.f;
   const float* lg = logits + (long)b * 144 * hw + cell;
@@ -86,19 +69,10 @@ __global__ __launch_bounds__(256) void convex_up4_bwd_kernel(const float* __rest
     const float gs[4] = {g4.x, g4.y, g4.z, g4.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float v[9], m = -INFINITY;
+      float v[9], acc = 0.f;
+      const float s = convex_weights(lg, hw, i * 4 + j, v);
 #pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        v[k] = lg[(long)(k * 16 + i * 4 + j) * hw];
-        m = fmaxf(m, v[k]);
-      }
-      float s = 0.f, acc = 0.f;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        v[k] = expf(v[k] - m);
-        s += v[k];
-        acc += v[k] * nb[k];
-      }
+      for (int k = 0; k < 9; ++k) acc += v[k] * nb[k];
       const float inv = 1.f / s, upv = acc * inv;
 #pragma unroll
       for (int k = 0; k < 9; ++k) {

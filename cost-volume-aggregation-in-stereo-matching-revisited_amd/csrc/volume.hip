@@ -10,6 +10,7 @@
 // as 16-byte-per-lane coalesced stores (the volume write is the HBM-bound part: 40*D*H*W floats).
 // The zero half-plane x < i is produced by the same kernel (no memset pass).
 #include "dca_common.h"
+#include "dca_softmax.h"
 #include "../../include/dca_hip.h"
 
 template <int CPG>
@@ -349,14 +350,8 @@ __global__ void softargmin_fwd_kernel(const float* __restrict__ x, float* __rest
       out[idx] = s;
       continue;
     }
-    float m = -INFINITY;
-    for (int k = 0; k < K; ++k) m = fmaxf(m, xp[k * HW]);
-    float s = 0.f, sk = 0.f;
-    for (int k = 0; k < K; ++k) {
-      const float e = expf(xp[k * HW] - m);
-      s += e;
-      sk += e * (float)k;
-    }
+    float m, s, sk;
+    softmax_moments(xp, K, HW, m, s, sk);
     if (mode == 1) {
       out[idx] = sk / s;
     } else {

@@ -142,6 +142,63 @@ def all_reduce_state(state, group=None):
     return state
 
 
+def risk_coverage(state):
+    """Host arithmetic of `ConfidenceCurve.result()`: state (nbins,3) int64 of ops.conf_histogram -- per confidence bin
+    the pixel count, the sum of |pred - gt| in units of 2^-20 pixels and the count of |pred - gt| > 3 -- -> dict with
+      counts                 (nbins,) int64, the pixels per bin
+      threshold, coverage, epe, bad3    one entry per NON-EMPTY bin, from the most confident bin downwards: keeping the
+                             pixels with confidence >= threshold[i] keeps the fraction coverage[i] of all pixels, with mean
+                             error epe[i] and the fraction bad3[i] of errors > 3; coverage ends at 1 and epe[-1] is the
+                             EPE over all pixels
+      aurc_epe               the trapezoid area under epe over coverage in [0, 1], the curve held at epe[0] below
+                             coverage[0] (a confidence that says nothing about the error gives the EPE itself; lower is
+                             better)
+      pixels                 the total count.
+    All sums are exact integers until the final divisions.  An empty state gives empty curves and aurc_epe 0."""
+    st = np.asarray(state)
+    assert st.ndim == 2 and st.shape[1] == 3 and st.dtype.kind in "iu", "not a confidence state"
+    st = st.astype(np.int64)
+    nbins = st.shape[0]
+    counts = st[:, 0].copy()
+    keep = np.nonzero(counts[::-1])[0]                      # descending confidence, empty bins left out
+    desc = st[::-1][keep]
+    n, err, bad = (np.cumsum(desc[:, k]) for k in range(3))
+    total = int(counts.sum())
+    nf = n.astype(np.float64)
+    coverage = nf / float(total) if total else nf
+    epe = err.astype(np.float64) / float(ops.CONF_ERR_SCALE) / nf
+    bad3 = bad.astype(np.float64) / nf
+    aurc = 0.0
+    if total:
+        c, e = np.concatenate([[0.0], coverage]), np.concatenate([epe[:1], epe])
+        aurc = float(((c[1:] - c[:-1]) * (e[1:] + e[:-1])).sum() * 0.5)
+    return {"counts": counts, "threshold": (nbins - 1 - keep).astype(np.float64) / nbins, "coverage": coverage, "epe": epe,
+            "bad3": bad3, "aurc_epe": aurc, "pixels": total}
+
+
+class ConfidenceCurve:
+    """Scores a confidence map against the ground truth over a run: `cc = ConfidenceCurve(); for frame:
+    cc.add(conf, pred, gt); print(cc.result()["aurc_epe"])`.  `add` is one launch (ops.conf_histogram) into an int64
+    state on the device and reads nothing back; `result()` reads the state once (`risk_coverage`).  Pixels with
+    0 < gt < maxdisp count; conf, pred, gt: float32 tensors of one shape on the device.  Bitwise reproducible.
+    Across ranks: `all_reduce_state(cc.state)` accepts this state unchanged (every entry is an integer sum)."""
+
+    def __init__(self, nbins=64, maxdisp=192, device="cuda"):
+        if not 2 <= int(nbins) <= ops.CONF_MAX_BINS:
+            raise ValueError(f"2 <= nbins <= {ops.CONF_MAX_BINS}")
+        self.maxdisp = maxdisp
+        self.state = torch.zeros((int(nbins), 3), device=device, dtype=torch.int64)
+
+    def reset(self):
+        self.state.zero_()
+
+    def add(self, conf, pred, gt):
+        ops.conf_histogram(conf, pred, gt, self.state, self.maxdisp)
+
+    def result(self):
+        return risk_coverage(self.state.cpu().numpy())
+
+
 class _HotPathWithConfusion:
     """`hot_path`-shaped callable for GraphedHotPath: the hot path with its three region volumes, then
     dca_region_confusion against the ground truth, so that one hipGraph holds both."""

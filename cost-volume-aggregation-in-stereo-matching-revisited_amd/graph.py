@@ -15,9 +15,10 @@ class GraphedHotPath:
     the same shapes to replay.  Returns the dict of outputs (static buffers: clone them if they must outlive the
     next call)."""
 
-    def __init__(self, model, *example_inputs, warmup: int = 2):
+    def __init__(self, model, *example_inputs, warmup: int = 2, **hot_path_kwargs):
         """example_inputs: the arguments of `model.hot_path` -- tensors, or tuples of tensors (the extractor's l2 / l3 /
-        l4 segments), or None"""
+        l4 segments), or None.  hot_path_kwargs: keywords handed to every `model.hot_path` call as they are (e.g.
+        confidence=1); they are part of what is captured."""
         assert not model.training, "graph capture is for the eval path (training BN updates buffers)"
         self.model = model
         self.static_in = [_tree(t, lambda u: u.detach().clone()) for t in example_inputs]
@@ -25,11 +26,11 @@ class GraphedHotPath:
         stream.wait_stream(torch.cuda.current_stream())
         with torch.no_grad(), torch.cuda.stream(stream):
             for _ in range(warmup):                      # warms hipFuncSetAttribute / allocator state outside capture
-                model.hot_path(*self.static_in)
+                model.hot_path(*self.static_in, **hot_path_kwargs)
         torch.cuda.current_stream().wait_stream(stream)
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.graph):
-            self.static_out = model.hot_path(*self.static_in)
+            self.static_out = model.hot_path(*self.static_in, **hot_path_kwargs)
 
     def __call__(self, *inputs):
         for s, t in zip(self.static_in, inputs):

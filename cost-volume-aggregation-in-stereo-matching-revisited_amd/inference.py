@@ -8,7 +8,11 @@ The reference's script calls `.squeeze()` on the model's return value although e
 
 `KittiInference(..., device_io=True)` moves the arithmetic around the model call to the GPU (csrc/frame_io.hip): the
 uint8 pair is uploaded as it is, normalised through a histogram-built table, placed in the frame, and the cropped
-float32 / uint16 disparity is read back -- two copies are all that is left on the host."""
+float32 / uint16 disparity is read back -- two copies are all that is left on the host.
+
+`KittiInferenceWithConfidence` returns a confidence map next to every disparity map: the probability mass of the final
+disparity distribution within `radius` bins of its peak, up-sampled with the disparity in one launch (DESIGN.md section
+6e; nothing in the reference computes it)."""
 from __future__ import annotations
 
 import collections
@@ -111,7 +115,7 @@ class _Slot:
         self.device = device
         self.in_pin = self.in_dev = None
         self.out_len = crop_height * crop_width
-        self.out = {}                # dtype -> (device, pinned)
+        self.out = {}                # (dtype, maps) -> (device, pinned)
         self.uploaded, self.computed, self.done = (torch.cuda.Event() for _ in range(3))
         self.meta = None             # (h, w, c, placement, offset of the right image) of the frame in the slot
         self.as_uint16 = False
@@ -125,12 +129,14 @@ class _Slot:
             self.in_dev = torch.empty(off + nbytes, device=self.device, dtype=torch.uint8)
         return off
 
-    def output(self, as_uint16):
+    def output(self, as_uint16, nmaps=1):
+        """(device, pinned) buffers with room for `nmaps` maps (disparity[, confidence]); the maps of a frame lie back to
+        back, map k of a rows x cols window at [k * rows * cols, (k + 1) * rows * cols)"""
         dtype = torch.uint16 if as_uint16 else torch.float32
-        if dtype not in self.out:
-            self.out[dtype] = (torch.empty(self.out_len, device=self.device, dtype=dtype),
-                               torch.empty(self.out_len, dtype=dtype).pin_memory())
-        return self.out[dtype]
+        if (dtype, nmaps) not in self.out:
+            self.out[dtype, nmaps] = (torch.empty(nmaps * self.out_len, device=self.device, dtype=dtype),
+                                      torch.empty(nmaps * self.out_len, dtype=dtype).pin_memory())
+        return self.out[dtype, nmaps]
 
 
 class KittiInference:
@@ -141,7 +147,13 @@ class KittiInference:
     3 x cva -> classif3 -> soft-argmin) is captured once for the fixed frame size and replayed (`graph=False`: eager).
 
     `device_io=True`: normalisation, padding, crop and the uint16 conversion run as HIP kernels; the host only copies the
-    uint8 pair into pinned memory and the result out of it.  `stream(pairs)` pipelines successive frames."""
+    uint8 pair into pinned memory and the result out of it.  `stream(pairs)` pipelines successive frames.
+
+    The subclass `KittiInferenceWithConfidence` hands out `(disp, conf)` per frame (class attribute `confidence`)."""
+
+    confidence = False           # True: a confidence map next to every disparity map (KittiInferenceWithConfidence)
+    radius = 1                   # its window, in 1/4-res disparity bins either side of the peak
+    CONF_U16_SCALE = 65535.0
 
     def __init__(self, model, crop_height: int = 384, crop_width: int = 1248, graph: bool = True, dtype=None,
                  device_io: bool = False):
@@ -159,8 +171,9 @@ class KittiInference:
         self.net.eval()
 
     @torch.no_grad()
-    def forward_frame(self, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
-        """(1,3,Hc,Wc) x2 on the GPU -> full-resolution disparity (1,1,Hc,Wc); = GwcNet.forward(...)[0] in eval mode"""
+    def forward_frame(self, left: torch.Tensor, right: torch.Tensor):
+        """(1,3,Hc,Wc) x2 on the GPU -> full-resolution disparity (1,1,Hc,Wc); = GwcNet.forward(...)[0] in eval mode.
+        With confidence: (disparity, confidence), both (1,1,Hc,Wc)."""
         net = self.net
         fl, fr = net.feature_extraction(left), net.feature_extraction(right)
         guidance = net.guidance(left)["g"]
@@ -169,15 +182,22 @@ class KittiInference:
             args += [fl["concat_feature"], fr["concat_feature"]]
         import contextlib
         from . import ops
+        kwargs = {"confidence": self.radius} if self.confidence else {}      # the statistics launch is part of the graph
         ctx = ops.reduced_precision(self.dtype) if self.dtype is not None else contextlib.nullcontext()
         with ctx:      # (a replay needs no context: the captured launches are already the reduced-precision kernels)
             if self.graph:
                 if self._graphed is None:
-                    self._graphed = GraphedHotPath(net, *args)
+                    self._graphed = GraphedHotPath(net, *args, **kwargs)
                 r = self._graphed(*args)
             else:
-                r = net.hot_path(*args)
-        return net.prop(guidance, r["pred4_q"])
+                r = net.hot_path(*args, **kwargs)
+        if not self.confidence:
+            return net.prop(guidance, r["pred4_q"])
+        # the leading planes of the statistics as they lie in memory (disparity, unimodal disparity, window mass): one
+        # up-sampling launch for all.  A frame is ONE image: only for B == 1 is this slice contiguous (no gather copy)
+        assert r["stats4_q"].shape[0] == 1
+        up = net.prop.forward_planes(guidance, r["stats4_q"][:, :ops.CONF_MASS + 1], (4.0, 4.0, 1.0))
+        return up[:, ops.CONF_DISP:ops.CONF_DISP + 1], up[:, ops.CONF_MASS:ops.CONF_MASS + 1]
 
     # ---- device I/O: three stages per frame, each enqueued on the stream it is given --------------------------------
     def _slot(self, i):
@@ -222,30 +242,37 @@ class KittiInference:
             lut, _ = ops.frame_lut(ops.frame_histogram(left, right), h * w)
             fl, fr = ops.frame_apply(left, right, lut, (self.crop_height, self.crop_width), src_y0, dst_y0, rows, cols,
                                      out=self._frames)
-            disp = self.forward_frame(fl, fr)
-            out = s.output(as_uint16)[0][:rows * cols].view(rows, cols)
-            if as_uint16:
-                ops.disp_export(disp, dst_y0, rows, cols, f32=False, u16=True, out_u16=out)
-            else:
-                ops.disp_export(disp, dst_y0, rows, cols, out_f32=out)
+            maps = self.forward_frame(fl, fr)
+            maps = maps if self.confidence else (maps,)
+            dev = s.output(as_uint16, len(maps))[0]
+            for k, (m, scale) in enumerate(zip(maps, (256.0, self.CONF_U16_SCALE))):
+                out = dev[k * rows * cols:(k + 1) * rows * cols].view(rows, cols)
+                if as_uint16:
+                    ops.disp_export(m.contiguous(), dst_y0, rows, cols, scale=scale, f32=False, u16=True, out_u16=out)
+                else:
+                    ops.disp_export(m.contiguous(), dst_y0, rows, cols, out_f32=out)
             s.computed.record(compute)
         s.as_uint16 = as_uint16
 
     def _readback(self, s, copy):
         """`copy` stream: device output -> pinned"""
         rows, cols = s.meta[3][2:]
-        dev, pin = s.output(s.as_uint16)
+        nmaps = 2 if self.confidence else 1
+        dev, pin = s.output(s.as_uint16, nmaps)
+        n = nmaps * rows * cols                          # one copy: the disparity, and the confidence behind it
         with torch.cuda.stream(copy):
             copy.wait_event(s.computed)
-            pin[:rows * cols].copy_(dev[:rows * cols], non_blocking=True)
+            pin[:n].copy_(dev[:n], non_blocking=True)
             s.done.record(copy)
 
     def _result(self, s):
         """host: the one synchronisation of a frame, then the result out of the pinned buffer"""
         rows, cols = s.meta[3][2:]
         s.done.synchronize()
-        pin = s.output(s.as_uint16)[1]
-        return pin[:rows * cols].numpy().reshape(rows, cols).copy()
+        nmaps = 2 if self.confidence else 1
+        pin = s.output(s.as_uint16, nmaps)[1]
+        maps = tuple(pin[k * rows * cols:(k + 1) * rows * cols].numpy().reshape(rows, cols).copy() for k in range(nmaps))
+        return maps if self.confidence else maps[0]
 
     def _call_device(self, left_rgb, right_rgb, as_uint16):
         dev = next(self.net.parameters()).device
@@ -258,8 +285,9 @@ class KittiInference:
 
     def stream(self, pairs, depth: int = 2, as_uint16: bool = False):
         """Generator over an iterable of (left_rgb, right_rgb) uint8 pairs (sizes may differ as long as each fits the
-        frame): yields the disparities in input order, `depth` frames in flight.  A copy stream beside the compute
-        stream carries the upload of frame i+1 and the read-back of frame i-1 while frame i computes."""
+        frame): yields the disparities -- with confidence, the (disp, conf) tuples -- in input order, `depth` frames in
+        flight.  A copy stream beside the compute stream carries the upload of frame i+1 and the read-back of frame i-1
+        while frame i computes."""
         if not self.device_io:
             raise RuntimeError("stream() needs KittiInference(..., device_io=True)")
         if depth < 1:
@@ -300,6 +328,38 @@ class KittiInference:
             return self._call_device(left_rgb, right_rgb, as_uint16)
         left, right, h, w = pad_or_crop(normalize_pair(left_rgb, right_rgb), self.crop_height, self.crop_width)
         dev = next(self.net.parameters()).device
-        disp = self.forward_frame(left.to(dev), right.to(dev))
-        disp = crop_back(disp.squeeze().cpu().numpy(), h, w, self.crop_height, self.crop_width)
-        return (disp * 256).astype("uint16") if as_uint16 else disp           # my_img.py:110
+        maps = self.forward_frame(left.to(dev), right.to(dev))
+        if not self.confidence:
+            disp = crop_back(maps.squeeze().cpu().numpy(), h, w, self.crop_height, self.crop_width)
+            return (disp * 256).astype("uint16") if as_uint16 else disp           # my_img.py:110
+        disp, conf = (crop_back(m.squeeze().cpu().numpy(), h, w, self.crop_height, self.crop_width) for m in maps)
+        if as_uint16:      # fp32 products, truncated, as dca_disp_export
+            return (disp * 256).astype("uint16"), (conf * np.float32(self.CONF_U16_SCALE)).astype("uint16")
+        return disp, conf
+
+
+class KittiInferenceWithConfidence(KittiInference):
+    """`disp, conf = KittiInferenceWithConfidence(model, ..., radius=1)(left_rgb, right_rgb)`: KittiInference with the same
+    arguments (host or device I/O, eager or graph, fp32 or reduced precision) whose `__call__` and `stream()` hand out a
+    `(disp, conf)` tuple per frame.  `conf` is the probability mass of the final disparity distribution within `radius`
+    1/4-res bins of its peak (GwcNet.predict's `confidence`), cropped by the same window as the disparity: float32 in
+    [0,1], or uint16(conf * 65535) with as_uint16 (dca_disp_export with scale 65535).  The statistics launch is part of
+    the captured hot path; with device I/O both maps come back in one copy and one synchronisation per frame.  The
+    disparity is bitwise KittiInference's."""
+
+    confidence = True
+
+    def __init__(self, model, *args, radius: int = 1, **kwargs):
+        super().__init__(model, *args, **kwargs)
+        if int(radius) < 0:
+            raise ValueError("radius >= 0")
+        self.radius = int(radius)
+
+
+def confidence_png(path: str, conf: np.ndarray) -> None:
+    """16-bit PNG of a confidence map: uint16(conf * 65535) for float input (as `as_uint16=True` gives it), 65535 = certain."""
+    from PIL import Image
+    conf = np.asarray(conf)
+    if conf.dtype != np.uint16:
+        conf = (conf.astype(np.float32) * np.float32(KittiInference.CONF_U16_SCALE)).astype("uint16")
+    Image.fromarray(conf).save(path, format="PNG")

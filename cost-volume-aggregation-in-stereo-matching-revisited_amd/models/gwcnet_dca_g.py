@@ -135,17 +135,22 @@ class GwcNet(nn.Module):
                 m.bias.data.zero_()
 
     # ---- the hot path proper: 1/4-res features -> 1/4-res disparity (+ training heads)
-    def hot_path(self, gwc_left, gwc_right, concat_left=None, concat_right=None, aux_volumes=False):
+    def hot_path(self, gwc_left, gwc_right, concat_left=None, concat_right=None, aux_volumes=False, confidence=None):
         with ops.batched_bn_counters():   # one multi-tensor add for all BatchNorm step counters
-            return self._hot_path(gwc_left, gwc_right, concat_left, concat_right, aux_volumes)
+            return self._hot_path(gwc_left, gwc_right, concat_left, concat_right, aux_volumes, confidence)
 
-    def _hot_path(self, gwc_left, gwc_right, concat_left=None, concat_right=None, aux_volumes=False):
+    def _hot_path(self, gwc_left, gwc_right, concat_left=None, concat_right=None, aux_volumes=False, confidence=None):
         """reference gwcnet_dca_g.py:216-239 (+ :244-275 when training).  Returns a dict with `pred4_q`
         (B,1,H/4,W/4) in 1/4-res pixels, `prob_volume2` and, in training mode, the auxiliary heads.  `aux_volumes`
         adds `prob_volume1` and `prob_volume3` (fp32, also under ops.reduced_precision): the three region heads the
-        reference's evaluation step scores (main_dca.py:211-213)."""
+        reference's evaluation step scores (main_dca.py:211-213).  `confidence` = a window radius (int; inference only)
+        adds `stats4_q` (B,5,H/4,W/4), the statistics of the final disparity distribution (ops.softargmin_stats), whose
+        plane 0 then IS `pred4_q` (a view; bitwise the soft-argmin): one launch in place of the soft-argmin's."""
         d = self.maxdisp // 4
         lp = ops._lp_dtype()
+        if confidence is not None and (self.training or torch.is_grad_enabled()):
+            raise RuntimeError("hot_path(confidence=radius) is inference only: call the model in eval mode under "
+                               "torch.no_grad()")
         if lp is not None and (self.training or torch.is_grad_enabled()):
             raise RuntimeError("ops.reduced_precision is inference only: call the model in eval mode under torch.no_grad()")
         # gwc (+ concat) volume in ONE tensor, from the extractor's l2/l3/l4 maps in place when they are handed over as
@@ -170,7 +175,11 @@ class GwcNet(nn.Module):
             logits2, out2 = self.classif2(out2, alias=True)
         prob_volume3, out3 = self.cva3(out2)
         logits3 = self.classif3(out3).squeeze(1)
-        res = {"pred4_q": ops.softargmin(logits3), "prob_volume2": prob_volume2}
+        if confidence is None:
+            res = {"pred4_q": ops.softargmin(logits3), "prob_volume2": prob_volume2}
+        else:
+            stats = ops.softargmin_stats(logits3, confidence)
+            res = {"pred4_q": stats[:, ops.CONF_DISP:ops.CONF_DISP + 1], "prob_volume2": prob_volume2, "stats4_q": stats}
         if aux_volumes:
             res["prob_volume1"], res["prob_volume3"] = prob_volume1, prob_volume3
         if self.training:
@@ -192,6 +201,35 @@ class GwcNet(nn.Module):
         if self.training:
             return [r["pred0"], r["pred_dca1"], r["pred_dca2"], r["pred1"], r["pred2"]], [r["pred_dca3"], pred4]
         return pred4, r["prob_volume2"].squeeze(1)
+
+    # planes of `stats4_q` that `predict` up-samples, with their scale: disparities and their spread are in 1/4-res pixels
+    # (x 4, as PropgationNet_4x scales the disparity), probabilities and the entropy are not
+    PREDICT_PLANES = (("disp", ops.CONF_DISP, 4.0), ("disp_unimodal", ops.CONF_DUNI, 4.0), ("confidence", ops.CONF_MASS, 1.0),
+                      ("entropy", ops.CONF_ENT, 1.0), ("std", ops.CONF_STD, 4.0))
+
+    @torch.no_grad()
+    def predict(self, left, right, radius=1):
+        """Inference with per-pixel confidence (no counterpart in the reference): eval mode, no grad.  Returns full-
+        resolution (B,1,H,W) maps: `disp` (bitwise `forward(left, right)[0]`), `disp_unimodal` (the soft-argmin over the
+        bins within `radius` of the most likely one: no averaging over two peaks at a depth edge), `confidence` (the
+        probability mass of that window, in [0,1]), `entropy` (of the whole distribution, normalised to [0,1]) and `std`
+        (its standard deviation in pixels).  All five go through the convex up-sampler in one launch; like the disparity,
+        every map falls towards 0 in the 4-pixel cells along the frame border (zero padding of the 3x3 neighbourhood)."""
+        was_training = self.training
+        self.eval()
+        try:
+            features_left = self.feature_extraction(left)
+            features_right = self.feature_extraction(right)
+            guidance = self.guidance(left)
+            r = self.hot_path(features_left["gwc_segments"], features_right["gwc_segments"],
+                              features_left.get("concat_feature"), features_right.get("concat_feature"),
+                              confidence=int(radius))
+            names, planes, scales = zip(*self.PREDICT_PLANES)
+            assert planes == tuple(range(ops.CONF_PLANES))         # stats4_q as it is: no gather
+            up = self.prop.forward_planes(guidance["g"], r["stats4_q"], scales)
+            return {name: up[:, i:i + 1] for i, name in enumerate(names)}
+        finally:
+            self.train(was_training)
 
 
 def __getattr__(name):

@@ -195,3 +195,8 @@ class PropgationNet_4x(nn.Module):
     def forward(self, guidance, disp):
         # unfold(4*disp) . softmax_9(mask) . sum . pixel-shuffle as one HIP kernel (csrc/heads2d.hip)
         return ops.convex_upsample4(self.conv(guidance), disp)
+
+    def forward_planes(self, guidance, planes, scales):
+        """Inference only: the mask conv once, then P <= 8 planes (B,P,h,w) -> (B,P,4h,4w) through one read of the mask,
+        plane p scaled by scales[p]; a plane with scale 4 is bitwise `forward` of that plane."""
+        return ops.convex_upsample4_planes(self.conv(guidance), planes, scales)

@@ -244,6 +244,33 @@ def regression(x):
     return _SoftArgmin.apply(x, 2)
 
 
+CONF_DISP, CONF_DUNI, CONF_MASS, CONF_ENT, CONF_STD, CONF_PLANES = 0, 1, 2, 3, 4, 5     # DCA_CONF_* of include/dca_hip.h
+
+
+def _req_no_grad(name, *tensors):
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
+        raise RuntimeError(f"{name} is inference only (no backward): call it under torch.no_grad() or detach its inputs")
+
+
+def softargmin_stats(logits, radius=1):
+    """(B,K,*spatial) logits -> (B,5,*spatial): per pixel the soft-argmin (plane CONF_DISP, bitwise `softargmin`), the
+    soft-argmin (CONF_DUNI) and the probability mass (CONF_MASS) of the window |k - argmax| <= radius, the entropy
+    normalised by log K (CONF_ENT) and the standard deviation (CONF_STD) of the soft-max distribution over dim 1
+    (definitions: include/dca_hip.h).  radius >= K means the whole range.  Inference only."""
+    _req_no_grad("softargmin_stats", logits)
+    x = _req(logits, "softargmin_stats")
+    radius = int(radius)
+    if x.dim() < 3 or x.numel() == 0 or radius < 0:
+        raise RuntimeError(f"softargmin_stats: expected non-empty (B,K,*spatial) logits and radius >= 0, got "
+                           f"{tuple(x.shape)} and radius {radius}")
+    B, K = x.shape[0], x.shape[1]
+    HW = x[0, 0].numel()
+    out = torch.empty((B, CONF_PLANES) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
+    with torch.cuda.device_of(x):
+        _chk(_L().dca_softargmin_stats(_ptr(x), _ptr(out), B, K, HW, min(radius, K), _stream()), "dca_softargmin_stats")
+    return out
+
+
 class _UpSoftArgmin(torch.autograd.Function):
     """trilinear x s up-sampling + softmax(dim 1) + disparity regression, fused (gwcnet_dca_g.py:261-264)."""
 
@@ -1549,6 +1576,35 @@ def convex_upsample4(mask_logits, disp):
     return _ConvexUp4.apply(mask_logits, disp)
 
 
+CONF_MAX_PLANES = 8      # DCA_CONF_MAX_PLANES
+
+
+def convex_upsample4_planes(mask_logits, planes, scales):
+    """`convex_upsample4` for P = 1..8 planes through one read of the mask: (B,144,h,w), (B,P,h,w), P floats ->
+    (B,P,4h,4w), plane p = convex combination of scales[p] * planes[:, p] over the 3x3 neighbourhood.  A plane with scale 4
+    is bitwise `convex_upsample4` of that plane.  Neighbours outside the map are 0 for every plane, so any plane falls
+    towards 0 in the cells along the frame border, as the disparity does.  Inference only."""
+    _req_no_grad("convex_upsample4_planes", mask_logits, planes)
+    mask_logits, planes = _req(mask_logits, "convex_upsample4_planes.mask"), _req(planes, "convex_upsample4_planes.planes")
+    scales = [float(v) for v in scales]
+    if mask_logits.dim() != 4 or planes.dim() != 4:
+        raise RuntimeError(f"convex_upsample4_planes: expected mask (B,144,h,w) and planes (B,P,h,w), got "
+                           f"{tuple(mask_logits.shape)} and {tuple(planes.shape)}")
+    B, C, h, w = mask_logits.shape
+    P = planes.shape[1]
+    if C != 144 or tuple(planes.shape) != (B, P, h, w) or not 1 <= P <= CONF_MAX_PLANES or len(scales) != P \
+            or planes.numel() == 0:
+        raise RuntimeError(f"convex_upsample4_planes: expected mask (B,144,h,w), planes (B,P,h,w) with 1 <= P <= "
+                           f"{CONF_MAX_PLANES} and P scales, got {tuple(mask_logits.shape)}, {tuple(planes.shape)} and "
+                           f"{len(scales)} scales")
+    up = torch.empty((B, P, 4 * h, 4 * w), device=planes.device, dtype=torch.float32)
+    sc = (ctypes.c_float * P)(*scales)       # host array, copied into the launch's arguments
+    with torch.cuda.device_of(planes):
+        _chk(_L().dca_convex_up4_planes(_ptr(mask_logits), _ptr(planes), ctypes.cast(sc, _vp), _ptr(up), B, P, h, w,
+                                        _stream()), "dca_convex_up4_planes")
+    return up
+
+
 class _FocalLevels(torch.autograd.Function):
     """sum_l w_l * StereoFocalLoss.loss_per_level(est_l, gt) for estimates of ONE resolution; `gt` is already pooled."""
 
@@ -1876,6 +1932,34 @@ def eval_accumulate(state, rec, cm, gt_shape):
     with torch.cuda.device_of(state):
         _chk(_L().dca_eval_accumulate(_ptr(rec), _ptr(cm), _ptr(state), rec.shape[0], nvol, C, int(gt_shape[-2]),
                                       int(gt_shape[-1]), _stream()), "dca_eval_accumulate")
+    return state
+
+
+CONF_MAX_BINS = 1024         # DCA_CONF_MAX_BINS
+CONF_ERR_SCALE = 1048576     # DCA_CONF_ERR_SCALE: the error sums of `conf_histogram` are in units of 2^-20 pixels
+
+
+def conf_histogram(conf, pred, gt, state, maxdisp):
+    """Adds the pixels of one batch to a risk-coverage state, in place: conf, pred, gt float32 of one shape, state
+    (nbins,3) int64 on the device.  Per confidence bin min(nbins-1, int(clamp(conf,0,1) * nbins)): the count of pixels
+    with 0 < gt < maxdisp and a confidence that is not NaN, the sum of trunc(|pred - gt| * 2^20) and the count of
+    |pred - gt| > 3.  Integer atomics only: bitwise reproducible.  One launch, no synchronisation."""
+    conf, pred, gt = (_req(t, "conf_histogram") for t in (conf, pred, gt))
+    if conf.shape != pred.shape or conf.shape != gt.shape or conf.numel() == 0:
+        raise RuntimeError(f"conf_histogram: conf, pred and gt must have one non-empty shape, got {tuple(conf.shape)}, "
+                           f"{tuple(pred.shape)} and {tuple(gt.shape)}")
+    if not isinstance(state, torch.Tensor) or not state.is_cuda:
+        raise RuntimeError("conf_histogram: the state must be on the ROCm device; there is no CPU fallback")
+    if any(t.device != conf.device for t in (pred, gt, state)):
+        raise RuntimeError(f"conf_histogram: conf, pred, gt and the state must be on one device, got {conf.device}, "
+                           f"{pred.device}, {gt.device} and {state.device}")
+    if state.dtype != torch.int64 or not state.is_contiguous() or state.dim() != 2 or state.shape[1] != 3 \
+            or not 2 <= state.shape[0] <= CONF_MAX_BINS:
+        raise RuntimeError(f"conf_histogram: the state must be a contiguous int64 (nbins,3) tensor, 2 <= nbins <= "
+                           f"{CONF_MAX_BINS}, got {state.dtype} {tuple(state.shape)}")
+    with torch.cuda.device_of(conf):
+        _chk(_L().dca_conf_histogram(_ptr(conf), _ptr(pred), _ptr(gt), _ptr(state), 1, conf.numel(), state.shape[0],
+                                     float(maxdisp), _stream()), "dca_conf_histogram")
     return state
 
 

@@ -531,6 +531,48 @@ int dca_train_crop_norm(const unsigned char* left, const unsigned char* right, c
 int dca_train_disp_crop(const void* src, int src_u16, float* gt, unsigned char* mask, int H, int W, int y1, int x1, int th,
                         int tw, int flip_rows, float scale, int inf_to_zero, float maxdisp, hipStream_t stream);
 
+/* ---- per-pixel confidence from the disparity distribution (confidence.hip); inference only, no backward ------------------
+ * The soft-max over the K = maxdisp/4 disparity bins that the soft-argmin reduces to one number (models/gwcnet_dca_g.py:
+ * `logits3`) holds more: how sharp it is, and where its winning mode lies.  The reference computes none of this.
+ *
+ * dca_softargmin_stats: logits (B,K,HW) fp32 -> out (B,DCA_CONF_PLANES,HW) fp32.  Per pixel, with m = max_k x_k,
+ * k* = the lowest k with x_k == m (taken on the logits: exact), e_k = expf(x_k - m), s = sum_k e_k and the window
+ * Wn = {k : |k - k*| <= radius} clipped to [0, K-1]:
+ *   [DCA_CONF_DISP]  sum_k k e_k / s                  the soft-argmin, bitwise dca_softargmin_fwd's mode 1 (one shared helper)
+ *   [DCA_CONF_DUNI]  sum_Wn k e_k / sum_Wn e_k        the soft-argmin of the winning mode alone (1/4-res pixels)
+ *   [DCA_CONF_MASS]  sum_Wn e_k / s                   the probability of that mode; radius 0: the peak probability
+ *   [DCA_CONF_ENT]   (logf(s) - sum_k e_k (x_k - m) / s) / logf(K)   entropy in [0, 1]; 0 for K = 1.  No 0 log 0: an
+ *                    underflowed e_k contributes 0, never NaN
+ *   [DCA_CONF_STD]   sqrt(sum_k e_k (k - d)^2 / s), d = plane 0   (two passes; E[k^2] - d^2 would cancel)
+ * radius >= 0; radius >= K means the whole range (DUNI = DISP up to rounding, MASS = 1).  K >= 1. */
+#define DCA_CONF_DISP 0
+#define DCA_CONF_DUNI 1
+#define DCA_CONF_MASS 2
+#define DCA_CONF_ENT 3
+#define DCA_CONF_STD 4
+#define DCA_CONF_PLANES 5
+int dca_softargmin_stats(const float* logits, float* out, int B, int K, long HW, int radius, hipStream_t stream);
+/* dca_convex_up4_planes: dca_convex_up4_fwd for P (1..DCA_CONF_MAX_PLANES) planes through ONE read of the mask logits:
+ * mask_logits (B,144,h,w), planes (B,P,h,w), scales: HOST array of P floats -> up (B,P,4h,4w),
+ * up_p = sum_k softmax_k(mask)[k,i,j] * scales[p] * planes_p[3x3 neighbour k].  The soft-max of a sub-pixel is computed
+ * once and applied to every plane with the loads, product and accumulation order of dca_convex_up4_fwd: a plane with
+ * scale 4 is bitwise that function's result.  Neighbours outside the map are 0 for EVERY plane (the reference's F.unfold
+ * zero padding, which the disparity already gets): at the frame border a confidence plane falls exactly where the
+ * disparity is pulled towards 0.  up must be 16-byte aligned. */
+#define DCA_CONF_MAX_PLANES 8
+int dca_convex_up4_planes(const float* mask_logits, const float* planes, const float* scales, float* up, int B, int P,
+                          int h, int w, hipStream_t stream);
+/* dca_conf_histogram: risk-coverage statistics.  conf, pred, gt: (B,HW) fp32; state: (nbins,3) int64 that the launch ADDS
+ * into (the caller zeroes it at the start of a run; states of several ranks add up).  A pixel counts if
+ * gt > 0 && gt < maxdisp && conf == conf;  bin = min(nbins - 1, (int)(clamp(conf, 0, 1) * nbins)) with the product in
+ * fp32;  err = |pred - gt| in fp32;  state[bin] += { 1, (long long)(err * 1048576.f) truncated, err > 3 }.  The error
+ * sum is kept in 2^-20 fixed point because integer sums do not depend on the order of the atomics: the state is bitwise
+ * reproducible.  2 <= nbins <= DCA_CONF_MAX_BINS. */
+#define DCA_CONF_MAX_BINS 1024
+#define DCA_CONF_ERR_SCALE 1048576
+int dca_conf_histogram(const float* conf, const float* pred, const float* gt, long long* state, int B, long HW, int nbins,
+                       float maxdisp, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
