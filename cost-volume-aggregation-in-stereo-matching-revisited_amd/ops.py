@@ -509,6 +509,52 @@ def _c1x3_eligible(x, x2, ksize, A, C1, y):
     return S % 4 == 0 and all(p % 16 == 0 for p in ptrs) and 64 * S * 4 < 0x7ffffff0
 
 
+def _conv_family(x, x2, A, B, ksize, stride, transposed, scale=None, res_pre=None, slope=1.0, y=None):
+    """the kernel family that serves y = conv(x [, x2]) -- "x2" (conv3d_f16x2.hip), "x3" (conv3d_bf16x3.hip), "s2x2"
+    (conv3d_s2_f16x2.hip), "dx3" (deconv3d_x3.hip), "c1x3" (conv1_x3.hip), else "mfma": the fp32 kernels of conv3d_mfma.hip,
+    which take every shape.  The only caller of the *_eligible predicates; y (the output tensor) is read for ksize 1 only."""
+    if _x3_eligible(x, x2, ksize, stride, transposed, A, B):
+        return "x2" if CONV_X2 else "x3"
+    if _s2x2_eligible(x, x2, ksize, stride, transposed, A, B, scale, res_pre, slope):
+        return "s2x2"
+    if _dx3_eligible(x, x2, ksize, stride, transposed, A, B):
+        return "dx3"
+    return "c1x3" if _c1x3_eligible(x, x2, ksize, A, x.shape[1], y) else "mfma"
+
+
+def _k3s1(weight, stride, transposed, x2, head=False):
+    """a 3x3x3 stride-1 convolution of one input, not transposed, that is not a logit head (Cout > 1): what the packed px2
+    operands, the twin and the alias output exist for.  head=True: that is one (Cout == 1) instead."""
+    return x2 is None and not transposed and int(stride) == 1 and weight.shape[2] == 3 and (weight.shape[0] == 1) == head
+
+
+def _x2_pairs(xp, yp, W):
+    """may the f16x2 3x3x3 stride-1 weight-gradient kernel read these two operands (packed px2 or not) at width W?  An fp32
+    operand needs W % 4 == 0 there; at any other width only two packed ones pair."""
+    return W % 4 == 0 or (xp and yp)
+
+
+def _wgrad_family(x, dy, Cx, Cy, ksize, stride):
+    """the kernel that serves the weight gradient of fine tensor x and dy: "x2" (conv3d_wgrad_f16x2.hip), "x3"
+    (conv3d_wgrad_bf16x3.hip), "s2x2" (conv3d_wgrad_s2_f16x2.hip: stride-2 / transposed convolution), else "mfma"
+    (conv3d_wgrad.hip, exact fp32, every shape).  Raises for a packed px2 operand that "x2" cannot take."""
+    Di, Hi, Wi = x.shape[2:]
+    Do, Ho, Wo = dy.shape[2:]
+    xp, yp = _is_packed(x), _is_packed(dy)
+    split = (CONV_X3 and ksize == 3 and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0
+             and max(Cx, Cy) * Di * Hi * Wi * 4 < 0x7ffffff0)
+    if split and CONV_X2 and stride == 1 and _x2_pairs(xp, yp, Wi):
+        return "x2"
+    if xp or yp:
+        raise RuntimeError("weight gradient: a packed px2 operand can only feed the f16x2 3x3x3 stride-1 kernel")
+    if split and stride == 1 and Wi % 4 == 0:
+        return "x3"
+    if (split and CONV_X2 and WGRAD_S2_X2 and stride == 2 and Wi % 4 == 0 and Wo % 4 == 0
+            and (Do, Ho, Wo) == ((Di + 1) // 2, (Hi + 1) // 2, (Wi + 1) // 2)):
+        return "s2x2"
+    return "mfma"
+
+
 def _slice_width(ksize, stride, transposed, B):
     """output channels one launch of dca_conv3d_forward produces (include/dca_hip.h)"""
     if ksize == 1 or transposed:
@@ -580,53 +626,41 @@ def _conv_sliced(x, x2, w_src, A, B, K, src_ab, flip, ksize, stride, transposed,
     write their channel slice of y (w_src is the PyTorch weight; src_ab / flip as in dca_conv3d_prep_weight).
     want_stats (no epilogue then): returns (y, part) where part holds the BatchNorm batch-statistics partials of y emitted
     by the convolution kernel itself (B * nchunk * 4 doubles, csrc/bn_fused_stats.h), or (y, None) when the kernel serving
-    this shape has no such form."""
-    y, part = _conv_sliced_impl(x, x2, w_src, A, B, K, src_ab, flip, ksize, stride, transposed, scale, shift, slope,
-                                res_pre, res_post, want_stats, emit_amax)
-    return (y, part) if want_stats else y
-
-
-def _conv_sliced_impl(x, x2, w_src, A, B, K, src_ab, flip, ksize, stride, transposed, scale, shift, slope, res_pre,
-                      res_post, want_stats, emit_amax=False):
-    """x may be a packed px2 operand (f16x2 kernels only); emit_amax: tag y with its per-channel maxima where the kernel
-    serving this shape can emit them (inference chains conv -> conv)"""
-    packed = _is_packed(x)
-    if packed and not (CONV_X2 and _x3_eligible(x, x2, ksize, stride, transposed, A, B)):
-        raise RuntimeError("conv3d: a packed px2 operand can only feed the f16x2 3x3x3 stride-1 convolution")
-    N = x.shape[0]
-    Di, Hi, Wi = x.shape[2:]
+    this shape has no such form.  x may be a packed px2 operand (f16x2 kernels only); emit_amax: tag y with its per-channel
+    maxima where the kernel serving this shape can emit them (inference chains conv -> conv)"""
+    N, C1, Di, Hi, Wi = x.shape
     Do, Ho, Wo = _out_dims((Di, Hi, Wi), ksize, stride, transposed)
     y = torch.empty((N, B, Do, Ho, Wo), device=x.device, dtype=torch.float32)
-    C1 = x.shape[1]
-    width = _slice_width(ksize, stride, transposed, B)
+    packed = _is_packed(x)
+    family = _conv_family(x, x2, A, B, ksize, stride, transposed, scale, res_pre, slope, y)
+    if packed and family != "x2":
+        raise RuntimeError("conv3d: a packed px2 operand can only feed the f16x2 3x3x3 stride-1 convolution")
     lib = _L()
-    if CONV_X2 and _x3_eligible(x, x2, ksize, stride, transposed, A, B):
+    partials = lambda nchunk: torch.empty((B * nchunk * 4,), device=x.device, dtype=torch.float64)   # bn_fused_stats.h
+    part = None
+    if family == "x2":
         wx, xexps = _x2_weights("dca_conv3d_x2", x, w_src, A, B, src_ab, flip, "packed" if packed else "tagged")
         if want_stats:
-            nchunk = lib.dca_conv3d_x2_stats_chunks(N, B, Di, Hi, Wi)
-            part = torch.empty((B * nchunk * 4,), device=x.device, dtype=torch.float64)
+            part = partials(lib.dca_conv3d_x2_stats_chunks(N, B, Di, Hi, Wi))
             _chk(lib.dca_conv3d_x2_forward_stats(_ptr(x), int(packed), _ptr(xexps), _ptr(wx), _ptr(y), _ptr(part), N, A, B,
                                                  Di, Hi, Wi, _stream()), "dca_conv3d_x2_forward_stats")
-            return y, part
-        ycm = _cslots(B, x.device) if emit_amax else None
-        _chk(lib.dca_conv3d_x2_forward(_ptr(x), int(packed), _ptr(xexps), _ptr(wx), _ptr(y), _ptr(scale), _ptr(shift),
-                                       _ptr(res_pre), _ptr(res_post), float(slope), _ptr(ycm), N, A, B, Di, Hi, Wi,
-                                       _stream()), "dca_conv3d_x2_forward")
-        _tag_cmax(y, ycm, lib.dca_conv3d_x2_stats_chunks(N, B, Di, Hi, Wi))
-        return y, None
-    if _x3_eligible(x, x2, ksize, stride, transposed, A, B):
+        else:
+            ycm = _cslots(B, x.device) if emit_amax else None
+            _chk(lib.dca_conv3d_x2_forward(_ptr(x), int(packed), _ptr(xexps), _ptr(wx), _ptr(y), _ptr(scale), _ptr(shift),
+                                           _ptr(res_pre), _ptr(res_post), float(slope), _ptr(ycm), N, A, B, Di, Hi, Wi,
+                                           _stream()), "dca_conv3d_x2_forward")
+            _tag_cmax(y, ycm, lib.dca_conv3d_x2_stats_chunks(N, B, Di, Hi, Wi))
+    elif family == "x3":
         wx = _x3_weights(w_src, A, B, src_ab, flip)
         if want_stats:
-            nchunk = lib.dca_conv3d_x3_stats_chunks(N, B, Di, Hi, Wi)
-            part = torch.empty((B * nchunk * 4,), device=x.device, dtype=torch.float64)
+            part = partials(lib.dca_conv3d_x3_stats_chunks(N, B, Di, Hi, Wi))
             _chk(lib.dca_conv3d_x3_forward_stats(_ptr(x), _ptr(wx), _ptr(y), _ptr(part), N, A, B, Di, Hi, Wi, _stream()),
                  "dca_conv3d_x3_forward_stats")
-            return y, part
-        _chk(lib.dca_conv3d_x3_forward(_ptr(x), _ptr(wx), _ptr(y), _ptr(scale), _ptr(shift), _ptr(res_pre),
-                                       _ptr(res_post), float(slope), N, A, B, Di, Hi, Wi, _stream()),
-             "dca_conv3d_x3_forward")
-        return y, None
-    if _s2x2_eligible(x, x2, ksize, stride, transposed, A, B, scale, res_pre, slope):
+        else:
+            _chk(lib.dca_conv3d_x3_forward(_ptr(x), _ptr(wx), _ptr(y), _ptr(scale), _ptr(shift), _ptr(res_pre),
+                                           _ptr(res_post), float(slope), N, A, B, Di, Hi, Wi, _stream()),
+                 "dca_conv3d_x3_forward")
+    elif family == "s2x2":
         wx, xexps = _x2_weights("dca_conv3d_s2x2", x, w_src, A, B, src_ab, flip, "tagged")
         nsl = lib.dca_conv3d_s2x2_out_slots(N, B, Di, Hi, Wi)
         ycm = _cslots(B, x.device) if (emit_amax and nsl <= CSLOTS) else None
@@ -634,26 +668,21 @@ def _conv_sliced_impl(x, x2, w_src, A, B, K, src_ab, flip, ksize, stride, transp
                                          _ptr(res_post), _ptr(ycm), N, A, B, Di, Hi, Wi, _stream()), "dca_conv3d_s2x2_forward")
         if ycm is not None:
             _tag_cmax(y, ycm, nsl)
-        return y, None
-    if _dx3_eligible(x, x2, ksize, stride, transposed, A, B):
+    elif family == "dx3":
         wx = _x3_weights(w_src, A, B, src_ab, flip)
         if want_stats:
-            nchunk = lib.dca_deconv3d_x3_stats_chunks(N, Di, Hi, Wi)
-            part = torch.empty((B * nchunk * 4,), device=x.device, dtype=torch.float64)
+            part = partials(lib.dca_deconv3d_x3_stats_chunks(N, Di, Hi, Wi))
             _chk(lib.dca_deconv3d_x3_forward_stats(_ptr(x), _ptr(wx), _ptr(y), _ptr(part), N, A, B, Di, Hi, Wi,
                                                    _stream()), "dca_deconv3d_x3_forward_stats")
-            return y, part
-        _chk(lib.dca_deconv3d_x3_forward(_ptr(x), _ptr(wx), _ptr(y), _ptr(scale), _ptr(shift), _ptr(res_pre),
-                                         _ptr(res_post), float(slope), N, A, B, Di, Hi, Wi, _stream()),
-             "dca_deconv3d_x3_forward")
-        return y, None
-    if _c1x3_eligible(x, x2, ksize, A, C1, y):
+        else:
+            _chk(lib.dca_deconv3d_x3_forward(_ptr(x), _ptr(wx), _ptr(y), _ptr(scale), _ptr(shift), _ptr(res_pre),
+                                             _ptr(res_post), float(slope), N, A, B, Di, Hi, Wi, _stream()),
+                 "dca_deconv3d_x3_forward")
+    elif family == "c1x3":
         S = Do * Ho * Wo
         C2 = 0 if x2 is None else x2.shape[1]
-        part = None
         if want_stats:
-            nchunk = lib.dca_conv1_x3_stats_chunks(N, S)
-            part = torch.empty((B * nchunk * 4,), device=x.device, dtype=torch.float64)
+            part = partials(lib.dca_conv1_x3_stats_chunks(N, S))
         for b0 in range(0, B, 32):
             bn = min(32, B - b0)
 
@@ -671,14 +700,15 @@ def _conv_sliced_impl(x, x2, w_src, A, B, K, src_ab, flip, ksize, stride, transp
                 _chk(lib.dca_conv1_x3_forward(_ptr(x), _ptr(x2), _ptr(wf), _ptr(y), _ptr(scale), _ptr(shift),
                                               _ptr(res_pre), _ptr(res_post), float(slope), N, C1, C2, bn, B, b0, S,
                                               _stream()), "dca_conv1_x3_forward")
-        return y, part
-    for b0 in range(0, B, width):
-        bn = min(width, B - b0)
-        wt, Apad = _prep_weight(w_src, A, B, K, src_ab, flip, ksize, stride, transposed, b0, bn)
-        _chk(lib.dca_conv3d_forward(_ptr(x), _ptr(x2), _ptr(wt), _ptr(y), _ptr(scale), _ptr(shift), _ptr(res_pre),
-                                    _ptr(res_post), float(slope), N, A, C1, bn, Apad, B, b0, Di, Hi, Wi, Do, Ho, Wo,
-                                    ksize, stride, int(transposed), _stream()), "dca_conv3d_forward")
-    return y, None
+    else:
+        width = _slice_width(ksize, stride, transposed, B)
+        for b0 in range(0, B, width):
+            bn = min(width, B - b0)
+            wt, Apad = _prep_weight(w_src, A, B, K, src_ab, flip, ksize, stride, transposed, b0, bn)
+            _chk(lib.dca_conv3d_forward(_ptr(x), _ptr(x2), _ptr(wt), _ptr(y), _ptr(scale), _ptr(shift), _ptr(res_pre),
+                                        _ptr(res_post), float(slope), N, A, C1, bn, Apad, B, b0, Di, Hi, Wi, Do, Ho, Wo,
+                                        ksize, stride, int(transposed), _stream()), "dca_conv3d_forward")
+    return (y, part) if want_stats else y
 
 
 def conv3d_prepared(x, wt, A, Apad, B, ksize, stride, transposed):
@@ -716,38 +746,27 @@ def _wgrad(x, dy, dw_view_ptr_tensor, dst_offset, Cx, Cy, ksize, stride, s_cy, s
     Do, Ho, Wo = dy.shape[2:]
     dst = _vp(dw_view_ptr_tensor.data_ptr() + 4 * dst_offset)
     lib = _L()
-    xp, yp = _is_packed(x), _is_packed(dy)
-    if (CONV_X2 and CONV_X3 and ksize == 3 and stride == 1 and (xp or Wi % 4 == 0) and (yp or Wi % 4 == 0)
-            and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0 and max(Cx, Cy) * Di * Hi * Wi * 4 < 0x7ffffff0):
+    family = _wgrad_family(x, dy, Cx, Cy, ksize, stride)
+    workspace = lambda nws: torch.empty((nws,), device=x.device, dtype=torch.float32)
+    if family == "x2":
         xex, yex = _exps_of(x), _exps_of(dy)
-        nws = lib.dca_conv3d_wgrad_x2_workspace(N, Cx, Cy, Di, Hi, Wi)
-        part = torch.empty((nws,), device=x.device, dtype=torch.float32)
-        _chk(lib.dca_conv3d_wgrad_x2(_ptr(x), int(xp), _ptr(xex), _ptr(dy), int(yp), _ptr(yex), _ptr(part), dst, N, Cx, Cy,
-                                     Di, Hi, Wi, s_cy, s_cx, _stream()), "dca_conv3d_wgrad_x2")
-        return
-    if xp or yp:
-        raise RuntimeError("weight gradient: a packed px2 operand can only feed the f16x2 3x3x3 stride-1 kernel")
-    if (CONV_X3 and ksize == 3 and stride == 1 and Wi % 4 == 0 and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0
-            and max(Cx, Cy) * Di * Hi * Wi * 4 < 0x7ffffff0):
-        nws = lib.dca_conv3d_wgrad_x3_workspace(N, Cx, Cy, Di, Hi, Wi)
-        part = torch.empty((nws,), device=x.device, dtype=torch.float32)
+        part = workspace(lib.dca_conv3d_wgrad_x2_workspace(N, Cx, Cy, Di, Hi, Wi))
+        _chk(lib.dca_conv3d_wgrad_x2(_ptr(x), int(_is_packed(x)), _ptr(xex), _ptr(dy), int(_is_packed(dy)), _ptr(yex),
+                                     _ptr(part), dst, N, Cx, Cy, Di, Hi, Wi, s_cy, s_cx, _stream()), "dca_conv3d_wgrad_x2")
+    elif family == "x3":
+        part = workspace(lib.dca_conv3d_wgrad_x3_workspace(N, Cx, Cy, Di, Hi, Wi))
         _chk(lib.dca_conv3d_wgrad_x3(_ptr(x), _ptr(dy), _ptr(part), dst, N, Cx, Cy, Di, Hi, Wi, s_cy, s_cx, _stream()),
              "dca_conv3d_wgrad_x3")
-        return
-    if (CONV_X2 and CONV_X3 and WGRAD_S2_X2 and ksize == 3 and stride == 2 and Wi % 4 == 0 and Wo % 4 == 0
-            and (Do, Ho, Wo) == ((Di + 1) // 2, (Hi + 1) // 2, (Wi + 1) // 2)
-            and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0 and max(Cx, Cy) * Di * Hi * Wi * 4 < 0x7ffffff0):
+    elif family == "s2x2":
         # stride-2 convolution / transposed convolution: x = the fine tensor, dy = the coarse one (conv3d_wgrad_s2_f16x2.hip)
         xex, yex = _exps_of(x), _exps_of(dy)
-        nws = lib.dca_conv3d_wgrad_s2_x2_workspace(N, Cx, Cy, Di, Hi, Wi)
-        part = torch.empty((nws,), device=x.device, dtype=torch.float32)
+        part = workspace(lib.dca_conv3d_wgrad_s2_x2_workspace(N, Cx, Cy, Di, Hi, Wi))
         _chk(lib.dca_conv3d_wgrad_s2_x2(_ptr(x), _ptr(xex), _ptr(dy), _ptr(yex), _ptr(part), dst, N, Cx, Cy, Di, Hi, Wi,
                                         s_cy, s_cx, _stream()), "dca_conv3d_wgrad_s2_x2")
-        return
-    nws = lib.dca_conv3d_wgrad_workspace(N, Cx, Cy, Do, Ho, Wo, ksize, stride)
-    part = torch.empty((nws,), device=x.device, dtype=torch.float32)
-    _chk(lib.dca_conv3d_wgrad(_ptr(x), _ptr(dy), _ptr(part), dst, N, Cx, Cy, Di, Hi, Wi, Do, Ho, Wo, ksize, stride,
-                              s_cy, s_cx, _stream()), "dca_conv3d_wgrad")
+    else:
+        part = workspace(lib.dca_conv3d_wgrad_workspace(N, Cx, Cy, Do, Ho, Wo, ksize, stride))
+        _chk(lib.dca_conv3d_wgrad(_ptr(x), _ptr(dy), _ptr(part), dst, N, Cx, Cy, Di, Hi, Wi, Do, Ho, Wo, ksize, stride,
+                                  s_cy, s_cx, _stream()), "dca_conv3d_wgrad")
 
 
 class _Conv3dC1(torch.autograd.Function):
@@ -817,10 +836,9 @@ class _Conv3d(torch.autograd.Function):
         ctx.packed_dy = bool(packed_dy)              # the gradient of y arrives as a packed px2 operand (_BnAct, pack_dy)
         ctx.x_exps = None
         # a packed twin of x (written beside it by its BatchNorm): this convolution and its weight gradient read the twin
-        xt = None
-        if (PACK and CONV_X2 and x2 is None and not transposed and stride == 1 and weight.shape[2] == 3 and weight.shape[0] > 1
-                and _x3_eligible(x, None, 3, 1, False, weight.shape[1], weight.shape[0])):
-            xt = _twin_of(x)
+        Cout, Cin = weight.shape[:2]
+        twin = PACK and _k3s1(weight, stride, transposed, x2) and _conv_family(x, None, Cin, Cout, 3, 1, False) == "x2"
+        xt = _twin_of(x) if twin else None
         ctx.x_twin = xt
         xin = x if xt is None else xt
         with torch.cuda.device_of(x):
@@ -854,10 +872,10 @@ class _Conv3d(torch.autograd.Function):
             raise RuntimeError("conv3d.backward: expected the packed px2 gradient of the BatchNorm behind this convolution "
                                "(the tag was lost on the way through autograd)")
         dy = _req(dy, "conv3d.backward", packed_ok=True)
-        if ctx.x_twin is not None and not _is_packed(dy) and x.shape[-1] % 4:
-            # the f16x2 weight-gradient kernel pairs a packed operand with an fp32 one only at W % 4 == 0, and an fp32 x of
-            # such a width never gets a packed dy (_pack_dy_ok): the weight gradient reads the fp32 x and takes the kernel
-            # that serves this width; the forward read the twin, which holds the same values
+        if ctx.x_twin is not None and not _x2_pairs(True, _is_packed(dy), x.shape[-1]):
+            # the twin cannot be paired with this dy (an fp32 x of such a width never gets a packed one: _pack_dy_ok): the
+            # weight gradient reads the fp32 x and takes the kernel that serves this width; the forward read the twin, which
+            # holds the same values
             xw = x
         ksize = weight.shape[2]
         K = ksize ** 3
@@ -967,8 +985,7 @@ def convbn3d_pair(x, conv_a, bn_a, slope_a, conv_b, bn_b, slope_b, pack_a=False)
 
 
 def conv3d(x, weight, stride=1, transposed=False, x2=None):
-    if (not transposed and x2 is None and weight.shape[0] == 1 and weight.shape[2] == 3 and int(stride) == 1
-            and weight.shape[1] in (32, 64)):
+    if _k3s1(weight, stride, transposed, x2, head=True) and weight.shape[1] in (32, 64):
         return _Conv3dC1.apply(x, weight)
     return _Conv3d.apply(x, x2, weight, int(stride), bool(transposed))
 
@@ -1301,12 +1318,12 @@ def _lp_dtype():
 def _pack_dy_ok(x, x2, conv, transposed, stride, res_pre):
     """may the gradient of this convolution's output travel as a packed px2 operand?  (its only readers are then the f16x2
     backward-data and weight-gradient kernels of this very convolution)"""
-    if not (PACK and CONV_X2 and x2 is None and not transposed and stride == 1 and conv.kernel_size[0] == 3 and res_pre is None):
+    if not (PACK and res_pre is None and _k3s1(conv.weight, stride, transposed, x2)):
         return False
     Cout, Cin = conv.weight.shape[0], conv.weight.shape[1]
-    if Cout % 8 or Cout < 8 or not _x3_eligible(x, None, 3, 1, False, Cin, Cout):
+    if Cout % 8 or _conv_family(x, None, Cin, Cout, 3, 1, False) != "x2":
         return False
-    return _is_packed(x) or (x.shape[-1] % 4 == 0 and x.data_ptr() % 16 == 0)
+    return _x2_pairs(_is_packed(x), True, x.shape[-1]) and (_is_packed(x) or x.data_ptr() % 16 == 0)
 
 
 def convbn3d(x, conv, bn, slope=1.0, res_pre=None, res_post=None, x2=None, alias=False, pack_out=False):
@@ -1327,8 +1344,8 @@ def convbn3d(x, conv, bn, slope=1.0, res_pre=None, res_post=None, x2=None, alias
     if alias:
         # alias=True: returns (z, x') with x' = x for the other consumers of x (see _Conv3d.forward); plain (z, x) where the
         # fused form does not apply
-        fuse = (PAIR_FUSE and torch.is_grad_enabled() and x.requires_grad and x2 is None and not transposed and stride == 1
-                and conv.kernel_size[0] == 3 and conv.weight.shape[0] > 1 and _lp_dtype() is None and x.dtype == torch.float32)
+        fuse = (PAIR_FUSE and torch.is_grad_enabled() and x.requires_grad and _k3s1(conv.weight, stride, transposed, x2)
+                and _lp_dtype() is None and x.dtype == torch.float32)
         if not fuse:
             return convbn3d(x, conv, bn, slope, res_pre, res_post, x2), x
         stats = bool(BN_FUSE and bn.training)
