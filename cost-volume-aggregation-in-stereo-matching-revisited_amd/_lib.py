@@ -113,6 +113,8 @@ SIGNATURES = {
     "dca_softargmin_stats": (_i, [_p, _p, _i, _i, _l, _i, _p]),
     "dca_convex_up4_planes": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "dca_conf_histogram": (_i, [_p, _p, _p, _p, _i, _l, _i, _f, _p]),
+    "dca_mirror_pair": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
+    "dca_lr_consistency": (_i, [_p] * 6 + [_i] * 4 + [_f, _p]),
 }
 
 _lib = None

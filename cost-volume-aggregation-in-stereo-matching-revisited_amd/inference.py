@@ -12,7 +12,11 @@ float32 / uint16 disparity is read back -- two copies are all that is left on th
 
 `KittiInferenceWithConfidence` returns a confidence map next to every disparity map: the probability mass of the final
 disparity distribution within `radius` bins of its peak, up-sampled with the disparity in one launch (DESIGN.md section
-6e; nothing in the reference computes it)."""
+6e; nothing in the reference computes it).
+
+`KittiInferenceLR` returns the left-right-checked, filled disparity and its validity mask: a second pass on the mirrored,
+swapped frames gives the right view's disparity, one launch cross-checks and fills (nothing in the
+reference computes it)."""
 from __future__ import annotations
 
 import collections
@@ -149,11 +153,17 @@ class KittiInference:
     `device_io=True`: normalisation, padding, crop and the uint16 conversion run as HIP kernels; the host only copies the
     uint8 pair into pinned memory and the result out of it.  `stream(pairs)` pipelines successive frames.
 
-    The subclass `KittiInferenceWithConfidence` hands out `(disp, conf)` per frame (class attribute `confidence`)."""
+    The subclass `KittiInferenceWithConfidence` hands out `(disp, conf)` per frame (class attribute `confidence`), the
+    subclass `KittiInferenceLR` `(disp_filled, valid)`: a frame's maps come from `_frame_maps`, `nmaps` of them."""
 
     confidence = False           # True: a confidence map next to every disparity map (KittiInferenceWithConfidence)
     radius = 1                   # its window, in 1/4-res disparity bins either side of the peak
-    CONF_U16_SCALE = 65535.0
+    CONF_U16_SCALE = 65535.0      # uint16 scale of the second map (a confidence in [0,1]; a 0 / 1 validity mask)
+
+    @property
+    def nmaps(self):
+        """maps handed out per frame: the disparity[, a second map in [0,1]]"""
+        return 2 if self.confidence else 1
 
     def __init__(self, model, crop_height: int = 384, crop_width: int = 1248, graph: bool = True, dtype=None,
                  device_io: bool = False):
@@ -199,6 +209,11 @@ class KittiInference:
         up = net.prop.forward_planes(guidance, r["stats4_q"][:, :ops.CONF_MASS + 1], (4.0, 4.0, 1.0))
         return up[:, ops.CONF_DISP:ops.CONF_DISP + 1], up[:, ops.CONF_MASS:ops.CONF_MASS + 1]
 
+    def _frame_maps(self, left, right, cols):
+        """the `nmaps` maps of one frame as a tuple; cols: the image's width inside the frame"""
+        maps = self.forward_frame(left, right)
+        return maps if self.confidence else (maps,)
+
     # ---- device I/O: three stages per frame, each enqueued on the stream it is given --------------------------------
     def _slot(self, i):
         dev = next(self.net.parameters()).device
@@ -242,8 +257,7 @@ class KittiInference:
             lut, _ = ops.frame_lut(ops.frame_histogram(left, right), h * w)
             fl, fr = ops.frame_apply(left, right, lut, (self.crop_height, self.crop_width), src_y0, dst_y0, rows, cols,
                                      out=self._frames)
-            maps = self.forward_frame(fl, fr)
-            maps = maps if self.confidence else (maps,)
+            maps = self._frame_maps(fl, fr, cols)
             dev = s.output(as_uint16, len(maps))[0]
             for k, (m, scale) in enumerate(zip(maps, (256.0, self.CONF_U16_SCALE))):
                 out = dev[k * rows * cols:(k + 1) * rows * cols].view(rows, cols)
@@ -257,7 +271,7 @@ class KittiInference:
     def _readback(self, s, copy):
         """`copy` stream: device output -> pinned"""
         rows, cols = s.meta[3][2:]
-        nmaps = 2 if self.confidence else 1
+        nmaps = self.nmaps
         dev, pin = s.output(s.as_uint16, nmaps)
         n = nmaps * rows * cols                          # one copy: the disparity, and the confidence behind it
         with torch.cuda.stream(copy):
@@ -269,10 +283,10 @@ class KittiInference:
         """host: the one synchronisation of a frame, then the result out of the pinned buffer"""
         rows, cols = s.meta[3][2:]
         s.done.synchronize()
-        nmaps = 2 if self.confidence else 1
+        nmaps = self.nmaps
         pin = s.output(s.as_uint16, nmaps)[1]
         maps = tuple(pin[k * rows * cols:(k + 1) * rows * cols].numpy().reshape(rows, cols).copy() for k in range(nmaps))
-        return maps if self.confidence else maps[0]
+        return maps if nmaps > 1 else maps[0]
 
     def _call_device(self, left_rgb, right_rgb, as_uint16):
         dev = next(self.net.parameters()).device
@@ -328,9 +342,9 @@ class KittiInference:
             return self._call_device(left_rgb, right_rgb, as_uint16)
         left, right, h, w = pad_or_crop(normalize_pair(left_rgb, right_rgb), self.crop_height, self.crop_width)
         dev = next(self.net.parameters()).device
-        maps = self.forward_frame(left.to(dev), right.to(dev))
-        if not self.confidence:
-            disp = crop_back(maps.squeeze().cpu().numpy(), h, w, self.crop_height, self.crop_width)
+        maps = self._frame_maps(left.to(dev), right.to(dev), min(w, self.crop_width))
+        if len(maps) == 1:
+            disp = crop_back(maps[0].squeeze().cpu().numpy(), h, w, self.crop_height, self.crop_width)
             return (disp * 256).astype("uint16") if as_uint16 else disp           # my_img.py:110
         disp, conf = (crop_back(m.squeeze().cpu().numpy(), h, w, self.crop_height, self.crop_width) for m in maps)
         if as_uint16:      # fp32 products, truncated, as dca_disp_export
@@ -354,6 +368,40 @@ class KittiInferenceWithConfidence(KittiInference):
         if int(radius) < 0:
             raise ValueError("radius >= 0")
         self.radius = int(radius)
+
+
+class KittiInferenceLR(KittiInference):
+    """`disp_filled, valid = KittiInferenceLR(model, ..., tau=1.0)(left_rgb, right_rgb)`: KittiInference with the same
+    arguments (host or device I/O, eager or graph, fp32 or reduced precision) whose `__call__` and `stream()` hand out a
+    `(disp_filled, valid)` tuple per frame (GwcNet.predict_lr's maps of those names; ops.lr_consistency).  Every frame
+    takes two passes of the network: the frames as they are, then the mirrored, swapped frames (`ops.mirror_pair` of the
+    float32 frames -- with device I/O the ones `frame_apply` wrote: the look-up table does not depend on the pixel
+    order, so that is exact), which give the right view's disparity.  With `graph=True` both passes replay the SAME
+    captured hot path; the first pass's 1/4-res disparity goes through the up-sampler, which allocates its result, before
+    the second replay overwrites the graph's static buffers.  Only the image's own columns take part in the check (`cols`
+    = its width inside the frame): the zero padding on the right is never matched against and never a fill source.
+    `valid` is float32 1.0 / 0.0, or uint16 65535 / 0 with as_uint16 (dca_disp_export with scale 65535).  With device I/O
+    both maps come back in one copy and one synchronisation per frame.  A frame costs about two of KittiInference's."""
+
+    nmaps = 2
+
+    def __init__(self, model, *args, tau: float = 1.0, **kwargs):
+        super().__init__(model, *args, **kwargs)
+        tau = float(tau)
+        if not (0.0 <= tau < float("inf")):
+            raise ValueError("tau must be finite and >= 0")
+        self.tau = tau
+        self._mirrored = None        # (2,1,3,Hc,Wc): the mirrored, swapped frames, rewritten whole by every frame
+
+    @torch.no_grad()
+    def _frame_maps(self, left, right, cols):
+        from . import ops
+        disp = self.forward_frame(left, right)       # its own tensor: the second replay below does not touch it
+        if self._mirrored is None or self._mirrored.shape[1:] != left.shape or self._mirrored.device != left.device:
+            self._mirrored = torch.empty((2,) + tuple(left.shape), device=left.device, dtype=torch.float32)
+        disp_m = self.forward_frame(*ops.mirror_pair(left.contiguous(), right.contiguous(), out=self._mirrored))
+        r = ops.lr_consistency(disp.contiguous(), disp_m.contiguous(), self.tau, cols, outputs=("valid", "filled"))
+        return r["filled"], r["valid"]
 
 
 def confidence_png(path: str, conf: np.ndarray) -> None:

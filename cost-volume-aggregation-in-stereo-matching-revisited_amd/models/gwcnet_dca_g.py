@@ -231,6 +231,29 @@ class GwcNet(nn.Module):
         finally:
             self.train(was_training)
 
+    def predict_lr(self, left, right, tau=1.0):
+        """Inference with the left-right consistency check (no counterpart in the reference): eval
+        mode, no grad.  Two passes of the unchanged network at the caller's batch size -- (left, right), then the mirrored,
+        swapped pair `ops.mirror_pair(left, right)`, which yields the right view's disparity in mirrored coordinates --
+        and one `ops.lr_consistency` launch.  The pairs are NOT stacked into one batch: the f16x2 operand scales are taken
+        per channel over the whole tensor, so a second pair in the batch would change the left disparity.  Returns full-
+        resolution (B,1,H,W) maps: `disp` (bitwise `forward(left, right)[0]`), `disp_filled` (`disp` where the two views
+        agree within `tau` pixels; elsewhere the smaller of the nearest agreeing neighbours in the row), `valid` (1.0 /
+        0.0), `lr_diff` (|d_left - d_right| at the matched position, +inf where that lies outside the image) and
+        `disp_right` (the right view's disparity in its own coordinates)."""
+        ops._req_no_grad("predict_lr", left, right)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                disp = self.forward(left, right)[0]
+                disp_m = self.forward(*ops.mirror_pair(left, right))[0]
+                r = ops.lr_consistency(disp, disp_m, tau)
+            return {"disp": disp, "disp_filled": r["filled"], "valid": r["valid"], "lr_diff": r["diff"],
+                    "disp_right": r["disp_right"]}
+        finally:
+            self.train(was_training)
+
 
 def __getattr__(name):
     # the reference also defines `hourglass` (gwcnet_dca_g.py:69-106); it lives in models/gwcnet.py here

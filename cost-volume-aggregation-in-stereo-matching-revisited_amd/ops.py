@@ -1981,6 +1981,79 @@ def conf_histogram(conf, pred, gt, state, maxdisp):
 
 
 # ------------------------------------------------------------------------------------------------
+# Left-right consistency (csrc/lr_consistency.hip): inference only, no counterpart in the reference
+# ------------------------------------------------------------------------------------------------
+LR_MAX_W = 8192              # DCA_LR_MAX_W
+LR_OUTPUTS = ("diff", "valid", "filled", "disp_right")
+
+
+def _req_f32_same(name, a, b, what):
+    """two contiguous float32 tensors of one non-empty shape on one ROCm device, as they are (no copy is made)"""
+    for t in (a, b):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{name}: {what} must be on the ROCm device; there is no CPU fallback")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"{name}: {what} must be contiguous float32 tensors, got {t.dtype}"
+                               f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+    if a.shape != b.shape or a.device != b.device or a.numel() == 0:
+        raise RuntimeError(f"{name}: {what} must have one non-empty shape on one device, got {tuple(a.shape)} on {a.device} "
+                           f"and {tuple(b.shape)} on {b.device}")
+
+
+def mirror_pair(left, right, out=None):
+    """(left, right) (...,H,W) float32 -> (flipW(right), flipW(left)), bit copies, one launch: the mirrored, swapped pair on
+    which the unchanged network computes the RIGHT view's disparity in mirrored coordinates (include/dca_hip.h).
+    out: a contiguous float32 (2, *left.shape) buffer to write into (allocated when None); the results are its two halves."""
+    _req_no_grad("mirror_pair", left, right)
+    _req_f32_same("mirror_pair", left, right, "left and right")
+    if left.dim() < 2:
+        raise RuntimeError(f"mirror_pair: expected (...,H,W) images, got {tuple(left.shape)}")
+    if out is None:
+        out = torch.empty((2,) + tuple(left.shape), device=left.device, dtype=torch.float32)
+    _req_dev(out, "mirror_pair", "out", torch.float32, (2,) + tuple(left.shape))
+    if out.device != left.device or out.untyped_storage().data_ptr() in (left.untyped_storage().data_ptr(),
+                                                                         right.untyped_storage().data_ptr()):
+        raise RuntimeError("mirror_pair: out must be a buffer of its own on the images' device (the flip is not in place)")
+    H, W = int(left.shape[-2]), int(left.shape[-1])
+    with torch.cuda.device_of(left):
+        _chk(_L().dca_mirror_pair(_ptr(left), _ptr(right), _ptr(out[0]), _ptr(out[1]), left.numel() // (H * W), H, W,
+                                  _stream()), "dca_mirror_pair")
+    return out[0], out[1]
+
+
+def lr_consistency(disp_left, disp_right_mirrored, tau=1.0, cols=None, outputs=None):
+    """Cross-check of a left disparity map against the right view's, invalidation and background fill, ONE launch
+    (definitions: include/dca_hip.h, dca_lr_consistency).  disp_left, disp_right_mirrored: (B,1,H,W) or (B,H,W) float32;
+    the second is what the network gives on `mirror_pair(left, right)`: right-image column i at index W-1-i.  tau: finite,
+    >= 0.  cols (default W): only columns [0, cols) of either image take part (a frame zero-padded on the right).
+    Returns a dict of maps shaped like the input: `diff` (|d - r|, +inf out of view), `valid` (1.0 / 0.0), `filled`
+    (valid pixels bit for bit; invalid ones from the nearest valid neighbours in the row, the smaller of the two) and
+    `disp_right` (the right view's disparity in its own coordinates).  outputs: the names wanted (default all four;
+    `valid` is always computed) -- the others are neither computed nor written.  W <= 8192.  Bitwise reproducible."""
+    _req_no_grad("lr_consistency", disp_left, disp_right_mirrored)
+    _req_f32_same("lr_consistency", disp_left, disp_right_mirrored, "the two disparity maps")
+    shape = tuple(disp_left.shape)
+    if len(shape) not in (3, 4) or (len(shape) == 4 and shape[1] != 1):
+        raise RuntimeError(f"lr_consistency: expected (B,1,H,W) or (B,H,W) disparity maps, got {shape}")
+    B, H, W = shape[0], shape[-2], shape[-1]
+    tau = float(tau)
+    if not (0.0 <= tau < math.inf):
+        raise RuntimeError(f"lr_consistency: tau must be finite and >= 0, got {tau}")
+    cols = W if cols is None else int(cols)
+    if not 1 <= cols <= W or W > LR_MAX_W:
+        raise RuntimeError(f"lr_consistency: 1 <= cols <= W <= {LR_MAX_W}, got cols {cols} and W {W}")
+    names = LR_OUTPUTS if outputs is None else tuple(outputs)
+    if any(n not in LR_OUTPUTS for n in names):
+        raise RuntimeError(f"lr_consistency: outputs are chosen from {LR_OUTPUTS}, got {names}")
+    res = {n: torch.empty(shape, device=disp_left.device, dtype=torch.float32) for n in LR_OUTPUTS
+           if n in names or n == "valid"}
+    with torch.cuda.device_of(disp_left):
+        _chk(_L().dca_lr_consistency(_ptr(disp_left), _ptr(disp_right_mirrored), *(_ptr(res.get(n)) for n in LR_OUTPUTS),
+                                     B, H, W, cols, tau, _stream()), "dca_lr_consistency")
+    return res
+
+
+# ------------------------------------------------------------------------------------------------
 # Inference frame I/O (my_img.py:47-110 around the model call): per-plane normalisation as histogram -> table -> look-up,
 # placement in the zero-padded frame, export of the cropped disparity (csrc/frame_io.hip).  No launch synchronises.
 # ------------------------------------------------------------------------------------------------

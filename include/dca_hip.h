@@ -573,6 +573,34 @@ int dca_convex_up4_planes(const float* mask_logits, const float* planes, const f
 int dca_conf_histogram(const float* conf, const float* pred, const float* gt, long long* state, int B, long HW, int nbins,
                        float maxdisp, hipStream_t stream);
 
+/* ---- left-right consistency (lr_consistency.hip); inference only, no backward, no counterpart in the reference ------------
+ * dca_mirror_pair: left, right (N,H,W) planar fp32 (N = B 3 for frames) -> out_left = flipW(right), out_right = flipW(left)
+ * in one launch, as bit copies.  On this mirrored, swapped pair the unchanged network computes the RIGHT view's disparity
+ * in mirrored coordinates: with R'(x) = R(W-1-x) and L'(x) = L(W-1-x), corr(R'(x), L'(x-d)) = corr(R(u), L(u+d)) at
+ * u = W-1-x.  The outputs must not alias the inputs or each other.
+ *
+ * dca_lr_consistency: ONE launch, one workgroup per image row.  dl (B,H,W): the left disparity; drm (B,H,W): the right
+ * disparity as the mirrored pass produced it -- right-image column i sits at index W-1-i, dR(i) = drm[W-1-i] (no un-flip
+ * pass); tau: finite, >= 0; cols, 1 <= cols <= W: the active width -- only columns [0, cols) of either image take part (a
+ * frame zero-padded on the right: the padding's disparity is never matched against and never a fill source).
+ * Outputs diff, valid, filled, disp_right (B,H,W) fp32; any pointer except valid may be NULL.  Per pixel x < cols, d = dl[x]:
+ *   xr = float(x) - d;  inview = d > 0 && xr >= 0;  i0 = floor(xr);  f = xr - i0;  i1 = min(i0 + 1, cols - 1);
+ *   r = (1 - f) dR(i0) + f dR(i1)            (fp32, products and sum rounded separately)
+ *   diff  = inview ? |d - r| : +inf          NaN when r is NaN; +inf when d is NaN (not in view)
+ *   valid = diff <= tau ? 1.0 : 0.0          a NaN never becomes valid and is never a fill source
+ *   filled: a valid pixel keeps dl bit for bit.  An invalid one, with l / rt the nearest valid column to its left / right
+ *           within [0, cols): both exist -> min(dl[l], dl[rt]) (the occluded band belongs to the background: the KITTI
+ *           devkit's background interpolation, rows only); one exists -> its value; none in the row -> dl, unchanged.
+ *   disp_right[i] = dR(i): the right view's disparity in its own coordinates.
+ * For x >= cols: valid = 0, diff = +inf, filled = dl, disp_right = drm[W-1-x].
+ * W <= DCA_LR_MAX_W (both rows are staged in LDS: 2 W floats).  After the comparison everything is integer arithmetic or a
+ * copy of an input value: bitwise reproducible. */
+#define DCA_LR_MAX_W 8192
+int dca_mirror_pair(const float* left, const float* right, float* out_left, float* out_right, int N, int H, int W,
+                    hipStream_t stream);
+int dca_lr_consistency(const float* dl, const float* drm, float* diff, float* valid, float* filled, float* disp_right,
+                       int B, int H, int W, int cols, float tau, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
