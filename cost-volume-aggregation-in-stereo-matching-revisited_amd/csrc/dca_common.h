@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/dca_hip.h"  // every translation unit that defines an entry point is compiled against its declaration
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -128,7 +129,7 @@ __device__ __forceinline__ float4 dca_bload4(__amdgpu_buffer_rsrc_t r, int byte_
 //      - atomicMax spread over 64 words was read WRONGLY inside hipGraph replays (root cause: DESIGN.md section 3,
 //        tools/graph_amax_repro.hip);
 //  * or a bound the producer computes before it writes (the packed "px2" operand format below).
-#define DCA_AMAX_CSLOTS 1024
+// DCA_AMAX_CSLOTS itself is part of the ABI (the caller allocates the slots): include/dca_hip.h defines it.
 // a value another kernel wrote shortly before, read with a device-coherent vector load instead of an s_load through the
 // scalar data cache
 __device__ __forceinline__ float dca_coherent_loadf(const float* p) {

@@ -18,11 +18,12 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import _lib, ops
 from .graph import GraphedHotPath
 
 # state layout: include/dca_hip.h (DCA_EVAL_*)
-BATCHES, SUMS, IMG_KEPT, IMG_EPE, IMG_D1, IMG_THRES, IMG_SEEN, PIXELS = 0, 1, 11, 12, 13, 14, 17, 18
+BATCHES, SUMS, IMG_KEPT, IMG_EPE, IMG_D1, IMG_THRES, IMG_SEEN, PIXELS = (
+    _lib.CONSTANTS[f"DCA_EVAL_{n}"] for n in ("BATCHES", "SUMS", "IMG_KEPT", "IMG_EPE", "IMG_D1", "IMG_THRES", "IMG_SEEN", "PIXELS"))
 STATE_HEAD = ops.EVAL_STATE_HEAD
 KEYS = ("loss", "epe", "1px", "3px", "mpa0", "mpa1", "mpa2", "mIoU0", "mIoU1", "mIoU2")
 

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 
+_C = _lib.CONSTANTS       # the integer #define DCA_* of include/dca_hip.h
 _vp = ctypes.c_void_p
 
 
@@ -244,7 +245,9 @@ def regression(x):
     return _SoftArgmin.apply(x, 2)
 
 
-CONF_DISP, CONF_DUNI, CONF_MASS, CONF_ENT, CONF_STD, CONF_PLANES = 0, 1, 2, 3, 4, 5     # DCA_CONF_* of include/dca_hip.h
+# planes of `softargmin_stats` (include/dca_hip.h)
+CONF_DISP, CONF_DUNI, CONF_MASS, CONF_ENT, CONF_STD, CONF_PLANES = (
+    _C[f"DCA_CONF_{n}"] for n in ("DISP", "DUNI", "MASS", "ENT", "STD", "PLANES"))
 
 
 def _req_no_grad(name, *tensors):
@@ -348,7 +351,7 @@ _X3_MIN_WORKGROUPS = 1
 # attribute set on an output there is still on what apply() returns -- and only through the four _tag_* setters.  Tensors
 # without a tag get one read pass (dca_cmax_f32).
 AMAX_STATS = {"tagged": 0, "computed": 0, "packed": 0}
-CSLOTS = 1024                                              # DCA_AMAX_CSLOTS of include/dca_hip.h
+CSLOTS = _C["DCA_AMAX_CSLOTS"]
 AMAX_EMIT = os.environ.get("DCA_AMAX_EMIT", "1") != "0"    # 0: no producer-side maxima, every operand gets its read pass (A/B)
 PACK = os.environ.get("DCA_PACK", "1") != "0"              # 0: no packed px2 operands, fp32 tensors everywhere (A/B)
 
@@ -1593,7 +1596,7 @@ def convex_upsample4(mask_logits, disp):
     return _ConvexUp4.apply(mask_logits, disp)
 
 
-CONF_MAX_PLANES = 8      # DCA_CONF_MAX_PLANES
+CONF_MAX_PLANES = _C["DCA_CONF_MAX_PLANES"]
 
 
 def convex_upsample4_planes(mask_logits, planes, scales):
@@ -1673,7 +1676,7 @@ def focal_loss_levels(ests, gt_pooled, weights, focal_coefficient):
 # ------------------------------------------------------------------------------------------------
 # Reduced-precision inference (BASELINE configs 2 / 5): bf16 or fp16 storage, one MFMA product, fp32 accumulation
 # ------------------------------------------------------------------------------------------------
-LP_DTYPES = {torch.bfloat16: 1, torch.float16: 2}      # DCA_BF16 / DCA_FP16 of include/dca_hip.h
+LP_DTYPES = {torch.bfloat16: _C["DCA_BF16"], torch.float16: _C["DCA_FP16"]}
 
 
 def _req_lp(t, name, lp):
@@ -1871,9 +1874,9 @@ def conv3d_c1_lp(x, weight):
 # Evaluation step (main_dca.py:143-246 `mytest`): disparity metrics, region confusion matrices, run state
 # (csrc/eval_metrics.hip; state layout in include/dca_hip.h).  No launch synchronises; all buffers are torch's.
 # ------------------------------------------------------------------------------------------------
-EVAL_REC = 8             # DCA_EVAL_REC
-EVAL_STATE_HEAD = 32     # DCA_EVAL_STATE_HEAD
-EVAL_MAX_CLASSES = 64    # DCA_EVAL_MAX_CLASSES
+EVAL_REC = _C["DCA_EVAL_REC"]
+EVAL_STATE_HEAD = _C["DCA_EVAL_STATE_HEAD"]
+EVAL_MAX_CLASSES = _C["DCA_EVAL_MAX_CLASSES"]
 
 
 def disp_metrics(pred, gt, maxdisp, mask=None):
@@ -1952,8 +1955,8 @@ def eval_accumulate(state, rec, cm, gt_shape):
     return state
 
 
-CONF_MAX_BINS = 1024         # DCA_CONF_MAX_BINS
-CONF_ERR_SCALE = 1048576     # DCA_CONF_ERR_SCALE: the error sums of `conf_histogram` are in units of 2^-20 pixels
+CONF_MAX_BINS = _C["DCA_CONF_MAX_BINS"]
+CONF_ERR_SCALE = _C["DCA_CONF_ERR_SCALE"]     # the error sums of `conf_histogram` are in units of 2^-20 pixels
 
 
 def conf_histogram(conf, pred, gt, state, maxdisp):
@@ -1983,7 +1986,7 @@ def conf_histogram(conf, pred, gt, state, maxdisp):
 # ------------------------------------------------------------------------------------------------
 # Left-right consistency (csrc/lr_consistency.hip): inference only, no counterpart in the reference
 # ------------------------------------------------------------------------------------------------
-LR_MAX_W = 8192              # DCA_LR_MAX_W
+LR_MAX_W = _C["DCA_LR_MAX_W"]
 LR_OUTPUTS = ("diff", "valid", "filled", "disp_right")
 
 

@@ -8,9 +8,13 @@
  * (0 = hipSuccess; invalid arguments -> hipErrorInvalidValue before anything is launched).
  *
  * Tensors are dense fp32 NC[D]HW (the reference's layout).  File:line citations are into the
- * reference tree.  The ctypes binding that mirrors this header lives in
- * cost-volume-aggregation-in-stereo-matching-revisited_amd/_lib.py; INTEGRATION.md shows how the
- * reference's own modules would call it.
+ * reference tree.  The ctypes binding in cost-volume-aggregation-in-stereo-matching-revisited_amd/_lib.py is read
+ * from this header at import; INTEGRATION.md shows how the reference's own modules would call it.
+ *
+ * What that reader relies on:
+ *   - one declaration per `int|long dca_*( ... );`, starting in column 0, every parameter named;
+ *   - a parameter is a pointer, a hipStream_t, or a scalar int, long, float or double (anything else is refused);
+ *   - an integer `#define DCA_* <literal>` is on one line.
  */
 #ifndef DCA_HIP_H
 #define DCA_HIP_H

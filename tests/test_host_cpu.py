@@ -33,6 +33,63 @@ def test_capi_argument_counts_match_header():
         assert len([a for a in m.group(1).split(",") if a.strip() and a.strip() != "void"]) == len(args), name
 
 
+def test_capi_argument_types_are_derived_from_header():
+    """types, not only counts: a swapped int / long or float / double loads and runs, with garbage sizes"""
+    from ctypes import c_double as d, c_float as f, c_int as i, c_long as l, c_void_p as p
+    from dcanet_amd import _lib
+    S = _lib.SIGNATURES
+    assert S["dca_bn_finalize"] == (i, [p, i, d, p, p, p, p, f, f, i, p, p, p, i, p, i, i, p])
+    assert S["dca_train_tables"] == (i, [p, l, p, f, f, p, p, p, p])
+    # const float* const*, const int*, void*, unsigned*, hipStream_t
+    assert S["dca_cost_volume_fwd"] == (i, [p, p, p, i, p, p, i, p, i, i, i, i, i, i, p, p])
+    assert S["dca_eval_state_len"] == (l, [i])
+    assert S["dca_abi_version"] == (i, [])
+    assert _lib.ABI_VERSION == _lib.CONSTANTS["DCA_ABI_VERSION"]
+
+    sigs, consts = _lib.parse_header(
+        "/* int dca_gone(int n); */\n#ifndef DCA_X_H\n#define DCA_X_H\n#define DCA_N 0x10\n#define DCA_M 7  // seven\n"
+        "long dca_y(const long n, const double* q,\n           hipStream_t stream);  /* trailing */\nint dca_z(void);\n")
+    assert sigs == {"dca_y": (l, [l, p, p]), "dca_z": (i, [])} and consts == {"DCA_N": 16, "DCA_M": 7}
+    for bad in ("short n", "unsigned n", "long long n", "hipStream_t"):
+        with pytest.raises(RuntimeError, match="dca_x"):
+            _lib.parse_header(f"int dca_x({bad});")
+    with pytest.raises(RuntimeError):
+        _lib.parse_header("#define DCA_N 3\nvoid helper(int n);\n")
+
+
+def test_every_entry_point_is_defined_against_the_header():
+    """C linkage compares nothing: a definition is checked against its declaration only if its file sees the header"""
+    csrc = os.path.join(ROOT, "cost-volume-aggregation-in-stereo-matching-revisited_amd", "csrc")
+    header = os.path.join(ROOT, "include", "dca_hip.h")
+    declared = set(re.findall(r"^(?:int|long)\s+(dca_\w+)\s*\(", open(header).read(), flags=re.M))
+
+    def closure(path, seen):
+        path = os.path.normpath(path)
+        if path not in seen and os.path.exists(path):
+            seen.add(path)
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), flags=re.M):
+                closure(os.path.join(os.path.dirname(path), inc), seen)
+        return seen
+
+    defined = set()
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith(".hip"):
+            continue
+        here = re.findall(r'^extern "C" (?:int|long) (dca_\w+)', open(os.path.join(csrc, name)).read(), flags=re.M)
+        assert not defined & set(here), (name, defined & set(here))
+        defined |= set(here)
+        if here:
+            assert os.path.normpath(header) in closure(os.path.join(csrc, name), set()), name
+    assert defined == declared, defined ^ declared
+
+    ndef = 0
+    for d in (csrc, os.path.join(ROOT, "include")):
+        for name in os.listdir(d):
+            if name.endswith((".h", ".hip")):
+                ndef += len(re.findall(r"^\s*#\s*define\s+DCA_AMAX_CSLOTS\b", open(os.path.join(d, name)).read(), flags=re.M))
+    assert ndef == 1
+
+
 # Every size query of the C ABI at shapes that are no tile multiples and sit on both sides of each clip (tiles below and
 # above the workgroups the grid rule allows, more channel blocks than CUs, the slot and block caps), on a 256-CU device --
 # also what a query assumes when no device can be asked.  Recorded from the library before the queries and the launchers
