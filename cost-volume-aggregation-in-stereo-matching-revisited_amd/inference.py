@@ -16,7 +16,10 @@ disparity distribution within `radius` bins of its peak, up-sampled with the dis
 
 `KittiInferenceLR` returns the left-right-checked, filled disparity and its validity mask: a second pass on the mirrored,
 swapped frames gives the right view's disparity, one launch cross-checks and fills (nothing in the
-reference computes it)."""
+reference computes it).
+
+`KittiInference3D` adds the geometry stage behind any of the three: metric depth and a coloured point cloud from a
+StereoCalib, filtered by the confidence or the left-right validity."""
 from __future__ import annotations
 
 import collections
@@ -24,6 +27,7 @@ import collections
 import numpy as np
 import torch
 
+from .geometry import depth_png  # noqa: F401  (the depth exporter, next to disparity_png)
 from .graph import GraphedHotPath
 
 
@@ -154,7 +158,8 @@ class KittiInference:
     uint8 pair into pinned memory and the result out of it.  `stream(pairs)` pipelines successive frames.
 
     The subclass `KittiInferenceWithConfidence` hands out `(disp, conf)` per frame (class attribute `confidence`), the
-    subclass `KittiInferenceLR` `(disp_filled, valid)`: a frame's maps come from `_frame_maps`, `nmaps` of them."""
+    subclass `KittiInferenceLR` `(disp_filled, valid)`: a frame's maps come from `_frame_maps`, `nmaps` of them, and go
+    into the slot's output through `_export` (`KittiInference3D` adds its depth map and point cloud there)."""
 
     confidence = False           # True: a confidence map next to every disparity map (KittiInferenceWithConfidence)
     radius = 1                   # its window, in 1/4-res disparity bins either side of the peak
@@ -257,16 +262,21 @@ class KittiInference:
             lut, _ = ops.frame_lut(ops.frame_histogram(left, right), h * w)
             fl, fr = ops.frame_apply(left, right, lut, (self.crop_height, self.crop_width), src_y0, dst_y0, rows, cols,
                                      out=self._frames)
-            maps = self._frame_maps(fl, fr, cols)
-            dev = s.output(as_uint16, len(maps))[0]
-            for k, (m, scale) in enumerate(zip(maps, (256.0, self.CONF_U16_SCALE))):
-                out = dev[k * rows * cols:(k + 1) * rows * cols].view(rows, cols)
-                if as_uint16:
-                    ops.disp_export(m.contiguous(), dst_y0, rows, cols, scale=scale, f32=False, u16=True, out_u16=out)
-                else:
-                    ops.disp_export(m.contiguous(), dst_y0, rows, cols, out_f32=out)
+            self._export(s, self._frame_maps(fl, fr, cols), as_uint16)
             s.computed.record(compute)
         s.as_uint16 = as_uint16
+
+    def _export(self, s, maps, as_uint16):
+        """current stream: the frame's maps, cropped to the image's window, into the slot's device output"""
+        from . import ops
+        dst_y0, rows, cols = s.meta[3][1:]
+        dev = s.output(as_uint16, len(maps))[0]
+        for k, (m, scale) in enumerate(zip(maps, (256.0, self.CONF_U16_SCALE))):
+            out = dev[k * rows * cols:(k + 1) * rows * cols].view(rows, cols)
+            if as_uint16:
+                ops.disp_export(m.contiguous(), dst_y0, rows, cols, scale=scale, f32=False, u16=True, out_u16=out)
+            else:
+                ops.disp_export(m.contiguous(), dst_y0, rows, cols, out_f32=out)
 
     def _readback(self, s, copy):
         """`copy` stream: device output -> pinned"""
@@ -370,6 +380,25 @@ class KittiInferenceWithConfidence(KittiInference):
         self.radius = int(radius)
 
 
+def _check_tau(tau) -> float:
+    tau = float(tau)
+    if not (0.0 <= tau < float("inf")):
+        raise ValueError("tau must be finite and >= 0")
+    return tau
+
+
+@torch.no_grad()
+def _lr_maps(infer, left, right, cols, outputs):
+    """the two passes of the left-right check for `infer` (its `tau`, its `_mirrored` buffer): the left disparity as the
+    network gave it and the maps of `ops.lr_consistency` named in `outputs`"""
+    from . import ops
+    disp = infer.forward_frame(left, right)          # its own tensor: the second replay below does not touch it
+    if infer._mirrored is None or infer._mirrored.shape[1:] != left.shape or infer._mirrored.device != left.device:
+        infer._mirrored = torch.empty((2,) + tuple(left.shape), device=left.device, dtype=torch.float32)
+    disp_m = infer.forward_frame(*ops.mirror_pair(left.contiguous(), right.contiguous(), out=infer._mirrored))
+    return disp, ops.lr_consistency(disp.contiguous(), disp_m.contiguous(), infer.tau, cols, outputs=outputs)
+
+
 class KittiInferenceLR(KittiInference):
     """`disp_filled, valid = KittiInferenceLR(model, ..., tau=1.0)(left_rgb, right_rgb)`: KittiInference with the same
     arguments (host or device I/O, eager or graph, fp32 or reduced precision) whose `__call__` and `stream()` hand out a
@@ -387,21 +416,139 @@ class KittiInferenceLR(KittiInference):
 
     def __init__(self, model, *args, tau: float = 1.0, **kwargs):
         super().__init__(model, *args, **kwargs)
-        tau = float(tau)
-        if not (0.0 <= tau < float("inf")):
-            raise ValueError("tau must be finite and >= 0")
-        self.tau = tau
+        self.tau = _check_tau(tau)
         self._mirrored = None        # (2,1,3,Hc,Wc): the mirrored, swapped frames, rewritten whole by every frame
 
     @torch.no_grad()
     def _frame_maps(self, left, right, cols):
-        from . import ops
-        disp = self.forward_frame(left, right)       # its own tensor: the second replay below does not touch it
-        if self._mirrored is None or self._mirrored.shape[1:] != left.shape or self._mirrored.device != left.device:
-            self._mirrored = torch.empty((2,) + tuple(left.shape), device=left.device, dtype=torch.float32)
-        disp_m = self.forward_frame(*ops.mirror_pair(left.contiguous(), right.contiguous(), out=self._mirrored))
-        r = ops.lr_consistency(disp.contiguous(), disp_m.contiguous(), self.tau, cols, outputs=("valid", "filled"))
+        _, r = _lr_maps(self, left, right, cols, ("valid", "filled"))
         return r["filled"], r["valid"]
+
+
+Frame3D = collections.namedtuple("Frame3D", "disp mask depth vertices")
+
+
+class _Geo:
+    """Per-slot buffers of KittiInference3D, allocated once for the frame size.  `head`: 16 bytes of `count` (2 int64), then
+    the frame's maps back to back (disparity[, mask], depth; float32) -- one copy brings the maps AND the count to the host.
+    `vert`: the vertex records, room for the worst case of the frame."""
+
+    def __init__(self, device, crop_height, crop_width, stride):
+        from . import ops
+        nbytes = 16 + 3 * crop_height * crop_width * 4
+        cap = -(-crop_height // stride) * -(-crop_width // stride)
+        self.head_dev = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        self.head_pin = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        self.vert_dev = torch.empty((cap, 4), device=device, dtype=torch.float32)
+        self.vert_pin = torch.empty((cap, 4), dtype=torch.float32).pin_memory()
+        self.offsets = ops.point_cloud_workspace(crop_height, crop_width, device)[0]
+        self.count = self.head_dev[:16].view(torch.int64)
+        self.head_done = torch.cuda.Event()
+        self.copy = None             # the stream the head went out on: the vertices follow it there
+
+    def maps(self, buf, nmaps, rows, cols):
+        """the views of `nmaps` rows x cols float32 maps in a head buffer"""
+        fl = buf[16:].view(torch.float32)
+        return [fl[k * rows * cols:(k + 1) * rows * cols].view(rows, cols) for k in range(nmaps)]
+
+
+class KittiInference3D(KittiInference):
+    """`disp, mask, depth, vertices = KittiInference3D(model, calib, mask=None | "confidence" | "lr", ...)(left_rgb,
+    right_rgb)`: KittiInference with device I/O (required: the colours are the uint8 left image that already lies in device
+    memory) followed by the geometry stage on the same stream: `ops.disp_to_depth` and
+    `ops.point_cloud` under `calib` (a geometry.StereoCalib of the images as they are handed in), `min_disp`, `max_depth`,
+    `stride` and, with a mask, `mask >= mask_min`.  The disparity and the mask per mode:
+      None          KittiInference's disparity, no mask (`mask` of the result is None)
+      "confidence"  KittiInferenceWithConfidence's disparity and window mass (`radius`)
+      "lr"          the UNFILLED left disparity and the validity map of the cross-check (`tau`; two passes per frame): a
+                    filled pixel is a guess, not a measurement, and must not become a point
+    `depth` is float32 metres, 0 where no point is; `vertices` a geometry.PLY_VERTEX array of exactly the kept pixels in
+    row-major order, in the left camera's frame (`geometry.write_ply` stores it as it is).  All buffers of a frame in
+    flight are allocated once per slot.  The read-back is one copy of the maps with the count in front, then -- once that
+    count is on the host -- one copy of exactly count * 16 bytes of vertices: ONE more host wait per frame than the other
+    classes have, on that frame's own copy only; in `stream()` the later frames keep computing meanwhile."""
+
+    def __init__(self, model, calib, *args, mask=None, mask_min: float = 0.5, min_disp: float = 0.0,
+                 max_depth: float = 80.0, stride: int = 1, radius: int = 1, tau: float = 1.0, **kwargs):
+        from . import ops
+        super().__init__(model, *args, **kwargs)
+        if not self.device_io:
+            raise ValueError("KittiInference3D needs device_io=True: the point colours are read from the uint8 image on the device")
+        if mask not in (None, "confidence", "lr"):
+            raise ValueError(f"mask is None, 'confidence' or 'lr', got {mask!r}")
+        if int(stride) < 1 or int(radius) < 0:
+            raise ValueError("stride >= 1 and radius >= 0")
+        ops._geo_scalars("KittiInference3D", calib, mask_min, min_disp, max_depth)       # the operators' ranges, up front
+        self.calib, self.mask_mode = calib, mask
+        self.filters = dict(mask_min=float(mask_min), min_disp=float(min_disp), max_depth=float(max_depth))
+        self.stride, self.radius, self.tau = int(stride), int(radius), _check_tau(tau)
+        self.confidence = mask == "confidence"
+        self._mirrored = None
+
+    @property
+    def nmaps(self):
+        """the network's maps per frame: the disparity[, the mask]; the depth map follows them in the slot's buffer"""
+        return 1 if self.mask_mode is None else 2
+
+    def _frame_maps(self, left, right, cols):
+        if self.mask_mode == "lr":
+            disp, r = _lr_maps(self, left, right, cols, ("valid",))
+            return disp, r["valid"]
+        return super()._frame_maps(left, right, cols)
+
+    def _geo(self, s):
+        if getattr(s, "geo", None) is None:
+            s.geo = _Geo(s.device, self.crop_height, self.crop_width, self.stride)
+        return s.geo
+
+    def _export(self, s, maps, as_uint16):
+        from . import ops
+        h, w, c, (src_y0, dst_y0, rows, cols), _ = s.meta
+        g = self._geo(s)
+        pred = maps[0].contiguous()
+        mask = maps[1].contiguous() if len(maps) > 1 else None
+        views = g.maps(g.head_dev, len(maps) + 1, rows, cols)
+        for m, out in zip((pred, mask) if mask is not None else (pred,), views):
+            ops.disp_export(m, dst_y0, rows, cols, out_f32=out)
+        window = (dst_y0, rows, cols)
+        ops.disp_to_depth(pred, self.calib, window, mask, out_f32=views[-1], **self.filters)
+        ops.point_cloud(pred, self.calib, s.in_dev[:h * w * c].view(h, w, c), mask, window, v0=src_y0, stride=self.stride,
+                        out=g.vert_dev, workspace=(g.offsets, g.count), **self.filters)
+
+    def _readback(self, s, copy):
+        """`copy` stream: the count and the maps -> pinned, one copy"""
+        rows, cols = s.meta[3][2:]
+        g = self._geo(s)
+        n = 16 + (self.nmaps + 1) * rows * cols * 4
+        with torch.cuda.stream(copy):
+            copy.wait_event(s.computed)
+            g.head_pin[:n].copy_(g.head_dev[:n], non_blocking=True)
+            g.head_done.record(copy)
+        g.copy = copy
+
+    def _result(self, s):
+        """host: wait for the maps and the count, send exactly the written records after them, wait for those"""
+        from .geometry import PLY_VERTEX
+        rows, cols = s.meta[3][2:]
+        g = self._geo(s)
+        g.head_done.synchronize()
+        written = int(g.head_pin[:16].view(torch.int64)[1])
+        with torch.cuda.stream(g.copy):
+            if written:
+                g.vert_pin[:written].copy_(g.vert_dev[:written], non_blocking=True)
+            s.done.record(g.copy)
+        maps = [m.numpy().copy() for m in g.maps(g.head_pin, self.nmaps + 1, rows, cols)]
+        s.done.synchronize()
+        vertices = g.vert_pin[:written].numpy().view(PLY_VERTEX).reshape(-1).copy()
+        return Frame3D(maps[0], maps[1] if self.nmaps == 2 else None, maps[-1], vertices)
+
+    def stream(self, pairs, depth: int = 2):
+        """Generator of Frame3D tuples in input order, `depth` frames in flight, each equal byte for byte to the one-at-a-time
+        call.  The vertex copy of frame i goes onto the copy stream directly behind that frame's maps."""
+        return super().stream(pairs, depth, False)
+
+    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray) -> Frame3D:
+        return self._call_device(left_rgb, right_rgb, False)
 
 
 def confidence_png(path: str, conf: np.ndarray) -> None:

@@ -2264,3 +2264,146 @@ def train_disp_crop(disp, y1, x1, maxdisp, out_gt, out_mask, flip_rows=False, sc
                                       th, tw, int(bool(flip_rows)), float(scale), int(bool(inf_to_zero)), float(maxdisp),
                                       _stream()), "dca_train_disp_crop")
     return out_gt, out_mask
+
+
+# ------------------------------------------------------------------------------------------------
+# Geometry from calibrated disparity (csrc/geometry.hip): metric depth and a compacted, coloured point
+# cloud from the maps the pipeline already holds on the device.  Inference only, no counterpart in the reference.  No launch
+# synchronises; with every buffer passed in nothing is allocated either (hipGraph capture).
+# ------------------------------------------------------------------------------------------------
+PC_TILE = _C["DCA_PC_TILE"]
+PC_RECORD_BYTES = _C["DCA_PC_RECORD_BYTES"]
+GEO_MIN_DISP = 0.0           # default filters: any non-negative disparity ...
+GEO_MAX_DEPTH = 80.0         # ... up to the range the KITTI depth benchmark evaluates (metres)
+
+
+def _geo_frame(name, pred, mask, window):
+    """the (Hc,Wc) / (1,1,Hc,Wc) prediction, the optional mask of its shape and the window (y0, rows, cols), default whole"""
+    _req_no_grad(name, pred, mask)
+    _req_dev(pred, name, "the prediction", torch.float32)
+    if pred.dim() < 2 or pred.numel() == 0 or pred.numel() != pred.shape[-2] * pred.shape[-1]:
+        raise RuntimeError(f"{name}: expected a (Hc,Wc) prediction of one frame, got {tuple(pred.shape)}")
+    if mask is not None:
+        _req_f32_same(name, pred, mask, "the prediction and the mask")
+    Hc, Wc = int(pred.shape[-2]), int(pred.shape[-1])
+    y0, rows, cols = (0, Hc, Wc) if window is None else (int(v) for v in window)
+    if y0 < 0 or rows <= 0 or cols <= 0 or y0 + rows > Hc or cols > Wc or Hc * Wc >= 1 << 31:
+        raise RuntimeError(f"{name}: the {rows} x {cols} window at row {y0} does not fit the {Hc} x {Wc} prediction")
+    return Hc, Wc, y0, rows, cols
+
+
+def _geo_scalars(name, calib, mask_min, min_disp, max_depth):
+    """(f, fb, cx, cy, doffs, min_disp, max_depth, mask_min) as floats, within the ranges of include/dca_hip.h"""
+    try:
+        f, fb, cx, cy, doffs = (float(getattr(calib, k)) for k in ("f", "fb", "cx", "cy", "doffs"))
+    except (AttributeError, TypeError, ValueError) as e:
+        raise RuntimeError(f"{name}: calib must be a geometry.StereoCalib (f, fb, cx, cy, doffs): {e}") from None
+    mask_min, min_disp, max_depth = float(mask_min), float(min_disp), float(max_depth)
+    if not (0.0 < f < math.inf and 0.0 < fb < math.inf and all(math.isfinite(v) for v in (cx, cy, doffs))):
+        raise RuntimeError(f"{name}: the calibration must be finite with f > 0 and f * baseline > 0")
+    if not 0.0 <= min_disp < math.inf:
+        raise RuntimeError(f"{name}: min_disp must be finite and >= 0, got {min_disp}")
+    if not 0.0 < max_depth < math.inf:
+        raise RuntimeError(f"{name}: max_depth must be finite and > 0, got {max_depth}")
+    if math.isnan(mask_min):
+        raise RuntimeError(f"{name}: mask_min must not be NaN")
+    return f, fb, cx, cy, doffs, min_disp, max_depth, mask_min
+
+
+def disp_to_depth(pred, calib, window=None, mask=None, mask_min=0.5, min_disp=GEO_MIN_DISP, max_depth=GEO_MAX_DEPTH,
+                  f32=True, u16=False, scale=256.0, out_f32=None, out_u16=None):
+    """Dense metric depth of the window (y0, rows, cols) of a disparity map (Hc,Wc) / (1,1,Hc,Wc), one launch:
+    Z = calib.fb / (d + calib.doffs) where d >= min_disp, 0 < Z <= max_depth and (mask is None or mask >= mask_min),
+    +0.0 elsewhere (the KITTI depth convention; definitions: include/dca_hip.h).  mask: float32, shaped like pred.
+    Returns (float32 (rows,cols) or None, uint16 (rows,cols) = trunc(Z * scale) saturated, or None); out_f32 / out_u16:
+    buffers of that shape to write into."""
+    Hc, Wc, y0, rows, cols = _geo_frame("disp_to_depth", pred, mask, window)
+    f, fb, cx, cy, doffs, min_disp, max_depth, mask_min = _geo_scalars("disp_to_depth", calib, mask_min, min_disp, max_depth)
+    if not (f32 or u16):
+        raise RuntimeError("disp_to_depth: nothing to compute (f32 and u16 are both off)")
+    if u16 and not 0.0 < float(scale) < math.inf:
+        raise RuntimeError(f"disp_to_depth: scale must be finite and > 0, got {scale}")
+    of = ou = None
+    if f32:
+        of = torch.empty((rows, cols), device=pred.device, dtype=torch.float32) if out_f32 is None else \
+            _req_dev(out_f32, "disp_to_depth", "out_f32", torch.float32, (rows, cols))
+    if u16:
+        ou = torch.empty((rows, cols), device=pred.device, dtype=torch.uint16) if out_u16 is None else \
+            _req_dev(out_u16, "disp_to_depth", "out_u16", torch.uint16, (rows, cols))
+    with torch.cuda.device_of(pred):
+        _chk(_L().dca_disp_to_depth(_ptr(pred), _ptr(mask), _ptr(of), _ptr(ou), Hc, Wc, y0, rows, cols, fb, doffs, min_disp,
+                                    max_depth, mask_min, float(scale), _stream()), "dca_disp_to_depth")
+    return of, ou
+
+
+def point_cloud_tiles(rows, cols):
+    """workgroups of the compaction of a rows x cols window: ceil(rows * cols / PC_TILE)"""
+    tiles = int(_L().dca_point_cloud_tiles(int(rows), int(cols)))
+    if tiles <= 0:
+        raise RuntimeError(f"point_cloud: a {rows} x {cols} window is empty or has 2^31 pixels or more")
+    return tiles
+
+
+def point_cloud_workspace(rows, cols, device):
+    """(tile_offsets int32 (tiles + 1,), count int64 (2,)) for `point_cloud(..., workspace=)` on windows up to rows x cols"""
+    return (torch.empty(point_cloud_tiles(rows, cols) + 1, device=device, dtype=torch.int32),
+            torch.empty(2, device=device, dtype=torch.int64))
+
+
+def point_cloud(pred, calib, rgb=None, mask=None, window=None, v0=0, stride=1, cap=None, out=None, workspace=None,
+                mask_min=0.5, min_disp=GEO_MIN_DISP, max_depth=GEO_MAX_DEPTH):
+    """The kept pixels of the window (y0, rows, cols) of a disparity map (Hc,Wc) / (1,1,Hc,Wc) as a compacted point cloud in
+    the left camera's frame, in row-major window order, three launches and no atomics: bitwise reproducible, order included
+    (definitions: include/dca_hip.h, dca_point_cloud).  A pixel (r, c) is kept under the filters of `disp_to_depth` and
+    r % stride == c % stride == 0; its image coordinates are (u, v) = (c, v0 + r).  rgb: the (H,W,3) / (H,W,4) uint8 source
+    image, read at (v0 + r, c); None: white.  mask: float32, shaped like pred.
+    Returns (vertices, count, tile_offsets):
+      vertices      (cap,4) float32: x, y, z and the colour bytes r, g, b, 255 in the fourth column -- 16-byte records, the
+                    body of a binary PLY file (`geometry.write_ply`); only the first count[1] rows are written
+      count         (2,) int64 on the device: kept pixels, records written = min(kept, cap)
+      tile_offsets  (tiles + 1,) int32 on the device: kept pixels before every tile of PC_TILE window pixels, then the total
+    cap: room in vertices, default the worst case ceil(rows / stride) * ceil(cols / stride), or out's.  out: a (cap,4)
+    float32 buffer; workspace: `point_cloud_workspace(...)` of a window at least this large.  With both given nothing is
+    allocated and the host never waits: the launches can be captured into a hipGraph."""
+    name = "point_cloud"
+    Hc, Wc, y0, rows, cols = _geo_frame(name, pred, mask, window)
+    f, fb, cx, cy, doffs, min_disp, max_depth, mask_min = _geo_scalars(name, calib, mask_min, min_disp, max_depth)
+    v0, stride = int(v0), int(stride)
+    if stride < 1 or v0 < 0:
+        raise RuntimeError(f"{name}: stride >= 1 and v0 >= 0, got stride {stride} and v0 {v0}")
+    C = Hs = Ws = 0
+    if rgb is not None:
+        _req_dev(rgb, name, "rgb", torch.uint8)
+        if rgb.dim() != 3 or rgb.shape[2] not in (3, 4) or rgb.device != pred.device or rgb.shape[0] * rgb.shape[1] >= 1 << 31:
+            raise RuntimeError(f"{name}: rgb must be a (H,W,3) or (H,W,4) uint8 image on the prediction's device, got "
+                               f"{tuple(rgb.shape)}")
+        Hs, Ws, C = (int(s) for s in rgb.shape)
+        if v0 + rows > Hs or cols > Ws:
+            raise RuntimeError(f"{name}: the {rows} x {cols} window at image row {v0} does not fit the {Hs} x {Ws} image")
+    tiles = point_cloud_tiles(rows, cols)
+    if out is not None:
+        _req_dev(out, name, "out", torch.float32)
+        if out.dim() != 2 or out.shape[1] != 4 or out.device != pred.device or out.data_ptr() % PC_RECORD_BYTES:
+            raise RuntimeError(f"{name}: out must be a 16-byte aligned (cap,4) float32 buffer on the prediction's device, got "
+                               f"{tuple(out.shape)}")
+        if cap is not None and int(cap) > out.shape[0]:
+            raise RuntimeError(f"{name}: cap {cap} exceeds the {out.shape[0]} records of out")
+    if cap is None:
+        cap = out.shape[0] if out is not None else -(-rows // stride) * -(-cols // stride)
+    cap = int(cap)
+    if cap < 0:
+        raise RuntimeError(f"{name}: cap >= 0, got {cap}")
+    if out is None:
+        out = torch.empty((cap, 4), device=pred.device, dtype=torch.float32)
+    if workspace is None:
+        workspace = point_cloud_workspace(rows, cols, pred.device)
+    offs, count = workspace
+    _req_dev(offs, name, "workspace[0] (tile_offsets)", torch.int32)
+    _req_dev(count, name, "workspace[1] (count)", torch.int64, (2,))
+    if offs.dim() != 1 or offs.numel() < tiles + 1 or offs.device != pred.device or count.device != pred.device:
+        raise RuntimeError(f"{name}: workspace[0] must hold {tiles + 1} int32 on the prediction's device, got {tuple(offs.shape)}")
+    with torch.cuda.device_of(pred):
+        _chk(_L().dca_point_cloud(_ptr(pred), _ptr(mask), _ptr(rgb), C, Hs, Ws, _ptr(out) if cap else None, cap, _ptr(offs),
+                                  _ptr(count), Hc, Wc, y0, rows, cols, v0, stride, f, fb, cx, cy, doffs, min_disp, max_depth,
+                                  mask_min, _stream()), "dca_point_cloud")
+    return out[:cap], count, offs[:tiles + 1]

@@ -605,6 +605,49 @@ int dca_mirror_pair(const float* left, const float* right, float* out_left, floa
 int dca_lr_consistency(const float* dl, const float* drm, float* diff, float* valid, float* filled, float* disp_right,
                        int B, int H, int W, int cols, float tau, hipStream_t stream);
 
+/* ---- geometry from calibrated disparity (geometry.hip); inference only, no backward, no counterpart in the reference -------
+ * All functions work on ONE frame.  pred (Hc,Wc) fp32: the disparity; the window is rows x cols pixels starting at frame
+ * row y0, column 0, as in dca_disp_export; mask (Hc,Wc) fp32 or NULL, indexed like pred (a confidence, a validity map).
+ * Window pixel (r, c), i = r cols + c, has the image coordinates u = c, v = v0 + r (v0: the image row of window row 0 --
+ * src_y0 of the placement for a cropped image).  With the calibration f (focal length, pixels), fb = float(f * baseline)
+ * rounded once from fp64 by the host, the principal point (cx, cy) and doffs = cx_right - cx_left (0 for KITTI), in fp32,
+ * every operation rounded on its own, IEEE division:
+ *   den = d + doffs;   Z = fb / den;   X = ((float(u) - cx) * Z) / f;   Y = ((float(v) - cy) * Z) / f
+ *   keep = d >= min_disp && den > 0 && Z > 0 && Z <= max_depth && (mask == NULL || mask >= mask_min)
+ *          && r % stride == 0 && c % stride == 0
+ * A NaN fails every comparison: NaN, +-inf and non-positive-denominator disparities are never kept.  Refused: a window
+ * outside the frame, fb or f not positive and finite, min_disp < 0 or not finite, max_depth <= 0 or not finite, stride < 1,
+ * cx, cy or doffs not finite, a NaN mask_min with a mask.
+ *
+ * dca_disp_to_depth: ONE launch -> the dense rows x cols depth map, Z where keep holds (stride 1), +0.0 elsewhere (the
+ * KITTI depth convention), as fp32 and / or uint16(Z * scale) (fp32 product, truncated toward zero, saturated to
+ * [0, 65535]; scale 256: the KITTI depth PNG; scale > 0, finite).  Either output may be NULL, not both.
+ *
+ * dca_point_cloud_tiles: ceil(rows cols / DCA_PC_TILE), the workgroups of the compaction; rows cols < 2^31 (0 otherwise).
+ *
+ * dca_point_cloud: the kept pixels as 16-byte records { float x, y, z; unsigned char r, g, b, a } -- the body of a binary
+ * little-endian PLY file byte for byte -- compacted in row-major window order: record k is the k-th kept pixel by i.
+ * rgb: the source image (Hsrc,Wsrc,C) interleaved uint8, C = 3 or 4, read at (v0 + r, c), or NULL: r = g = b = 255; a = 255
+ * always.  vertices: room for cap records, 16-byte aligned (one 16-byte store per record); nothing is written at or
+ * beyond record cap; cap = 0 is legal and vertices may then be NULL.  tile_offsets: tiles + 1 words of workspace AND
+ * result: tile_offsets[t] = kept pixels with i < t DCA_PC_TILE, tile_offsets[tiles] = the total.  count: 2 words,
+ * count[0] = total kept, count[1] = min(total, cap) = records written.
+ * Three launches on the stream -- count per tile (wave ballots), exclusive scan of the tile counts by ONE workgroup,
+ * rank and write per tile -- with the kernel boundaries as the only global synchronisation: no atomics, no flag one
+ * workgroup polls for another, so the records and their order are bitwise reproducible and nothing can wait on a
+ * workgroup that is not resident.  The window must also fit the source when rgb is given (v0 + rows <= Hsrc,
+ * cols <= Wsrc). */
+#define DCA_PC_TILE 1024
+#define DCA_PC_RECORD_BYTES 16
+int dca_disp_to_depth(const float* pred, const float* mask, float* out_f32, unsigned short* out_u16, int Hc, int Wc, int y0,
+                      int rows, int cols, float fb, float doffs, float min_disp, float max_depth, float mask_min,
+                      float scale, hipStream_t stream);
+long dca_point_cloud_tiles(int rows, int cols);
+int dca_point_cloud(const float* pred, const float* mask, const unsigned char* rgb, int C, int Hsrc, int Wsrc, void* vertices,
+                    long cap, unsigned* tile_offsets, long long* count, int Hc, int Wc, int y0, int rows, int cols, int v0,
+                    int stride, float f, float fb, float cx, float cy, float doffs, float min_disp, float max_depth,
+                    float mask_min, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
