@@ -58,8 +58,9 @@ template <> struct Out<_Float16> {
   }
 };
 
-// requires W % 4 == 0, D % 4 == 0, 16-byte aligned feature maps and volume
-template <int CPG, typename OT>
+// requires W % 4 == 0, 16-byte aligned feature maps and volume, and D % 4 == 0 unless TAIL: then the last disparity quad
+// may be partial (its own instantiation, so that the aligned kernel's code stays what it was)
+template <int CPG, typename OT, bool TAIL>
 __global__ __launch_bounds__(256) void gwc_fused_kernel(VolArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int W = a.W, D = a.D, PAD = (D + 3) & ~3, RW = W + PAD;
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(256) void gwc_fused_kernel(VolArgs a) {
   }
   __syncthreads();
   const float inv = 1.0f / (float)CPG;
-  const int DQ = D >> 2, rows = 256 / WQ > 0 ? 256 / WQ : 1;   // disparity quads handled concurrently
+  const int DQ = TAIL ? (D + 3) >> 2 : D >> 2, rows = 256 / WQ > 0 ? 256 / WQ : 1;   // disparity quads handled concurrently
   const int xq = tid % WQ, iq0 = tid / WQ;
   const bool idle = tid >= rows * WQ && WQ <= 256;
   OT* vbase = (OT*)a.vol + (((long)b * a.Gtot + g) * D) * HW + (long)y * W;
@@ -117,9 +118,11 @@ __global__ __launch_bounds__(256) void gwc_fused_kernel(VolArgs a) {
       }
 #pragma unroll
       for (int di = 0; di < 4; ++di) {
-        const float v[4] = {o[di][0] * inv, o[di][1] * inv, o[di][2] * inv, o[di][3] * inv};
-        vm = fmaxf(fmaxf(vm, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
-        Out<OT>::store4(vbase + (long)(i0 + di) * HW + x0, v);
+        if (!TAIL || i0 + di < D) {    // D % 4 != 0: the rest of the last quad lies outside the volume
+          const float v[4] = {o[di][0] * inv, o[di][1] * inv, o[di][2] * inv, o[di][3] * inv};
+          vm = fmaxf(fmaxf(vm, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+          Out<OT>::store4(vbase + (long)(i0 + di) * HW + x0, v);
+        }
       }
     }
   }
@@ -155,17 +158,25 @@ __global__ __launch_bounds__(256) void concat_fused_kernel(VolArgs a) {
   }
 }
 
-template <int CPG, typename OT>
-int launch_gwc(const VolArgs& a, hipStream_t s) {
+template <int CPG, typename OT, bool TAIL>
+int launch_gwc_tail(const VolArgs& a, hipStream_t s) {
   const int PAD = (a.D + 3) & ~3;
   const size_t lds = (size_t)CPG * (2 * a.W + PAD) * 4;
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
   if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)gwc_fused_kernel<CPG, OT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)gwc_fused_kernel<CPG, OT, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
-  hipLaunchKernelGGL((gwc_fused_kernel<CPG, OT>), dim3(a.H, a.G, a.B), dim3(256), lds, s, a);
+  hipLaunchKernelGGL((gwc_fused_kernel<CPG, OT, TAIL>), dim3(a.H, a.G, a.B), dim3(256), lds, s, a);
   return dca_launch_status();
+}
+
+// D % 4 != 0 is served for the 2-byte volumes only (the fp32 volume of such a D is built by volume.hip)
+template <int CPG, typename OT>
+int launch_gwc(const VolArgs& a, hipStream_t s) {
+  if (a.D % 4 == 0) return launch_gwc_tail<CPG, OT, false>(a, s);
+  if constexpr (sizeof(OT) == 2) return launch_gwc_tail<CPG, OT, true>(a, s);
+  return (int)hipErrorInvalidValue;
 }
 
 template <typename OT>
@@ -196,7 +207,7 @@ extern "C" int dca_cost_volume_fwd(const float* const* refs, const float* const*
   DCA_REQUIRE(B > 0 && H > 0 && W > 0 && maxdisp > 0 && num_groups > 0 && Cc >= 0);
   DCA_REQUIRE((Cc == 0) == (cref == nullptr) && (Cc == 0) == (ctgt == nullptr));
   DCA_REQUIRE(dtype == 0 || dtype == DCA_BF16 || dtype == DCA_FP16);
-  DCA_REQUIRE(W % 4 == 0 && maxdisp % 4 == 0 && H <= 65535 && num_groups <= 65535 && B <= 65535);
+  DCA_REQUIRE(W % 4 == 0 && (maxdisp % 4 == 0 || dtype != 0) && H <= 65535 && num_groups <= 65535 && B <= 65535);
   VolArgs a;
   a.C = 0;
   for (int i = 0; i < 3; ++i) {

@@ -178,17 +178,18 @@ class _CostVolume(torch.autograd.Function):
 def cost_volume(ref, tgt, maxdisp, num_groups, cref=None, ctgt=None, out_dtype=torch.float32):
     """build_gwc_volume(ref, tgt) [cat build_concat_volume(cref, ctgt)] as ONE (B, G + 2*Cc, D, H, W) tensor.  `ref` /
     `tgt` may be tuples of channel segments (the extractor's l2 / l3 / l4 maps) that are read in place.  Falls back to
-    the separate builders + torch.cat when the fused kernel's alignment needs (W % 4, D % 4) are not met."""
+    the separate builders + torch.cat when W % 4 != 0, and for the fp32 volume also when D % 4 != 0 (the fused kernel takes
+    any D; the fp32 routing is left as it was).  The reduced-precision volume has the fused builder only: any D, W % 4 == 0."""
     refs = tuple(ref) if isinstance(ref, (tuple, list)) else (ref,)
     tgts = tuple(tgt) if isinstance(tgt, (tuple, list)) else (tgt,)
     W = refs[0].shape[-1]
     C = sum(t.shape[1] for t in refs)
     cpg = C // num_groups if num_groups else 0
-    ok = (W % 4 == 0 and maxdisp % 4 == 0 and len(refs) <= 3 and cpg in (1, 2, 4, 8, 16) and C % num_groups == 0
-          and all(t.shape[1] % cpg == 0 for t in refs))
+    ok = (W % 4 == 0 and (maxdisp % 4 == 0 or out_dtype != torch.float32) and len(refs) <= 3 and cpg in (1, 2, 4, 8, 16)
+          and C % num_groups == 0 and all(t.shape[1] % cpg == 0 for t in refs))
     if not ok:
         if out_dtype != torch.float32:
-            raise RuntimeError("cost_volume: the reduced-precision volume needs W % 4 == 0 and maxdisp % 4 == 0")
+            raise RuntimeError("cost_volume: the reduced-precision volume needs W % 4 == 0")
         r1 = refs[0] if len(refs) == 1 else torch.cat(refs, 1)
         t1 = tgts[0] if len(tgts) == 1 else torch.cat(tgts, 1)
         vol = gwc_volume(r1, t1, maxdisp, num_groups)

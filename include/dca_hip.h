@@ -53,8 +53,9 @@ int dca_concat_volume_bwd(const float* gvol, float* gref, float* gtgt, int B, in
  * -- from `nseg` (1..3) channel segments of the correlation features: refs[s], tgts[s]: (B, seg_channels[s], H, W), read
  * in place instead of their concatenation gwc_feature = torch.cat((l2, l3, l4), 1) (gwcnet_dca_g.py:60).  refs / tgts /
  * seg_channels are HOST arrays.  cref, ctgt: (B, Cc, H, W) or NULL.  dtype: 0 = fp32 volume, DCA_BF16 / DCA_FP16 = the
- * reduced-precision inference path's storage type.  W % 4 == 0, maxdisp % 4 == 0, 16-byte aligned tensors; every
- * segment width must be a multiple of channels / num_groups. */
+ * reduced-precision inference path's storage type.  W % 4 == 0, 16-byte aligned tensors; every segment width must be a
+ * multiple of channels / num_groups.  maxdisp % 4 == 0 for the fp32 volume; any maxdisp for the 2-byte volumes (the
+ * disparities are walked four at a time and the last quad may be partial). */
 int dca_cost_volume_fwd(const float* const* refs, const float* const* tgts, const int* seg_channels, int nseg,
                         const float* cref, const float* ctgt, int Cc, void* vol, int B, int H, int W, int maxdisp,
                         int num_groups, int dtype, unsigned* vmax, hipStream_t stream);

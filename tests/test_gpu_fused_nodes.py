@@ -14,6 +14,7 @@ Every reference is a float64 PyTorch graph on the CPU in which the shared tensor
 by autograd.  Every case asserts the kernel route it is on (the eligibility predicates of ops.py, the gradient object a
 _GradProbe / a spy on ops._conv_sliced sees, the autograd node that built the result) before it compares, and prints its
 measured errors."""
+import ctypes
 import functools
 import itertools
 
@@ -577,7 +578,10 @@ def test_cost_volume_fused_reduced_precision(name, lp, monkeypatch):
 
 @pytest.mark.parametrize("name", list(VOL_FALLBACK))
 def test_cost_volume_fallback(name, monkeypatch):
-    """W % 4 != 0 or D % 4 != 0: the separate builders, same bounds; the reduced-precision request raises before any launch"""
+    """W % 4 != 0 or D % 4 != 0: the separate builders, same bounds.  The reduced-precision request raises before any
+    launch at W % 4 != 0; at D % 4 != 0 alone it is served by the fused builder (partial last disparity quad): fp64 on the
+    same features at the gwc bound plus the rounding of the store, the concat part and the zero half-plane exact, and
+    nothing written outside the volume"""
     ops = _ops()
     _family(monkeypatch, ops, "f16x2")
     segC, G, Cc, D, H, W, B = VOL_FALLBACK[name]
@@ -585,6 +589,33 @@ def test_cost_volume_fallback(name, monkeypatch):
     vol, leaves = _vol_run(ops, ref, G, D)
     assert type(vol.grad_fn).__name__ != "_CostVolumeBackward", "expected the fallback"
     _vol_check(vol, leaves, ref, G, Cc, D, len(segC))
+    if W % 4 == 0:
+        assert D % 4
+        want = ref["vol"]
+        for lp, half_ulp in ((torch.bfloat16, 2.0 ** -8), (torch.float16, 2.0 ** -11)):
+            vlp, srcs = _vol_run(ops, ref, G, D, out_dtype=lp)
+            assert type(vlp.grad_fn).__name__ == "_CostVolumeBackward" and vlp.dtype == lp and vlp.shape == want.shape
+            got = vlp.detach().cpu().double()
+            err = (got - want).abs()
+            assert (err <= 2e-6 * max(1.0, want.abs().max().item()) + half_ulp * want.abs()).all(), err.max().item()
+            if Cc:
+                assert torch.equal(got[:, G:], want[:, G:].to(lp).double()), "concat part"
+            for d in range(1, D):
+                assert not bool(got[:, :, d, :, :min(d, W)].any()), f"x < d must be exactly 0 (d = {d})"
+            # the C entry on a volume inside a sentinel-filled buffer (-1024 is exact in both types)
+            n, pad = want.numel(), 4096
+            big = torch.full((n + 2 * pad,), -1024.0, device=DEV, dtype=lp)
+            nseg = len(segC)
+            feats = [t.detach() for t in srcs]
+            rp = (ctypes.c_void_p * nseg)(*[t.data_ptr() for t in feats[:nseg]])
+            tp = (ctypes.c_void_p * nseg)(*[t.data_ptr() for t in feats[nseg:2 * nseg]])
+            sc = (ctypes.c_int * nseg)(*segC)
+            cl, cr = (feats[2 * nseg], feats[2 * nseg + 1]) if Cc else (None, None)
+            ops._chk(ops._L().dca_cost_volume_fwd(rp, tp, sc, nseg, ops._ptr(cl), ops._ptr(cr), Cc, ops._ptr(big[pad:pad + n]),
+                                                  B, H, W, D, G, ops.LP_DTYPES[lp], None, ops._stream()), "dca_cost_volume_fwd")
+            assert torch.equal(big[pad:pad + n].view(want.shape), vlp.detach()), "direct C-ABI call differs from the op"
+            assert bool((big[:pad] == -1024.0).all()) and bool((big[pad + n:] == -1024.0).all()), "wrote outside the volume"
+        return
 
     def no_launch():
         raise AssertionError("a kernel launch was attempted")

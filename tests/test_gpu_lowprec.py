@@ -3,6 +3,8 @@ bf16 / fp16 storage, one MFMA product per multiply, fp32 accumulation.  Kernel-l
 evaluation of the SAME rounded operands (products of 2-byte operands are exact in fp32, so only the summation order and
 the final rounding to the storage type differ); the end-to-end gate is SURVEY 8(d)'s |EPE_build - EPE_ref| <= 1e-3
 against a common ground truth, with the mean-abs deviation from the fp32 oracle reported."""
+import zlib
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -16,6 +18,12 @@ LPS = [torch.bfloat16, torch.float16]
 
 def ulp(dtype):
     return 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
+
+
+def _seeded_affine(tag, C):
+    """per-channel scale ~ U(0.5, 1.5) and shift ~ N(0, 0.1), the same numbers in every run"""
+    g = torch.Generator().manual_seed(zlib.crc32(tag.encode()))
+    return torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.1
 
 
 CASES = [  # N, Cin, Cout, (D,H,W), in_f32, out_f32, affine, slope, pre, post
@@ -39,8 +47,7 @@ def test_conv3d_lp(case, lp):
     x = seeded_tensor(f"lp.x{case}", (N, Cin) + dims)
     w = seeded_tensor(f"lp.w{case}", (Cout, Cin, 3, 3, 3)) * (2.0 / (27 * Cin)) ** 0.5
     odt = torch.float32 if out32 else lp
-    scale = (torch.rand(Cout) + 0.5) if aff else None
-    shift = torch.randn(Cout) * 0.1 if aff else None
+    scale, shift = _seeded_affine(f"lp.a{case}", Cout) if aff else (None, None)
     rp = seeded_tensor(f"lp.p{case}", (N, Cout) + dims).to(odt) if pre else None
     rq = seeded_tensor(f"lp.q{case}", (N, Cout) + dims).to(odt) if post else None
     xin = x if in32 else x.to(lp)
@@ -79,8 +86,7 @@ def test_conv1x1_lp(case, lp):
     x2 = seeded_tensor(f"lp1.y{case}", (N, C2) + dims).to(lp) if C2 else None
     w = seeded_tensor(f"lp1.w{case}", (Cout, C1 + C2, 1, 1, 1)) * (2.0 / (C1 + C2)) ** 0.5
     odt = torch.float32 if out32 else lp
-    scale = (torch.rand(Cout) + 0.5) if aff else None
-    shift = torch.randn(Cout) * 0.1 if aff else None
+    scale, shift = _seeded_affine(f"lp1.a{case}", Cout) if aff else (None, None)
     rp = seeded_tensor(f"lp1.p{case}", (N, Cout) + dims).to(odt) if pre else None
     rq = seeded_tensor(f"lp1.q{case}", (N, Cout) + dims).to(odt) if post else None
     xin = x if x2 is None else torch.cat([x, x2], 1)
@@ -120,8 +126,7 @@ def test_deconv3d_lp(case, lp, exact):
     odims = tuple(2 * d for d in dims)
     x = seeded_tensor(f"dc.x{case}", (N, Cin) + dims)
     w = seeded_tensor(f"dc.w{case}", (Cin, Cout, 3, 3, 3)) * (2.0 / (27 * Cin / 8)) ** 0.5
-    scale = (torch.rand(Cout) + 0.5) if aff else None
-    shift = torch.randn(Cout) * 0.1 if aff else None
+    scale, shift = _seeded_affine(f"dc.a{case}", Cout) if aff else (None, None)
     rp = seeded_tensor(f"dc.p{case}", (N, Cout) + odims).to(lp) if pre else None
     rq = seeded_tensor(f"dc.q{case}", (N, Cout) + odims).to(lp) if post else None
     xr, wr = (x.double(), w.double()) if exact else (x.to(lp).double(), w.to(lp).double())
@@ -158,8 +163,7 @@ def test_conv3d_s2_lp(case, lp, exact):
     N, Cin, Cout, dims, aff, slope = case
     x = seeded_tensor(f"s2.x{case}", (N, Cin) + dims).to(lp)
     w = seeded_tensor(f"s2.w{case}", (Cout, Cin, 3, 3, 3)) * (2.0 / (27 * Cin)) ** 0.5
-    scale = (torch.rand(Cout) + 0.5) if aff else None
-    shift = torch.randn(Cout) * 0.1 if aff else None
+    scale, shift = _seeded_affine(f"s2.a{case}", Cout) if aff else (None, None)
     ref = F.conv3d(x.double(), (w if exact else w.to(lp)).double(), None, 2, 1)
     if aff:
         ref = ref * scale.double().view(1, -1, 1, 1, 1) + shift.double().view(1, -1, 1, 1, 1)
@@ -170,6 +174,124 @@ def test_conv3d_s2_lp(case, lp, exact):
     assert got.dtype == torch.float32 and got.shape == ref.shape
     err = (got.double().cpu() - ref).abs().max().item()
     assert err <= 2e-5 * max(1.0, ref.abs().max().item()), f"max err {err:.3e}"
+
+
+SENTINEL, PAD = -1024.0, 4096        # exact in bf16 and fp16
+
+
+def _inside_sentinels(numel, dtype):
+    """(buffer, view of `numel` elements in its middle): PAD sentinel elements on either side of the view"""
+    big = torch.full((numel + 2 * PAD,), SENTINEL, device=DEV, dtype=dtype)
+    return big, big[PAD:PAD + numel]
+
+
+def _sentinels_intact(big, numel):
+    return bool((big[:PAD] == SENTINEL).all()) and bool((big[PAD + numel:] == SENTINEL).all())
+
+
+POOL_CASES = [  # NC, (D, H, W)
+    (3, (1, 1, 4)),         # a single pair; every row but one is padding
+    (6, (5, 7, 8)),         # odd D and H
+    (2, (4, 9, 260)),       # 65 pairs: a second, partial block in x; Ho = 5: a partial block in y
+    (64, (3, 2, 12)),
+]
+
+
+@pytest.mark.parametrize("lp", LPS, ids=["bf16", "fp16"])
+@pytest.mark.parametrize("case", POOL_CASES, ids=str)
+def test_avg_pool3d_lp(case, lp):
+    """AvgPool3d(3, 2, 1) of a 2-byte tensor (csrc/lp_glue.hip) against fp64 on the same values, at the gate of
+    test_avgpool; the C entry writes nothing outside its output"""
+    from dcanet_amd import ops
+    NC, dims = case
+    x = seeded_tensor(f"lpp.x{case}", (1, NC) + dims).to(lp)
+    # F.avg_pool3d(x, 3, 2, 1) with its zero padding written out: PyTorch refuses an input smaller than the window
+    ref = F.avg_pool3d(F.pad(x.double(), (1, 1, 1, 1, 1, 1)), 3, 2, 0)
+    xg = x.to(DEV)
+    got = ops.avg_pool3d_lp(xg)
+    assert got.dtype == torch.float32 and got.shape == ref.shape
+    err = (got.double().cpu() - ref).abs().max().item()
+    assert err <= 1e-6 * max(1.0, ref.abs().max().item()), f"max err {err:.3e}"
+    big, yv = _inside_sentinels(ref.numel(), torch.float32)
+    ops._chk(ops._L().dca_avgpool3d_lp_fwd(ops._ptr(xg), ops._ptr(yv), NC, dims[0], dims[1], dims[2], ops.LP_DTYPES[lp],
+                                           ops._stream()), "dca_avgpool3d_lp_fwd")
+    assert torch.equal(yv.view(ref.shape), got), "direct C-ABI call differs from the op"
+    assert _sentinels_intact(big, ref.numel()), "wrote outside y"
+
+
+@pytest.mark.parametrize("lp", LPS, ids=["bf16", "fp16"])
+def test_avg_pool3d_lp_refuses_a_width_off_the_quad_grid(lp):
+    """W = 6: the kernel reads aligned quads, so the C entry returns an error before any launch"""
+    from dcanet_amd import ops
+    x = seeded_tensor("lpp.x6", (1, 3, 2, 2, 6)).to(lp).to(DEV)
+    with pytest.raises(RuntimeError, match="dca_avgpool3d_lp_fwd"):
+        ops.avg_pool3d_lp(x)
+    big, yv = _inside_sentinels(3 * 1 * 1 * 3, torch.float32)
+    rc = ops._L().dca_avgpool3d_lp_fwd(ops._ptr(x), ops._ptr(yv), 3, 2, 2, 6, ops.LP_DTYPES[lp], ops._stream())
+    torch.cuda.synchronize()
+    assert rc != 0 and bool((big == SENTINEL).all()), rc
+
+
+UP_CASES = [  # NC, (D, H, W)
+    (2, (1, 1, 1)),         # every index clamped at both ends
+    (3, (2, 3, 5)),
+    (2, (3, 5, 65)),        # a second block in x and in y
+    (64, (2, 2, 3)),
+]
+
+
+@pytest.mark.parametrize("lp", LPS, ids=["bf16", "fp16"])
+@pytest.mark.parametrize("case", UP_CASES, ids=str)
+def test_trilinear_up2_lp(case, lp):
+    """x2 trilinear up-sampling stored in the 2-byte type (csrc/lp_glue.hip) against fp64, at the gate of test_trilinear
+    plus the rounding of the store; the C entry writes nothing outside its output"""
+    from dcanet_amd import ops
+    NC, dims = case
+    x = seeded_tensor(f"lpu.x{case}", (1, NC) + dims)
+    ref = F.interpolate(x.double(), scale_factor=2, mode="trilinear")
+    xg = x.to(DEV)
+    got = ops.trilinear_up2_lp(xg, lp)
+    assert got.dtype == lp and got.shape == ref.shape
+    err = (got.double().cpu() - ref).abs()
+    lim = 2e-6 * max(1.0, ref.abs().max().item()) + ulp(lp) * ref.abs()
+    assert (err <= lim).all(), f"max err {err.max().item():.3e} at |ref| {ref.abs().flatten()[err.argmax()].item():.3e}"
+    big, yv = _inside_sentinels(ref.numel(), lp)
+    ops._chk(ops._L().dca_trilinear_up2_lp_fwd(ops._ptr(xg), ops._ptr(yv), NC, dims[0], dims[1], dims[2], ops.LP_DTYPES[lp],
+                                               ops._stream()), "dca_trilinear_up2_lp_fwd")
+    assert torch.equal(yv.view(ref.shape), got), "direct C-ABI call differs from the op"
+    assert _sentinels_intact(big, ref.numel()), "wrote outside y"
+
+
+HEAD_CASES = [  # N, C, (D, H, W)
+    (1, 32, (1, 1, 4)),
+    (2, 32, (3, 5, 8)),
+    (1, 32, (4, 6, 12)),
+    (1, 64, (2, 3, 4)),
+]
+
+
+@pytest.mark.parametrize("lp", LPS, ids=["bf16", "fp16"])
+@pytest.mark.parametrize("case", HEAD_CASES, ids=str)
+def test_conv3d_c1_lp(case, lp):
+    """the classif3 logit head on a 2-byte tensor -- tap expansion through conv1x1_lp, then the 27-tap gather -- against a
+    real 3x3x3 convolution in fp64 on the same rounded operands; the gather writes nothing outside its output"""
+    from dcanet_amd import ops
+    N, C, dims = case
+    x = seeded_tensor(f"lph.x{case}", (N, C) + dims).to(lp)
+    w = seeded_tensor(f"lph.w{case}", (1, C, 3, 3, 3)) * (2.0 / (27 * C)) ** 0.5
+    ref = F.conv3d(x.double(), w.to(lp).double(), None, 1, 1)
+    xg, wg = x.to(DEV), w.to(DEV)
+    with torch.no_grad():
+        got = ops.conv3d_c1_lp(xg, wg)
+        T = ops.conv1x1_lp(xg, wg[0].reshape(C, 27).t().contiguous(), lp, out_dtype=torch.float32)
+    assert got.dtype == torch.float32 and got.shape == ref.shape
+    err = (got.double().cpu() - ref).abs().max().item()
+    assert err <= 2e-5 * max(1.0, ref.abs().max().item()), f"max err {err:.3e}"
+    big, yv = _inside_sentinels(ref.numel(), torch.float32)
+    ops._chk(ops._L().dca_conv3d_c1_gather(ops._ptr(T), ops._ptr(yv), N, dims[0], dims[1], dims[2], ops._stream()),
+             "dca_conv3d_c1_gather")
+    assert torch.equal(yv.view(ref.shape), got), "direct C-ABI call differs from the op"
+    assert _sentinels_intact(big, ref.numel()), "wrote outside y"
 
 
 def test_conv3d_lp_refuses_training():
