@@ -5,7 +5,10 @@ The stereo focal loss runs as ONE HIP kernel per direction for all levels of a r
 Laplace target, focal weight, masks and the mean fused; the reference materialises five (B,48,h,w) temporaries per
 level).  Quirks of the reference are reproduced, not fixed: the estimates handed in by GwcNet are already softmax
 outputs and get log_softmax-ed again; the mean runs over all pixels, valid or not.  Like every kernel of this package
-the focal loss needs ROCm tensors: there is no CPU fallback."""
+the focal loss needs ROCm tensors: there is no CPU fallback.
+
+`PhotometricLoss` has no counterpart in the reference: the self-supervised loss of DESIGN.md section 6h (view synthesis +
+the reference's unused `loss_disp_smoothness`), one HIP launch per direction for all levels (csrc/selfsup.hip)."""
 import torch
 import torch.nn.functional as F
 
@@ -98,3 +101,26 @@ def focal_loss(disp_ests, disp_gt, maxdisp, focal_coefficient, sparse):
         for i in range(0, len(ests), 8):
             total = total + ev.loss_levels(ests[i:i + 8], ws[i:i + 8], disp_gt)
     return total
+
+
+class PhotometricLoss(object):
+    """`PhotometricLoss()(disp_ests, left, right, valid=None)`: sum_l weights[l] (photo_l + lam smooth_l) over the
+    full-resolution disparity maps of the training forward (`[pred_dca3, pred4]`, weighted like `model_loss`), from the
+    image pair alone -- no ground truth (`ops.selfsup_loss`; definitions in include/dca_hip.h).  left, right: the
+    (B,3,H,W) float32 images as the network sees them, normalised or not; valid: (B,H,W) float32 or bool, e.g. the
+    left-right check's mask, no gradient.  After a call `last` holds the detached (L,3) per-level (photo, smooth, sum M).
+
+    Data parallel note: like `model_loss`, every rank divides by its own sum M and the gradients are averaged over ranks;
+    that equals the global masked mean only when all ranks keep the same number of pixels."""
+
+    def __init__(self, weights=(1.8, 2.1), alpha=0.85, lam=0.1, c1=1e-4, c2=9e-4):
+        self.weights = tuple(float(w) for w in weights)
+        self.alpha, self.lam, self.c1, self.c2 = float(alpha), float(lam), float(c1), float(c2)
+        self.last = None
+
+    def __call__(self, disp_ests, left, right, valid=None):
+        if len(disp_ests) != len(self.weights):
+            raise RuntimeError(f"PhotometricLoss: {len(self.weights)} weights for {len(disp_ests)} disparity maps")
+        loss, self.last = ops.selfsup_loss(left, right, list(disp_ests), self.weights, valid, self.alpha, self.lam, self.c1,
+                                           self.c2)
+        return loss

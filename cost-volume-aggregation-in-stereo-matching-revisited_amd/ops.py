@@ -2058,6 +2058,109 @@ def lr_consistency(disp_left, disp_right_mirrored, tau=1.0, cols=None, outputs=N
 
 
 # ------------------------------------------------------------------------------------------------
+# Self-supervised loss (csrc/selfsup.hip): view synthesis + edge-aware smoothness, all levels of a
+# step in one launch per direction.  The smoothness term is the reference's util.py:76-86; the rest has no counterpart.
+# ------------------------------------------------------------------------------------------------
+SELFSUP_MAX_LEVELS = _C["DCA_SELFSUP_MAX_LEVELS"]
+SELFSUP_TILE = (_C["DCA_SELFSUP_TILE_H"], _C["DCA_SELFSUP_TILE_W"])
+SELFSUP_SUMS = _C["DCA_SELFSUP_SUMS"]
+SELFSUP_OUT = _C["DCA_SELFSUP_OUT"]
+SELFSUP_MAX_SAMPLE = (1 << 31) - 1          # 3 H W, the elements of one sample's image: offsets inside a sample are 32-bit
+
+
+def _selfsup_check(left, right, disps, weights, valid, scalars):
+    """validates the arguments of `selfsup_loss`; returns (B, H, W, weights as floats, valid_u8)"""
+    name = "selfsup_loss"
+    for t, what in ((left, "left"), (right, "right")):
+        _req_dev(t, name, f"the {what} image", torch.float32)
+    if left.dim() != 4 or left.shape[1] != 3 or left.shape != right.shape or left.device != right.device:
+        raise RuntimeError(f"{name}: expected two (B,3,H,W) images of one shape on one device, got {tuple(left.shape)} and "
+                           f"{tuple(right.shape)}")
+    B, _, H, W = (int(s) for s in left.shape)
+    if B < 1 or H < 3 or W < 3:
+        raise RuntimeError(f"{name}: the 3x3 windows need B >= 1, H >= 3 and W >= 3, got {tuple(left.shape)}")
+    if 3 * H * W > SELFSUP_MAX_SAMPLE or W > 1 << 24 or B > 65535:
+        raise RuntimeError(f"{name}: 3 H W <= {SELFSUP_MAX_SAMPLE} (offsets inside a sample are 32-bit), W <= 2^24 and "
+                           f"B <= 65535, got {tuple(left.shape)}")
+    disps = list(disps)
+    if not 1 <= len(disps) <= SELFSUP_MAX_LEVELS or len(weights) != len(disps):
+        raise RuntimeError(f"{name}: 1 to {SELFSUP_MAX_LEVELS} disparity maps with one weight each, got {len(disps)} maps and "
+                           f"{len(weights)} weights")
+    for d in disps:
+        _req_dev(d, name, "a disparity map", torch.float32)
+        if tuple(d.shape) not in ((B, H, W), (B, 1, H, W)) or d.device != left.device:
+            raise RuntimeError(f"{name}: expected ({B},{H},{W}) or ({B},1,{H},{W}) disparity maps on {left.device}, got "
+                               f"{tuple(d.shape)} on {d.device}")
+    valid_u8 = 0
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or not valid.is_cuda or valid.device != left.device:
+            raise RuntimeError(f"{name}: valid must be on the images' ROCm device; there is no CPU fallback")
+        if valid.dtype not in (torch.float32, torch.bool) or not valid.is_contiguous() or valid.numel() != B * H * W \
+                or tuple(valid.shape) not in ((B, H, W), (B, 1, H, W)):
+            raise RuntimeError(f"{name}: valid must be a contiguous float32 or bool ({B},{H},{W}) tensor, got {valid.dtype} "
+                               f"{tuple(valid.shape)}")
+        if valid.requires_grad:
+            raise RuntimeError(f"{name}: valid carries no gradient")
+        valid_u8 = int(valid.dtype == torch.bool)
+    alpha, lam, c1, c2 = scalars
+    if not (0.0 <= alpha <= 1.0) or not (c1 > 0.0 and c2 > 0.0) or lam != lam:
+        raise RuntimeError(f"{name}: 0 <= alpha <= 1, c1 > 0, c2 > 0 and a lam that is a number, got alpha {alpha}, lam {lam}, "
+                           f"c1 {c1}, c2 {c2}")
+    return B, H, W, [float(w) for w in weights], valid_u8
+
+
+class _SelfSupLoss(torch.autograd.Function):
+    """sum_l w_l (photo_scale photo_l + lam smooth_l) and the detached (L,3) per-level (photo, smooth, sum M)"""
+
+    @staticmethod
+    def forward(ctx, left, right, valid, weights, scalars, photo_scale, *disps):
+        B, H, W, weights, valid_u8 = _selfsup_check(left, right, disps, weights, valid, scalars)
+        n = len(disps)
+        tiles = -(-H // SELFSUP_TILE[0]) * -(-W // SELFSUP_TILE[1])
+        work = torch.empty((n * B * tiles * SELFSUP_SUMS,), device=left.device, dtype=torch.float64)
+        out = torch.empty((n * SELFSUP_OUT + 1,), device=left.device, dtype=torch.float32)
+        dptr = (ctypes.c_void_p * n)(*[d.data_ptr() for d in disps])
+        wts = (ctypes.c_float * n)(*weights)
+        with torch.cuda.device_of(left):
+            _chk(_L().dca_selfsup_loss_fwd(_ptr(left), _ptr(right), dptr, wts, n, _ptr(valid), valid_u8, _ptr(work), _ptr(out),
+                                           B, H, W, *scalars, photo_scale, _stream()), "dca_selfsup_loss_fwd")
+        ctx.save_for_backward(left, right, valid, out, *disps)
+        ctx.meta = (B, H, W, weights, valid_u8, scalars, photo_scale)
+        stats = out[:n * SELFSUP_OUT].view(n, SELFSUP_OUT)[:, :3]
+        ctx.mark_non_differentiable(stats)
+        return out[n * SELFSUP_OUT], stats
+
+    @staticmethod
+    def backward(ctx, gloss, _gstats):
+        left, right, valid, out, *disps = ctx.saved_tensors
+        B, H, W, weights, valid_u8, scalars, photo_scale = ctx.meta
+        n = len(disps)
+        gloss = _req(gloss.reshape(1), "selfsup_loss.backward")
+        gds = [torch.empty_like(d) for d in disps]
+        dptr = (ctypes.c_void_p * n)(*[d.data_ptr() for d in disps])
+        gptr = (ctypes.c_void_p * n)(*[g.data_ptr() for g in gds])
+        wts = (ctypes.c_float * n)(*weights)
+        with torch.cuda.device_of(left):
+            _chk(_L().dca_selfsup_loss_bwd(_ptr(left), _ptr(right), dptr, gptr, wts, n, _ptr(valid), valid_u8, _ptr(out),
+                                           _ptr(gloss), B, H, W, *scalars, photo_scale, _stream()), "dca_selfsup_loss_bwd")
+        return (None,) * 6 + tuple(gds)
+
+
+def selfsup_loss(left, right, disps, weights, valid=None, alpha=0.85, lam=0.1, c1=1e-4, c2=9e-4, photo_scale=1.0):
+    """Self-supervised stereo loss of up to 8 disparity maps in one launch per direction (definitions: include/dca_hip.h,
+    dca_selfsup_loss_fwd): sum_l weights[l] (photo_l + lam smooth_l), where photo_l compares `left` with `right` warped
+    along the row by disps[l] (alpha SSIM over 3x3 windows + (1 - alpha) L1, at interior pixels that are in view and
+    `valid`) and smooth_l is the reference's edge-aware `loss_disp_smoothness` (util.py:76-86).
+    left, right: (B,3,H,W) float32, used as given; disps: (B,H,W) or (B,1,H,W) contiguous float32, full-resolution pixels;
+    valid: (B,H,W) float32 or bool, no gradient, default all ones; photo_scale: 1, or 0 for the smoothness term alone.
+    3 H W < 2^31 per sample.  Returns (loss, stats): a 0-dim float32 tensor with a gradient to the disparity maps only,
+    and the detached (L,3) float32 per-level (photo, smooth, sum M) for logging.  Bitwise reproducible; no host
+    synchronisation; graph-capturable."""
+    scalars = (float(alpha), float(lam), float(c1), float(c2))
+    return _SelfSupLoss.apply(left, right, valid, tuple(float(w) for w in weights), scalars, float(photo_scale), *disps)
+
+
+# ------------------------------------------------------------------------------------------------
 # Inference frame I/O (my_img.py:47-110 around the model call): per-plane normalisation as histogram -> table -> look-up,
 # placement in the zero-padded frame, export of the cropped disparity (csrc/frame_io.hip).  No launch synchronises.
 # ------------------------------------------------------------------------------------------------

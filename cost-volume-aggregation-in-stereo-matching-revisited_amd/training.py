@@ -9,6 +9,9 @@ contrast mean, an exact integer sum.  This module restates every step in numpy (
 path and the yardstick of the GPU tests) and `TrainInput(device_io=True)` runs the same steps as HIP kernels
 (csrc/train_io.hip) on the uint8 pair and the raw disparity as the decoder delivered them.
 
+`SelfSupStep` is a training step WITHOUT ground truth (no counterpart in the reference): the
+supervised losses are replaced by `models.loss.PhotometricLoss` on the image pair.
+
 `train()` indexes with the mask for the EPE (a device-to-host stall) and calls `.item()` twice; `TrainStep` keeps
 [steps, sum loss, sum epe, sum #mask] in a device fp64 state and synchronises only in `result()`.
 
@@ -28,6 +31,7 @@ from .evaluation import all_reduce_state  # noqa: F401  (same contract: every en
 from .inference import imagenet_lut
 
 STEPS, SUM_LOSS, SUM_EPE, PIXELS = 0, 1, 2, 3      # TrainStep.state
+SS_STEPS, SS_LOSS, SS_PHOTO, SS_SMOOTH, SS_KEPT = 0, 1, 2, 3, 4      # SelfSupStep.state
 
 
 # ---- byte tables -------------------------------------------------------------------------------------------------------
@@ -438,3 +442,85 @@ class TrainStep:
         return {"steps": int(steps), "loss": float(s[SUM_LOSS] / steps) if steps else 0.0,
                 "epe": float(s[SUM_EPE] / steps) if steps else 0.0,
                 "pixels": int(s[PIXELS]) if np.isfinite(s[PIXELS]) else 0}
+
+
+# ---- SelfSupStep -----------------------------------------------------------------------------------------------------------
+class SelfSupStep:
+    """`ss = SelfSupStep(model, optimizer); for batch: ss.step(imgL, imgR); print(ss.result())` -- a training step that
+    needs no ground truth, in the shape of `TrainStep`: `bind`, `local_step`, `optimizer_step`, `step`, `result`.
+
+    `step` enqueues (the mask pass,) zero_grad, the training forward, `loss(disp_outputs, imgL, imgR, valid)`, backward and
+    the optimizer step, and adds [1, loss, sum_l w_l photo_l / sum_l w_l, sum_l w_l smooth_l / sum_l w_l, share of interior
+    pixels kept (sum M over the interior pixel count, mean over the levels)] to `state` (device, float64), all without a
+    host synchronisation; `result()` is the one synchronisation.
+
+    Only `disp_outputs` (`[pred_dca3, pred4]`) are supervised: the five class-volume heads of the training forward
+    (`cls_outputs`) take no part in this loss, so the parameters that only they depend on get NO gradient in such a step
+    (their `.grad` stays None after `zero_grad`, and the optimizer leaves them alone).  To train them as well, add the
+    supervised loss on the pairs that have a label: `loss_a + loss_b`.
+
+    mask=None: every in-view interior pixel counts.  mask="lr": `valid` is `model.predict_lr(imgL, imgR, tau)["valid"]`,
+    taken BEFORE the training forward with the weights as they are: two more forward passes in eval mode under no_grad,
+    which leave the BatchNorm running statistics alone; the model is put back into train mode afterwards.  Across ranks
+    every rank divides by its own sum M (the note at `models.loss.PhotometricLoss`); `all_reduce_state(ss.state)` before
+    `result()` as with `TrainStep`."""
+
+    def __init__(self, model, optimizer, loss=None, mask=None, tau=1.0):
+        if mask not in (None, "lr"):
+            raise ValueError(f"mask {mask!r}: None or 'lr'")
+        if loss is None:
+            from .models.loss import PhotometricLoss
+            loss = PhotometricLoss()
+        self.model, self.optimizer, self.loss, self.mask, self.tau = model, optimizer, loss, mask, float(tau)
+        dev = next(model.parameters()).device
+        self.state = torch.zeros(5, device=dev, dtype=torch.float64)
+        self._one = torch.ones((), device=dev, dtype=torch.float64)
+        self._w = torch.tensor(loss.weights, device=dev, dtype=torch.float64)
+        self._w /= self._w.sum()
+        self._bound = None
+        self.last = None      # (loss, per-level (photo, smooth, sum M)) of the last step: device tensors
+
+    def reset(self):
+        self.state.zero_()
+
+    def bind(self, imgL, imgR):
+        if imgL.dim() != 4 or imgL.shape[1] != 3 or imgL.shape != imgR.shape or imgL.dtype != torch.float32:
+            raise ValueError(f"expected two (B,3,H,W) float32 images, got {tuple(imgL.shape)} and {tuple(imgR.shape)}")
+        self._bound = (imgL, imgR)
+
+    def local_step(self):
+        """(mask pass,) zero_grad, forward, loss, backward, sums into the state; returns the detached loss"""
+        imgL, imgR = self._bound
+        valid = None
+        if self.mask == "lr":
+            valid = self.model.predict_lr(imgL, imgR, self.tau)["valid"]
+        self.model.train()
+        self.optimizer.zero_grad()
+        _cls_outputs, disp_outputs = self.model(imgL, imgR)
+        loss = self.loss(disp_outputs, imgL, imgR, valid)
+        loss.backward()
+        with torch.no_grad():
+            stats = self.loss.last.double()               # (L,3): photo, smooth, sum M
+            interior = float(imgL.shape[0] * (imgL.shape[2] - 2) * (imgL.shape[3] - 2))
+            loss_d = loss.detach()
+            self.state += torch.stack([self._one, loss_d.double(), (self._w * stats[:, 0]).sum(),
+                                       (self._w * stats[:, 1]).sum(), stats[:, 2].mean() / interior])
+        self.last = (loss_d, self.loss.last)
+        return loss_d
+
+    def optimizer_step(self):
+        self.optimizer.step()
+
+    def step(self, imgL, imgR):
+        self.bind(imgL, imgR)
+        loss = self.local_step()
+        self.optimizer_step()
+        return loss
+
+    def result(self):
+        """one device -> host copy: {"steps", "loss", "photo", "smooth", "kept"}, means over the steps"""
+        s = self.state.cpu().numpy()
+        n = s[SS_STEPS]
+        mean = (lambda i: float(s[i] / n)) if n else (lambda i: 0.0)
+        return {"steps": int(n), "loss": mean(SS_LOSS), "photo": mean(SS_PHOTO), "smooth": mean(SS_SMOOTH),
+                "kept": mean(SS_KEPT)}

@@ -649,6 +649,54 @@ int dca_point_cloud(const float* pred, const float* mask, const unsigned char* r
                     int stride, float f, float fb, float cx, float cy, float doffs, float min_disp, float max_depth,
                     float mask_min, hipStream_t stream);
 
+/* ---- self-supervised loss (selfsup.hip): view synthesis + edge-aware smoothness -----------------------
+ * Training without ground truth.  The smoothness term is the reference's util.py:76-86 `loss_disp_smoothness` (defined
+ * there, never called); the view-synthesis term has no counterpart in the reference.
+ * left = I, right = R: (B,3,H,W) planar fp32, used as given.  disps / gdisps / weights: HOST arrays of nlev
+ * (<= DCA_SELFSUP_MAX_LEVELS) device pointers to (B,H,W) fp32 maps in full-resolution pixels / floats w_l.  valid: (B,H,W)
+ * device, fp32 (valid_u8 = 0) or one byte per pixel, 0 / 1 (valid_u8 = 1), or NULL (all ones); it carries no gradient.
+ * Per level, sample and pixel (y, x), d = d_l(b, y, x):
+ *   xs = float(x) - d;  xc = clamp(xs, 0, W-1);  x0 = min(floor(xc), W-2);  t = xc - x0
+ *   Y_c = R_c[y, x0] + t (R_c[y, x0+1] - R_c[y, x0]);   inview = 0 <= xs <= W-1   (false for a NaN)
+ *   dY_c/dd = -(R_c[y, x0+1] - R_c[y, x0]) where 0 < xs < W-1, and 0 where xs is clamped
+ * Photometric term, at interior pixels p (1 <= y <= H-2, 1 <= x <= W-2; the 3x3 window means carry no padding), per
+ * channel c with mu = the window mean, var_I = E[I^2] - mu_I^2, var_Y, cov = E[IY] - mu_I mu_Y (evaluated around the
+ * window means: the same numbers without the cancellation):
+ *   SSIM_c = (2 mu_I mu_Y + c1)(2 cov + c2) / ((mu_I^2 + mu_Y^2 + c1)(var_I + var_Y + c2))
+ *   e(p) = alpha mean_c clamp((1 - SSIM_c) / 2, 0, 1) + (1 - alpha) mean_c |I_c - Y_c|
+ *   M(p) = inview(p) valid(p)      only the centre pixel is masked; a window may contain clamped samples
+ *   photo_l = sum M e / max(sum M, 1)                    sum M is a constant for the gradient
+ * Smoothness term, over all H (W-1) horizontal and (H-1) W vertical pairs, independent of valid:
+ *   wx(p) = exp(-mean_c |I_c(p) - I_c(p + x^)|), wy likewise;
+ *   smooth_l = (sum |d(p) - d(p + x^)| wx + sum |d(p) - d(p + y^)| wy) / (sum wx + sum wy)
+ * total = sum_l w_l (photo_scale photo_l + lam smooth_l); photo_scale = 1, or 0: the smoothness term alone, in which case
+ * right and valid are not read.  The gradient of |.| at 0 and of the clamps at their ends is 0.
+ *
+ * dca_selfsup_loss_fwd: TWO launches.  (1) grid (tiles, B, nlev), tiles = ceil(H / DCA_SELFSUP_TILE_H) ceil(W /
+ * DCA_SELFSUP_TILE_W): a tile with a one-pixel halo in LDS per channel; the warped image is recomputed, never stored; every
+ * workgroup writes DCA_SELFSUP_SUMS doubles (sum M e, sum M, sum |dd| w, sum w) to work, which holds
+ * nlev B tiles DCA_SELFSUP_SUMS doubles.  (2) one workgroup adds them in a fixed order and writes out, nlev DCA_SELFSUP_OUT + 1
+ * floats: per level (photo_l, smooth_l, sum M, 1 / max(sum M, 1), 1 / (sum wx + sum wy)), then the total.
+ * dca_selfsup_loss_bwd: ONE launch, the same tiles with a two-pixel halo; `out` is the forward's, unchanged; gloss: one
+ * device float, the incoming gradient.  gdisps[l] = gloss d total / d d_l, every element written exactly once; the gradient
+ * at p collects (dS/dmu_Y + 2 Y_p dS/dE[Y^2] + I_p dS/dE[IY]) / 9 from the (up to nine) interior windows that contain p.
+ * gdisps[l] must not alias disps[l].
+ * No atomics and no host synchronisation: loss and gradients are bitwise reproducible, the launches graph-capturable.
+ * Refused: H < 3, W < 3, W > 2^24, 3 H W >= 2^31 (offsets inside a sample are 32-bit), B > 65535, nlev outside
+ * [1, DCA_SELFSUP_MAX_LEVELS], alpha outside [0, 1], c1 or c2 not positive, NaN lam or photo_scale, NULL pointers. */
+#define DCA_SELFSUP_MAX_LEVELS 8
+#define DCA_SELFSUP_TILE_W 64
+#define DCA_SELFSUP_TILE_H 16
+#define DCA_SELFSUP_SUMS 4
+#define DCA_SELFSUP_OUT 5
+int dca_selfsup_loss_fwd(const float* left, const float* right, const float* const* disps, const float* weights, int nlev,
+                         const void* valid, int valid_u8, double* work, float* out, int B, int H, int W, float alpha,
+                         float lam, float c1, float c2, float photo_scale, hipStream_t stream);
+int dca_selfsup_loss_bwd(const float* left, const float* right, const float* const* disps, float* const* gdisps,
+                         const float* weights, int nlev, const void* valid, int valid_u8, const float* out,
+                         const float* gloss, int B, int H, int W, float alpha, float lam, float c1, float c2,
+                         float photo_scale, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
