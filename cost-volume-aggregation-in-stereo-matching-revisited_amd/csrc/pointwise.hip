@@ -1093,6 +1093,21 @@ extern "C" int dca_bn_backward(const float* dz, const float* y, const float* res
   return dca_launch_status();
 }
 
+// The reduce and finalize passes of dca_bn_backward alone (no res_pre): dgb for a consumer that forms dy itself
+// (conv1_bwd_fused.hip).  Same chunking and kernels, so dgamma / dbeta are the bits dca_bn_backward gives.
+extern "C" int dca_bn_backward_reduce(const float* dz, const float* y, const float* stats, double* part, float* dgb, int N,
+                                      int C, long S, float slope, int training, hipStream_t stream) {
+  DCA_REQUIRE(dz && y && stats && part && dgb && N > 0 && C > 0 && S > 0 && C <= 65535);
+  int nchunk; long len;
+  chunking(S, C, &nchunk, &len);
+  const int vec = (S % 4 == 0) && ((((uintptr_t)dz | (uintptr_t)y) & 15) == 0);
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, nchunk), dim3(256), 0, stream, dz, y, (const float*)nullptr, stats, part,
+                     N, C, S, nchunk, len, slope, vec, (unsigned*)nullptr);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, stream, part, nchunk, (double)N * (double)S, dgb, C,
+                     stats, training, (const unsigned*)nullptr, (const unsigned*)nullptr, 0, (int*)nullptr);
+  return dca_launch_status();
+}
+
 // BatchNorm backward (no res_pre) writing dy in the packed px2 format: dyp (N*C*S*4 bytes), dyexps (C ints, out) = the
 // per-channel exponents dy was scaled by, from the bound of bn_bwd_finalize_kernel; gmax = scratch of C * DCA_AMAX_CSLOTS
 // words; ymax / ymax_slots = the per-channel max |y - mean| slots the forward apply pass emitted (may be null / 0).

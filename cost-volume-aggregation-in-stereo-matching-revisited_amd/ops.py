@@ -334,6 +334,7 @@ DECONV_X3 = os.environ.get("DCA_DECONV", "x3") != "fp32"
 C1_WGRAD_FUSED = os.environ.get("DCA_C1_WGRAD", "fused") != "expand"   # logit heads: weight gradient without the 27-plane tensor (A/B)
 CONV_S2_X2 = os.environ.get("DCA_CONV_S2", "x2") != "fp32"     # the stride-2 convolution itself on the f16x2 split (A/B)
 BN_FUSE = os.environ.get("DCA_BN_FUSE", "1") != "0"        # BatchNorm batch statistics from the conv epilogue (training)   # the transposed-convolution member of the family alone (A/B timing)
+C1_BWD_FUSE = os.environ.get("DCA_C1_BWD", "fused") != "split"      # 1x1x1 conv + BatchNorm backward as one launch (A/B)
 _X3_MIN_WORKGROUPS = 1
 
 
@@ -524,6 +525,48 @@ def _conv_family(x, x2, A, B, ksize, stride, transposed, scale=None, res_pre=Non
     if _dx3_eligible(x, x2, ksize, stride, transposed, A, B):
         return "dx3"
     return "c1x3" if _c1x3_eligible(x, x2, ksize, A, x.shape[1], y) else "mfma"
+
+
+def _c1_bwd_route(x, x2, weight, res_pre=None):
+    """how the backward of a 1x1x1 convolution with a BatchNorm behind it runs -- "fused" (conv1_bwd_fused.hip: the BatchNorm
+    backward stops after its reduction and hands dz on, ONE launch forms dy in registers and gives dx [, dx2] and dw) or
+    "split" (the BatchNorm writes dy; backward-data and weight gradient per input through _conv_family / _wgrad_family).
+    Asked once, in the forward, by convbn3d / convbn3d_pair: the BatchNorm and the convolution node get the same answer."""
+    if not C1_BWD_FUSE or res_pre is not None or weight.dim() != 5 or weight.shape[2] != 1 or not torch.is_grad_enabled():
+        return "split"
+    C1, C2 = x.shape[1], (0 if x2 is None else x2.shape[1])
+    if weight.shape[0] != 32 or (C1, C2) not in ((32, 0), (32, 32)) or weight.shape[1] != C1 + C2:
+        return "split"
+    tensors = (x, weight) if x2 is None else (x, x2, weight)
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.requires_grad for t in tensors):
+        return "split"      # the launch produces every gradient
+    if x2 is not None and x2.shape != x.shape:
+        return "split"
+    S = x[0, 0].numel()
+    return "fused" if (S % 4 == 0 and x.shape[0] * 32 * S * 4 < 0x7ffff000) else "split"
+
+
+def _c1_bwd_fused(dz, x, x2, weight):
+    """(dx, dx2 or None, dw) of the 1x1x1 convolution whose BatchNorm handed its dz on (tag _dca_lazy, _BnAct.backward)"""
+    tag = getattr(dz, "_dca_lazy", None)
+    if tag is None:
+        raise RuntimeError("conv3d.backward: expected the gradient the BatchNorm behind this 1x1x1 convolution hands on "
+                           "(the tag was lost on the way through autograd)")
+    y, stats, dgb, slope, training = tag
+    if y.shape != dz.shape or y.shape[0] != x.shape[0] or y.shape[2:] != x.shape[2:]:
+        raise RuntimeError("conv3d.backward: the BatchNorm's gradient does not belong to this convolution")
+    N, C1 = x.shape[0], x.shape[1]
+    C2 = 0 if x2 is None else x2.shape[1]
+    S = x[0, 0].numel()
+    lib = _L()
+    part = torch.empty((lib.dca_conv1_bwd_fused_workspace(N, S, int(x2 is not None)),), device=x.device, dtype=torch.float32)
+    gx = torch.empty_like(x)
+    gx2 = None if x2 is None else torch.empty_like(x2)
+    gw = torch.empty_like(weight)
+    _chk(lib.dca_conv1_bwd_fused(_ptr(dz), _ptr(y), _ptr(stats), _ptr(dgb), float(slope), int(training), _ptr(x), _ptr(x2),
+                                 _ptr(weight), _ptr(part), _ptr(gx), _ptr(gx2), _ptr(gw), C1 + C2, 1, N, C1, C2,
+                                 weight.shape[0], S, _stream()), "dca_conv1_bwd_fused")
+    return gx, gx2, gw
 
 
 def _k3s1(weight, stride, transposed, x2, head=False):
@@ -821,7 +864,7 @@ class _Conv3d(torch.autograd.Function):
     Optional second input x2 = implicit channel concat for the 1x1x1 `fuse` conv."""
 
     @staticmethod
-    def forward(ctx, x, x2, weight, stride, transposed, want_stats=False, alias=False, packed_dy=False):
+    def forward(ctx, x, x2, weight, stride, transposed, want_stats=False, alias=False, packed_dy=False, lazy_dy=False):
         """want_stats: returns (y, part) -- part = the BatchNorm batch-statistics partials of y from the convolution
         kernel's own epilogue (not differentiable; csrc/bn_fused_stats.h), empty where the kernel serving this shape
         cannot produce them.
@@ -838,6 +881,7 @@ class _Conv3d(torch.autograd.Function):
         ctx.set_materialize_grads(False)             # an unused output's gradient arrives as None, not as a tensor of zeros
         ctx.x_px2 = getattr(x, "_dca_px2", None)    # save_for_backward keeps the tensor, not its Python attributes
         ctx.packed_dy = bool(packed_dy)              # the gradient of y arrives as a packed px2 operand (_BnAct, pack_dy)
+        ctx.lazy_dy = bool(lazy_dy)                  # it arrives as the BatchNorm's own dz, tagged (_BnAct, lazy_dy)
         ctx.x_exps = None
         # a packed twin of x (written beside it by its BatchNorm): this convolution and its weight gradient read the twin
         Cout, Cin = weight.shape[:2]
@@ -871,7 +915,7 @@ class _Conv3d(torch.autograd.Function):
         stride, transposed = ctx.meta
         g_alias = _opt(rest[-1], "conv3d.backward") if (ctx.alias and rest) else None
         if dy is None:       # y was not used: nothing flows through the convolution, only past it (alias)
-            return g_alias, None, None, None, None, None, None, None
+            return g_alias, None, None, None, None, None, None, None, None
         if ctx.packed_dy and not _is_packed(dy):
             raise RuntimeError("conv3d.backward: expected the packed px2 gradient of the BatchNorm behind this convolution "
                                "(the tag was lost on the way through autograd)")
@@ -912,6 +956,9 @@ class _Conv3d(torch.autograd.Function):
                 C1 = x.shape[1]
                 if Cout not in (32, 64):
                     raise RuntimeError("1x1x1 conv backward-data needs 32 or 64 output channels")
+                if ctx.lazy_dy:
+                    gx, gx2, gw = _c1_bwd_fused(dy, x, x2, weight)
+                    need_x = need_x2 = need_w = False
                 if need_x:
                     wa = w2[:, :C1].contiguous()
                     gx = _conv_sliced(dy, None, wa, Cout, C1, 1, 1, 0, 1, 1, False)
@@ -925,7 +972,7 @@ class _Conv3d(torch.autograd.Function):
                         _wgrad(x2, dy, gw, C1, Cin - C1, Cout, 1, 1, Cin, 1)
         if g_alias is not None:      # alias on a path without the fused form
             gx = g_alias if gx is None else gx + g_alias
-        return gx, gx2, gw, None, None, None, None, None
+        return gx, gx2, gw, None, None, None, None, None, None
 
 
 class _ConvPair(torch.autograd.Function):
@@ -935,9 +982,11 @@ class _ConvPair(torch.autograd.Function):
     (three passes over a 1/4-resolution tensor).  Same kernels, same values: (a + b) is one fp32 addition either way."""
 
     @staticmethod
-    def forward(ctx, x, wa, wb, want_stats):
+    def forward(ctx, x, wa, wb, want_stats, lazy_b=False):
+        """lazy_b: the gradient of the 1x1x1 branch arrives as its BatchNorm's own dz, tagged (_BnAct, lazy_dy)"""
         x, wa, wb = _req(x, "conv_pair"), _req(wa, "conv_pair.weight_a"), _req(wb, "conv_pair.weight_b")
         ctx.save_for_backward(x, wa, wb)
+        ctx.lazy_b = bool(lazy_b)
         with torch.cuda.device_of(x):
             if want_stats:
                 ya, pa = _conv_forward_impl(x, None, wa, 2, False, want_stats=True)
@@ -958,14 +1007,20 @@ class _ConvPair(torch.autograd.Function):
         if Cb not in (32, 64):
             raise RuntimeError("1x1x1 conv backward-data needs 32 or 64 output channels")
         with torch.cuda.device_of(x):
-            gb = _conv_sliced(dyb, None, wb.reshape(Cb, Cin).contiguous(), Cb, Cin, 1, 1, 0, 1, 1, False)
+            if ctx.lazy_b:
+                gb, _, gwb = _c1_bwd_fused(dyb, x, None, wb)
+            else:
+                gb = _conv_sliced(dyb, None, wb.reshape(Cb, Cin).contiguous(), Cb, Cin, 1, 1, 0, 1, 1, False)
+                gwb = None
             gx = _conv_sliced(dya, None, wa, Ca, Cin, 27, 1, 0, 3, 2, True, res_post=gb)     # d(x) = A^T dya + B^T dyb
             if gx.shape != x.shape:
                 raise RuntimeError("stride-2 conv backward needs even input dims")
-            gwa, gwb = torch.empty_like(wa), torch.empty_like(wb)
+            gwa = torch.empty_like(wa)
             _wgrad(x, dya, gwa, 0, Cin, Ca, 3, 2, Cin * 27, 27)
-            _wgrad(x, dyb, gwb, 0, Cin, Cb, 1, 1, Cin, 1)
-        return gx, gwa, gwb, None
+            if gwb is None:
+                gwb = torch.empty_like(wb)
+                _wgrad(x, dyb, gwb, 0, Cin, Cb, 1, 1, Cin, 1)
+        return gx, gwa, gwb, None, None
 
 
 PAIR_FUSE = os.environ.get("DCA_PAIR_FUSE", "1") != "0"
@@ -982,9 +1037,10 @@ def convbn3d_pair(x, conv_a, bn_a, slope_a, conv_b, bn_b, slope_b, pack_a=False)
     if not ok:
         return convbn3d(x, conv_a, bn_a, slope_a, pack_out=pack_a), convbn3d(x, conv_b, bn_b, slope_b)
     stats = bool(BN_FUSE and bn_a.training and bn_b.training)
-    ya, pa, yb, pb = _ConvPair.apply(x, conv_a.weight, conv_b.weight, stats)
+    lazy = _c1_bwd_route(x, None, conv_b.weight) == "fused"
+    ya, pa, yb, pb = _ConvPair.apply(x, conv_a.weight, conv_b.weight, stats, lazy)
     za = bn_act(ya, bn_a, slope_a, stats_part=pa if pa.numel() else None, pack_out=pack_a)
-    zb = bn_act(yb, bn_b, slope_b, stats_part=pb if pb.numel() else None)
+    zb = bn_act(yb, bn_b, slope_b, stats_part=pb if pb.numel() else None, lazy_dy=lazy)
     return za, zb
 
 
@@ -1063,7 +1119,7 @@ class _BnAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, gamma, beta, running_mean, running_var, training, momentum, eps, slope, res_pre, res_post,
-                part=None, zmax=None, pack_z=False, pack_dy=False):
+                part=None, zmax=None, pack_z=False, pack_dy=False, lazy_dy=False):
         """zmax: per-channel slot words that receive max |z| (see _cslots); z is tagged with them here"""
         y = _req(y, "batch_norm")
         res_pre, res_post = _opt(res_pre, "res_pre"), _opt(res_post, "res_post")
@@ -1072,6 +1128,7 @@ class _BnAct(torch.autograd.Function):
         lib = _L()
         pack_z = int(pack_z) if (training and C % 8 == 0) else 0
         pack_dy = bool(pack_dy and res_pre is None and C % 8 == 0)
+        ctx.lazy_dy = bool(lazy_dy and res_pre is None and not pack_dy)
         with torch.cuda.device_of(y):
             zexps = torch.empty((C,), device=y.device, dtype=torch.int32) if pack_z else None
             rpre = _slots_of(res_pre) if (pack_z and res_pre is not None) else None
@@ -1108,16 +1165,24 @@ class _BnAct(torch.autograd.Function):
             nchunk = lib.dca_bn_num_chunks(C, S)
             part = torch.empty((C * nchunk * 2,), device=y.device, dtype=torch.float64)
             dgb = torch.empty((4 * C,), device=y.device, dtype=torch.float32)
-            dy = torch.empty_like(y)
             g_out = None
-            if pack_dy:
+            if ctx.lazy_dy:
+                # reduce and finalize only: the 1x1x1 convolution that produced y forms dy itself (_c1_bwd_fused) from dz,
+                # which travels on as an alias of its own carrying what that launch needs
+                _chk(lib.dca_bn_backward_reduce(_ptr(dz), _ptr(y), _ptr(stats), _ptr(part), _ptr(dgb), N, C, S, float(slope),
+                                                int(training), _stream()), "dca_bn_backward_reduce")
+                dy = dz.view_as(dz)
+                dy._dca_lazy = (y, stats, dgb, slope, training)
+            elif pack_dy:
                 dyexps = torch.empty((C,), device=y.device, dtype=torch.int32)
                 gmax = torch.empty((C * CSLOTS,), device=y.device, dtype=torch.int32)
+                dy = torch.empty_like(y)
                 _chk(lib.dca_bn_backward_pack(_ptr(dz), _ptr(y), _ptr(stats), _ptr(part), _ptr(dgb), _ptr(dy), _ptr(dyexps),
                                               _ptr(gmax), _ptr(ymax), ymax_slots if ymax is not None else 0, N, C, S,
                                               float(slope), int(training), _stream()), "dca_bn_backward_pack")
                 _tag_px2(dy, dyexps)
             else:
+                dy = torch.empty_like(y)
                 want_g = has_pre and slope != 1.0 and ctx.needs_input_grad[9]
                 g_out = torch.empty_like(y) if want_g else None
                 dm = _cslots(C, y.device) if CONV_X2 else None     # per-channel max |dy| for the convolution's backward kernels
@@ -1129,7 +1194,7 @@ class _BnAct(torch.autograd.Function):
         if has_pre and ctx.needs_input_grad[9]:
             g_pre = g_out if g_out is not None else dz
         g_post = dz if (has_post and ctx.needs_input_grad[10]) else None
-        return dy, dgb[:C], dgb[C:2 * C], None, None, None, None, None, None, g_pre, g_post, None, None, None, None
+        return dy, dgb[:C], dgb[C:2 * C], None, None, None, None, None, None, g_pre, g_post, None, None, None, None, None
 
 
 _tls = threading.local()
@@ -1264,14 +1329,16 @@ class batched_bn_counters:
         return False
 
 
-def bn_act(y, bn, slope=1.0, res_pre=None, res_post=None, stats_part=None, pack_out=False, pack_dy=False):
+def bn_act(y, bn, slope=1.0, res_pre=None, res_post=None, stats_part=None, pack_out=False, pack_dy=False, lazy_dy=False):
     """Applies the nn.BatchNorm3d module `bn` (parameters/buffers only; its forward is never called).
     stats_part: batch-statistics partial sums of y from the producing convolution (`_Conv3d` with want_stats), if it made them.
     pack_out: True -- the result has ONE consumer, an f16x2 3x3x3 stride-1 convolution: write it in the packed px2 operand
     format instead of fp32; "both" -- several consumers, ONE of them such a convolution: fp32 result plus a packed twin that
     this convolution and its weight gradient pick up (training BatchNorm only; plain fp32 otherwise).  The packed forms do
     not depend on the width; at W % 4 != 0 the twin's reader gets an fp32 gradient (_pack_dy_ok) and takes the fp32 tensor
-    for its weight gradient (_Conv3d.backward), the forward still reads the twin.  pack_dy: see _BnAct."""
+    for its weight gradient (_Conv3d.backward), the forward still reads the twin.  pack_dy: see _BnAct.
+    lazy_dy: y's only producer is a 1x1x1 convolution node that was told the same (_c1_bwd_route == "fused"): backward runs
+    the reduction only and hands dz on, tagged, for that node's one fused launch.  Never set by a caller that owns y."""
     momentum = 0.1 if bn.momentum is None else bn.momentum
     training = bn.training or bn.running_mean is None
     if _lp_dtype() is not None:
@@ -1283,7 +1350,8 @@ def bn_act(y, bn, slope=1.0, res_pre=None, res_post=None, stats_part=None, pack_
     pack_dy = bool(pack_dy and PACK and CONV_X2 and res_pre is None and C % 8 == 0)
     zm = _cslots(C, y.device) if (CONV_X2 and pack_z != 1) else None    # per-channel max |z|: the next convolution's operand scales
     z = _BnAct.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps, float(slope),
-                     res_pre, res_post, stats_part if training else None, zm, pack_z, pack_dy)
+                     res_pre, res_post, stats_part if training else None, zm, pack_z, pack_dy,
+                     bool(lazy_dy and res_pre is None))
     if bn.training and bn.num_batches_tracked is not None:
         pending = getattr(_tls, "pending", None)
         if pending is not None:
@@ -1377,8 +1445,13 @@ def convbn3d(x, conv, bn, slope=1.0, res_pre=None, res_post=None, x2=None, alias
         # the convolution kernel emits the batch statistics of its own output where it has such a form (the bf16x3 family):
         # no separate pass over y
         pdy = _pack_dy_ok(x, x2, conv, transposed, stride, res_pre)
-        y, part = _Conv3d.apply(x, x2, conv.weight, int(stride), bool(transposed), True, False, pdy)
-        return bn_act(y, bn, slope, res_pre, res_post, part if part.numel() else None, pack_out=pack_out, pack_dy=pdy)
+        lazy = not transposed and _c1_bwd_route(x, x2, conv.weight, res_pre) == "fused"
+        y, part = _Conv3d.apply(x, x2, conv.weight, int(stride), bool(transposed), True, False, pdy, lazy)
+        return bn_act(y, bn, slope, res_pre, res_post, part if part.numel() else None, pack_out=pack_out, pack_dy=pdy,
+                      lazy_dy=lazy)
+    if not transposed and _lp_dtype() is None and _c1_bwd_route(x, x2, conv.weight, res_pre) == "fused":
+        y = _Conv3d.apply(x, x2, conv.weight, int(stride), False, False, False, False, True)   # eval-mode BatchNorm under grad
+        return bn_act(y, bn, slope, res_pre, res_post, lazy_dy=True)
     y = conv3d(x, conv.weight, stride, transposed, x2)
     return bn_act(y, bn, slope, res_pre, res_post)
 

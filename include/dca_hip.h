@@ -118,6 +118,20 @@ long dca_conv3d_wgrad_workspace(int N, int Cx, int Cy, int Do, int Ho, int Wo, i
 int dca_conv3d_wgrad(const float* x, const float* dy, float* part, float* dw, int N, int Cx, int Cy, int Di, int Hi,
                      int Wi, int Do, int Ho, int Wo, int ksize, int stride, long s_cy, long s_cx, hipStream_t stream);
 
+/* Backward of y = conv1x1x1(x [, x2]; w) followed by z = act(BN(y)) as one pass (conv1_bwd_fused.hip): from dz, y, the
+ * BatchNorm's stats = [mean | invstd | scale | shift] and dgb (dca_bn_backward_reduce) it forms the gradient of y in
+ * registers -- the values dca_bn_backward writes as dy, never stored -- and from it
+ *   dx (N,32,S) = W[:, :32]^T dy,  dx2 (N,32,S) = W[:, 32:]^T dy (x2 != null),  dw[cy*s_cy + cx*s_cx] = sum dy[cy] x[cx]
+ * with x2's block at dw + 32*s_cx; the bits are those of dca_conv3d_wgrad (ksize 1) and of dca_conv1_x3_forward with the
+ * transposed weight (the bf16x3 product) over that dy.
+ * Cout == 32, (C1,C2) in {(32,0),(32,32)}, S % 4 == 0, dz / y / x / x2 16-byte aligned, N*32*S*4 < 0x7ffff000
+ * (hipErrorInvalidValue otherwise: callers use dca_bn_backward + dca_conv1_x3_forward + dca_conv3d_wgrad).
+ * w: the fp32 weight (32, C1+C2); part: scratch of dca_conv1_bwd_fused_workspace(N, S, x2 != null) floats. */
+long dca_conv1_bwd_fused_workspace(int N, long S, int two);
+int dca_conv1_bwd_fused(const float* dz, const float* y, const float* stats, const float* dgb, float slope, int training,
+                        const float* x, const float* x2, const float* w, float* part, float* dx, float* dx2, float* dw,
+                        long s_cy, long s_cx, int N, int C1, int C2, int Cout, long S, hipStream_t stream);
+
 /* 1x1x1 convolutions with fp32 tensors on the bf16 matrix pipe, fp32-grade (conv1_x3.hip: the exact three-way split of
  * conv3d_bf16x3.hip on an LDS-free data path): same contract as dca_conv3d_forward(ksize 1) -- x (N,C1,S) [, x2 (N,C2,S)],
  * y (N,CoutTotal,S) channels [co_off, co_off+Cout), Cout <= 32, (C1,C2) in {(32,0),(64,0),(32,32)}, S % 4 == 0.
@@ -312,6 +326,9 @@ int dca_bn_apply_pack(const float* y, const float* stats, const int* zexps, void
 int dca_bn_backward(const float* dz, const float* y, const float* res_pre, const float* stats, double* part,
                     float* dgb, float* dy, float* g_out, int N, int C, long S, float slope, int training,
                     unsigned* dmax, hipStream_t stream);
+/* the reduce and finalize passes of dca_bn_backward alone (no res_pre): dgb only, for dca_conv1_bwd_fused */
+int dca_bn_backward_reduce(const float* dz, const float* y, const float* stats, double* part, float* dgb, int N, int C,
+                           long S, float slope, int training, hipStream_t stream);
 int dca_bn_backward_pack(const float* dz, const float* y, const float* stats, double* part, float* dgb, void* dyp,
                          int* dyexps, unsigned* gmax, const unsigned* ymax, int ymax_slots, int N, int C, long S,
                          float slope, int training, hipStream_t stream);
