@@ -19,7 +19,10 @@ swapped frames gives the right view's disparity, one launch cross-checks and fil
 reference computes it).
 
 `KittiInference3D` adds the geometry stage behind any of the three: metric depth and a coloured point cloud from a
-StereoCalib, filtered by the confidence or the left-right validity."""
+StereoCalib, filtered by the confidence or the left-right validity.
+
+Every class takes `rectify=` a geometry.RectifyMaps: the pair is then a RAW camera pair, rectified on the device in one
+launch (csrc/rectify.hip) in front of the unchanged chain."""
 from __future__ import annotations
 
 import collections
@@ -27,7 +30,7 @@ import collections
 import numpy as np
 import torch
 
-from .geometry import depth_png  # noqa: F401  (the depth exporter, next to disparity_png)
+from .geometry import depth_png, rectify_pair_host  # noqa: F401  (depth_png: the depth exporter, next to disparity_png)
 from .graph import GraphedHotPath
 
 
@@ -127,6 +130,8 @@ class _Slot:
         self.uploaded, self.computed, self.done = (torch.cuda.Event() for _ in range(3))
         self.meta = None             # (h, w, c, placement, offset of the right image) of the frame in the slot
         self.as_uint16 = False
+        self.rect = {}               # channels -> the rectified pair (rectify=), allocated once for the maps' dst_hw
+        self.left = None             # the left image the frame in the slot was built from, as it lies in device memory
 
     def reserve_input(self, nbytes):
         """room for two images of nbytes each, the second at the next multiple of 16 (vector loads); returns its offset"""
@@ -136,6 +141,15 @@ class _Slot:
             self.in_pin = torch.empty(off + nbytes, dtype=torch.uint8).pin_memory()
             self.in_dev = torch.empty(off + nbytes, device=self.device, dtype=torch.uint8)
         return off
+
+    def rectified(self, hd, wd, c):
+        """the two (hd,wd,c) uint8 images `ops.rectify_pair` writes, the second at a multiple of 16 bytes (vector stores)"""
+        if c not in self.rect:
+            n = hd * wd * c
+            off = (n + 15) & ~15
+            buf = torch.empty(off + n, device=self.device, dtype=torch.uint8)
+            self.rect[c] = (buf[:n].view(hd, wd, c), buf[off:off + n].view(hd, wd, c))
+        return self.rect[c]
 
     def output(self, as_uint16, nmaps=1):
         """(device, pinned) buffers with room for `nmaps` maps (disparity[, confidence]); the maps of a frame lie back to
@@ -147,7 +161,23 @@ class _Slot:
         return self.out[dtype, nmaps]
 
 
-class KittiInference:
+class _TakesRectify(type):
+    """The keyword `rectify=` of KittiInference and every subclass is taken HERE, when the class is called, and is in place as
+    `self.rectify` before `__init__` runs: the parameter list of `KittiInference.__init__` is kept as it is (callers and
+    subclasses forward it positionally and through *args / **kwargs)."""
+
+    def __call__(cls, *args, rectify=None, **kwargs):
+        if rectify is not None and not all(hasattr(rectify, k) for k in ("src_hw", "dst_hw", "X", "Y", "valid")):
+            raise TypeError(f"rectify= must be a geometry.RectifyMaps, got {type(rectify)}")
+        obj = cls.__new__(cls)
+        obj.rectify = rectify
+        obj.__init__(*args, **kwargs)
+        if rectify is not None:
+            placement(*rectify.dst_hw, obj.crop_height, obj.crop_width)      # the rectified image must fit or cover the frame
+        return obj
+
+
+class KittiInference(metaclass=_TakesRectify):
     """`disp = KittiInference(model)(left_rgb, right_rgb)`: my_img.py:89-110 `my()` without the file I/O.
 
     `model` is a GwcNet (or the nn.DataParallel wrapper the reference builds, my_img.py:37) already on the GPU with its
@@ -157,10 +187,16 @@ class KittiInference:
     `device_io=True`: normalisation, padding, crop and the uint16 conversion run as HIP kernels; the host only copies the
     uint8 pair into pinned memory and the result out of it.  `stream(pairs)` pipelines successive frames.
 
+    `rectify=maps` (keyword, every subclass too; a geometry.RectifyMaps): the pairs handed in are RAW (maps.src_hw) and are
+    rectified first -- `ops.rectify_pair` into a per-slot device buffer with device_io, `rectify_pair_host` without -- and
+    everything behind (normalisation, placement, the maps handed out) is of the rectified images (maps.dst_hw): the result is
+    what rectifying on the host and handing the rectified pair in gives.  None (the default) changes nothing.
+
     The subclass `KittiInferenceWithConfidence` hands out `(disp, conf)` per frame (class attribute `confidence`), the
     subclass `KittiInferenceLR` `(disp_filled, valid)`: a frame's maps come from `_frame_maps`, `nmaps` of them, and go
     into the slot's output through `_export` (`KittiInference3D` adds its depth map and point cloud there)."""
 
+    rectify = None               # a geometry.RectifyMaps: set by the `rectify=` keyword before __init__ runs
     confidence = False           # True: a confidence map next to every disparity map (KittiInferenceWithConfidence)
     radius = 1                   # its window, in 1/4-res disparity bins either side of the peak
     CONF_U16_SCALE = 65535.0      # uint16 scale of the second map (a confidence in [0,1]; a 0 / 1 validity mask)
@@ -236,7 +272,10 @@ class KittiInference:
             raise ValueError(f"device_io takes two (H,W,3) or (H,W,4) uint8 images of one shape, got {left_rgb.dtype} "
                              f"{left_rgb.shape} and {right_rgb.dtype} {right_rgb.shape}")
         h, w, c = left_rgb.shape
-        place = placement(h, w, self.crop_height, self.crop_width)
+        if self.rectify is not None and (h, w) != tuple(self.rectify.src_hw):
+            raise ValueError(f"rectify= was built for {self.rectify.src_hw[0]} x {self.rectify.src_hw[1]} raw images, got "
+                             f"{h} x {w}")
+        place = placement(*((h, w) if self.rectify is None else self.rectify.dst_hw), self.crop_height, self.crop_width)
         n = h * w * c
         off = s.reserve_input(n)
         s.uploaded.synchronize()                     # the previous copy out of the pinned buffer
@@ -259,6 +298,10 @@ class KittiInference:
             compute.wait_event(s.uploaded)
             compute.wait_event(s.done)               # the previous read-back of this slot's output
             left, right = s.in_dev[:n].view(h, w, c), s.in_dev[off:off + n].view(h, w, c)
+            if self.rectify is not None:
+                h, w = self.rectify.dst_hw
+                left, right = ops.rectify_pair(left, right, self.rectify, out=s.rectified(h, w, c))
+            s.left = left
             lut, _ = ops.frame_lut(ops.frame_histogram(left, right), h * w)
             fl, fr = ops.frame_apply(left, right, lut, (self.crop_height, self.crop_width), src_y0, dst_y0, rows, cols,
                                      out=self._frames)
@@ -350,6 +393,8 @@ class KittiInference:
     def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray, as_uint16: bool = False) -> np.ndarray:
         if self.device_io:
             return self._call_device(left_rgb, right_rgb, as_uint16)
+        if self.rectify is not None:
+            left_rgb, right_rgb = rectify_pair_host(left_rgb, right_rgb, self.rectify)
         left, right, h, w = pad_or_crop(normalize_pair(left_rgb, right_rgb), self.crop_height, self.crop_width)
         dev = next(self.net.parameters()).device
         maps = self._frame_maps(left.to(dev), right.to(dev), min(w, self.crop_width))
@@ -456,7 +501,9 @@ class KittiInference3D(KittiInference):
     """`disp, mask, depth, vertices = KittiInference3D(model, calib, mask=None | "confidence" | "lr", ...)(left_rgb,
     right_rgb)`: KittiInference with device I/O (required: the colours are the uint8 left image that already lies in device
     memory) followed by the geometry stage on the same stream: `ops.disp_to_depth` and
-    `ops.point_cloud` under `calib` (a geometry.StereoCalib of the images as they are handed in), `min_disp`, `max_depth`,
+    `ops.point_cloud` under `calib` (a geometry.StereoCalib of the images as they are handed in; with `rectify=` of the rectified pair, by default the
+    maps' own `calib`, and pixels whose source footprint leaves the raw image -- `rectify.valid[0] == 0` -- get depth 0 and no
+    vertex: the validity map is the mask, or multiplies it), `min_disp`, `max_depth`,
     `stride` and, with a mask, `mask >= mask_min`.  The disparity and the mask per mode:
       None          KittiInference's disparity, no mask (`mask` of the result is None)
       "confidence"  KittiInferenceWithConfidence's disparity and window mass (`radius`)
@@ -468,10 +515,17 @@ class KittiInference3D(KittiInference):
     count is on the host -- one copy of exactly count * 16 bytes of vertices: ONE more host wait per frame than the other
     classes have, on that frame's own copy only; in `stream()` the later frames keep computing meanwhile."""
 
-    def __init__(self, model, calib, *args, mask=None, mask_min: float = 0.5, min_disp: float = 0.0,
+    def __init__(self, model, calib=None, *args, mask=None, mask_min: float = 0.5, min_disp: float = 0.0,
                  max_depth: float = 80.0, stride: int = 1, radius: int = 1, tau: float = 1.0, **kwargs):
         from . import ops
         super().__init__(model, *args, **kwargs)
+        if calib is None:
+            calib = getattr(self.rectify, "calib", None)
+            if calib is None:
+                raise ValueError("KittiInference3D needs calib=, or rectify= maps that carry the rectified pair's calibration")
+        if self.rectify is not None and not float(mask_min) > 0.0:
+            raise ValueError("with rectify= the maps' validity (0 / 1) enters the mask: mask_min must be > 0")
+        self._valid_frame = None     # rectify=: valid[0] placed in the frame, float32 (Hc,Wc), built once
         if not self.device_io:
             raise ValueError("KittiInference3D needs device_io=True: the point colours are read from the uint8 image on the device")
         if mask not in (None, "confidence", "lr"):
@@ -511,9 +565,20 @@ class KittiInference3D(KittiInference):
         for m, out in zip((pred, mask) if mask is not None else (pred,), views):
             ops.disp_export(m, dst_y0, rows, cols, out_f32=out)
         window = (dst_y0, rows, cols)
+        if self.rectify is not None:     # a pixel without a full source footprint is no measurement (the maps handed out stay as they are)
+            valid = self._valid(pred.device, src_y0, dst_y0, rows, cols).view_as(pred)
+            mask = valid if mask is None else mask * valid
         ops.disp_to_depth(pred, self.calib, window, mask, out_f32=views[-1], **self.filters)
-        ops.point_cloud(pred, self.calib, s.in_dev[:h * w * c].view(h, w, c), mask, window, v0=src_y0, stride=self.stride,
+        ops.point_cloud(pred, self.calib, s.left, mask, window, v0=src_y0, stride=self.stride,
                         out=g.vert_dev, workspace=(g.offsets, g.count), **self.filters)
+
+    def _valid(self, device, src_y0, dst_y0, rows, cols):
+        """rectify.valid[0] as a float32 mask placed in the frame like the image; built once (the frame size is fixed)"""
+        if self._valid_frame is None or self._valid_frame.device != device:
+            frame = np.zeros((self.crop_height, self.crop_width), np.float32)
+            frame[dst_y0:dst_y0 + rows, :cols] = self.rectify.valid[0][src_y0:src_y0 + rows, :cols]
+            self._valid_frame = torch.from_numpy(frame).to(device)
+        return self._valid_frame
 
     def _readback(self, s, copy):
         """`copy` stream: the count and the maps -> pinned, one copy"""

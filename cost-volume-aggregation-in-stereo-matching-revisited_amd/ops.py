@@ -2333,6 +2333,57 @@ def disp_export(pred, y0, h, w, scale=256.0, f32=True, u16=False, out_f32=None, 
 
 
 # ------------------------------------------------------------------------------------------------
+# Rectification of a raw pair in front of the frame I/O (csrc/rectify.hip): one launch gathers both
+# images through the fixed-point maps of a geometry.RectifyMaps.  No launch synchronises.
+# ------------------------------------------------------------------------------------------------
+RECT_MAX_SRC = _C["DCA_RECT_MAX_SRC"]
+
+
+def _overlap(a, b):
+    return a.data_ptr() < b.data_ptr() + b.numel() * b.element_size() and \
+        b.data_ptr() < a.data_ptr() + a.numel() * a.element_size()
+
+
+def rectify_pair(left_u8, right_u8, maps, out=None):
+    """The raw (Hs,Ws,C) uint8 pair, C = 3 or 4, through `maps` (a geometry.RectifyMaps with src_hw == (Hs,Ws)) -> the two
+    rectified (Hd,Wd,C) uint8 images, one launch: bilinear with 5 fractional bits per axis, zero outside the source, a
+    fourth channel 255 (definitions: include/dca_hip.h, dca_rectify_pair; geometry.rectify_pair_host is the numpy
+    restatement, equal bit for bit).  out: a (2,Hd,Wd,C) uint8 buffer or a pair of (Hd,Wd,C) buffers to write into, which
+    must not overlap the inputs or each other.  With `out` given and the maps already on the device (their first use uploads
+    them) nothing is allocated and the host never waits: the launch can be captured into a hipGraph."""
+    name = "rectify_pair"
+    Hs, Ws, C = _req_u8_pair(left_u8, right_u8, name)
+    if not hasattr(maps, "device_maps") or not hasattr(maps, "src_hw"):
+        raise RuntimeError(f"{name}: maps must be a geometry.RectifyMaps, got {type(maps)}")
+    if (Hs, Ws) != tuple(maps.src_hw):
+        raise RuntimeError(f"{name}: the maps were built for {maps.src_hw[0]} x {maps.src_hw[1]} images, got {Hs} x {Ws}")
+    if left_u8.device != right_u8.device:
+        raise RuntimeError(f"{name}: the two images must be on one device")
+    Hd, Wd = maps.dst_hw
+    if max(Hs, Ws) > RECT_MAX_SRC or Hs * Ws * C >= 1 << 31 or Hd * Wd * C >= 1 << 31:
+        raise RuntimeError(f"{name}: the source may be at most {RECT_MAX_SRC} x {RECT_MAX_SRC} and every image must stay "
+                           "below 2^31 bytes")
+    if out is None:
+        out = torch.empty((2, Hd, Wd, C), device=left_u8.device, dtype=torch.uint8)
+    if not isinstance(out, (torch.Tensor, tuple, list)) or len(out) != 2:
+        raise RuntimeError(f"{name}: out must be a (2,{Hd},{Wd},{C}) uint8 buffer or a pair of ({Hd},{Wd},{C}) buffers")
+    ol, orr = out[0], out[1]
+    for t, what in ((ol, "out[0]"), (orr, "out[1]")):
+        _req_dev(t, name, what, torch.uint8, (Hd, Wd, C))
+        if t.device != left_u8.device:
+            raise RuntimeError(f"{name}: {what} must be on the images' device")
+        if _overlap(t, left_u8) or _overlap(t, right_u8):
+            raise RuntimeError(f"{name}: {what} must not alias an input image")
+    if _overlap(ol, orr):
+        raise RuntimeError(f"{name}: out[0] and out[1] must not alias each other")
+    dmaps, plane = maps.device_maps(left_u8.device)
+    with torch.cuda.device_of(left_u8):
+        _chk(_L().dca_rectify_pair(_ptr(left_u8), _ptr(right_u8), _ptr(dmaps), plane, _ptr(ol), _ptr(orr), Hs, Ws, Hd, Wd, C,
+                                   _stream()), "dca_rectify_pair")
+    return ol, orr
+
+
+# ------------------------------------------------------------------------------------------------
 # Training inputs (dataloader/datasets.py:221-254, 270-317 after the decode): photometric augmentation as one byte table
 # per image, crop, occlusion patch, normalisation, ground-truth crop and mask (csrc/train_io.hip).  No launch synchronises;
 # dcanet_amd.training holds the numpy restatements and the TrainInput / TrainStep classes built on these.

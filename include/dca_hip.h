@@ -714,6 +714,26 @@ int dca_selfsup_loss_bwd(const float* left, const float* right, const float* con
                          const float* gloss, int B, int H, int W, float alpha, float lam, float c1, float c2,
                          float photo_scale, hipStream_t stream);
 
+/* ---- stereo rectification of a raw pair (rectify.hip); inference only, no counterpart in the reference --
+ * dca_rectify_pair: ONE launch remaps both images.  left, right: (Hs,Ws,C) interleaved uint8, C = 3 or 4; out_left,
+ * out_right: (Hd,Wd,C); maps: four planes of map_plane words each, X_left, Y_left, X_right, Y_right, the first Hd Wd words
+ * of a plane the source coordinates of the destination pixels in row-major order with DCA_RECT_FRAC_BITS fractional bits
+ * (geometry.RectifyMaps builds them on the host); map_plane >= Hd Wd and a multiple of 4, so that a 16-byte aligned maps
+ * keeps every 4-pixel group of every plane aligned.  Per destination pixel with map entry (X, Y):
+ *   x0 = X >> 5, a = X & 31, y0 = Y >> 5, b = Y & 31        (arithmetic shift; any int32 is legal)
+ *   out_c = ((32-a)(32-b) p(y0,x0) + a(32-b) p(y0,x0+1) + (32-a) b p(y0+1,x0) + a b p(y0+1,x0+1) + 512) >> 10,  c < 3
+ * where p(r, x) is source byte c of pixel (r, x) and 0 outside [0,Hs) x [0,Ws) (constant-zero border); a fourth channel is
+ * written as 255.  Integer arithmetic only, no atomics: bitwise defined (geometry.rectify_pair_host is the numpy
+ * restatement).  A thread writes 4 consecutive destination pixels as one 12- / 16-byte group when maps is 16-byte aligned and
+ * the view's output base is 4-byte (C = 3) / 16-byte (C = 4) aligned, byte by byte otherwise and at the image's tail.
+ * Refused: NULL pointers, C outside {3, 4}, non-positive sizes, Hs or Ws > DCA_RECT_MAX_SRC, an image of 2^31 bytes or more
+ * (offsets are 32-bit).  The outputs must not alias the inputs or each other. */
+#define DCA_RECT_FRAC_BITS 5
+#define DCA_RECT_MAX_SRC 16384
+int dca_rectify_pair(const unsigned char* left, const unsigned char* right, const int* maps, long map_plane,
+                     unsigned char* out_left, unsigned char* out_right, int Hs, int Ws, int Hd, int Wd, int C,
+                     hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
