@@ -1452,6 +1452,11 @@ def convbn3d(x, conv, bn, slope=1.0, res_pre=None, res_post=None, x2=None, alias
     if not transposed and _lp_dtype() is None and _c1_bwd_route(x, x2, conv.weight, res_pre) == "fused":
         y = _Conv3d.apply(x, x2, conv.weight, int(stride), False, False, False, False, True)   # eval-mode BatchNorm under grad
         return bn_act(y, bn, slope, res_pre, res_post, lazy_dy=True)
+    if _is_packed(x) and _pack_dy_ok(x, x2, conv, transposed, stride, res_pre):
+        # DCA_BN_FUSE=0: the alias node before this layer packs its output all the same, and a packed x pairs only with a
+        # packed gradient in the weight-gradient kernel at W % 4 != 0 (_x2_pairs): hand it one, as the branch above does
+        y = _Conv3d.apply(x, x2, conv.weight, int(stride), bool(transposed), False, False, True)
+        return bn_act(y, bn, slope, res_pre, res_post, pack_dy=True)
     y = conv3d(x, conv.weight, stride, transposed, x2)
     return bn_act(y, bn, slope, res_pre, res_post)
 
