@@ -226,12 +226,16 @@ class EvalStep:
     dca_disp_metrics and dca_eval_accumulate follow the up-sampler as plain launches on the same stream.
     dtype: None (fp32) or torch.float16 / torch.bfloat16 (ops.reduced_precision; the region volumes stay fp32).
     The metric launches are bitwise reproducible; whole steps repeat bit for bit when the 2D networks' MIOpen
-    convolutions do (torch.backends.cudnn.deterministic = True)."""
+    convolutions do (torch.backends.cudnn.deterministic = True).
+    error_images=True: one more launch per step (`ops.disp_error_image` behind `ops.disp_metrics`, same stream, same pred, gt
+    and pads; a plain launch with graph=True too) leaves the batch's KITTI error maps in `last["error_image"]`, (B,H,W,3) uint8
+    with the colour key; nothing is read back and the run state is bitwise the same with or without."""
 
-    def __init__(self, model, maxdisp=192, graph=False, dtype=None):
+    def __init__(self, model, maxdisp=192, graph=False, dtype=None, error_images=False):
         self.net = model.module if isinstance(model, torch.nn.DataParallel) else model
         self.net.eval()
         self.maxdisp, self.graph, self.dtype = maxdisp, graph, dtype
+        self.error_images = bool(error_images)
         self._tail = _HotPathWithConfusion(self.net)
         self._graphed = {}
         self.state = ops.eval_state(self.net.maxdisp // 8, next(self.net.parameters()).device)
@@ -265,6 +269,8 @@ class EvalStep:
         ops.eval_accumulate(self.state, rec, r["cm"], gt.shape)
         self.last = {"pred": pred, "rec": rec, "cm": r["cm"], "volumes": r["volumes"], "top_pad": top_pad,
                      "right_pad": right_pad}
+        if self.error_images:
+            self.last["error_image"] = ops.disp_error_image(pred, gt, f32=False, u8=True)[1]
 
     def result(self):
         """one device -> host copy; across ranks call `all_reduce_state(ev.state)` first"""

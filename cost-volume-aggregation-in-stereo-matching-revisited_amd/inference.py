@@ -21,6 +21,9 @@ reference computes it).
 `KittiInference3D` adds the geometry stage behind any of the three: metric depth and a coloured point cloud from a
 StereoCalib, filtered by the confidence or the left-right validity.
 
+`KittiInferenceColor` hands out the colour-coded disparity map (the KITTI devkit's colours, or grey) next to the disparity,
+coloured on the device in one launch behind any of the three (csrc/visualize.hip).
+
 Every class takes `rectify=` a geometry.RectifyMaps: the pair is then a RAW camera pair, rectified on the device in one
 launch (csrc/rectify.hip) in front of the unchanged chain."""
 from __future__ import annotations
@@ -614,6 +617,124 @@ class KittiInference3D(KittiInference):
 
     def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray) -> Frame3D:
         return self._call_device(left_rgb, right_rgb, False)
+
+
+class _Color:
+    """Per-slot buffers of KittiInferenceColor, allocated once for the frame size: the float32 disparity of a rows x cols
+    window at byte 0, its uint8 RGB image behind it at byte 4 rows cols -- one copy brings both to the host."""
+
+    def __init__(self, device, crop_height, crop_width):
+        nbytes = 7 * crop_height * crop_width
+        self.dev = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        self.pin = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+
+    @staticmethod
+    def views(buf, rows, cols):
+        n = rows * cols
+        return buf[:4 * n].view(torch.float32).view(rows, cols), buf[4 * n:7 * n].view(rows, cols, 3)
+
+
+class KittiInferenceColor(KittiInference):
+    """`disp, rgb = KittiInferenceColor(model, cmap="kitti", max_disp=None, mask=None | "confidence" | "lr", ...)(left_rgb,
+    right_rgb)`: KittiInference with device I/O (required: the picture is made where the disparity lies) followed by one
+    launch of `ops.disp_colorize` on the same stream.  `disp` is float32 (h,w), bitwise
+    KittiInference's; `rgb` is uint8 (h,w,3), the same window (`color_png` stores it as it is).
+      cmap       "kitti": the KITTI devkit's disp_to_color; "gray"
+      max_disp   None: the model's `maxdisp`; a number: t = min(d / max_disp, 1); "auto": every frame is ranged over its own
+                 valid pixels by `ops.disp_range` on the device, and the launch reads the pair from device memory
+      mask       None; "confidence": KittiInferenceWithConfidence's window mass (`radius`), pixels below `mask_min` are black;
+                 "lr": the validity map of the left-right check (`tau`; two passes per frame), invalid pixels are black and the
+                 disparity is the UNFILLED one
+    Pixels whose disparity is not finite or not > 0 are black.  Both maps come back in one copy and one synchronisation per
+    frame."""
+
+    def __init__(self, model, *args, cmap: str = "kitti", max_disp=None, mask=None, mask_min: float = 0.5, radius: int = 1,
+                 tau: float = 1.0, device_io: bool = True, **kwargs):
+        if len(args) < 5:                # (KittiInference takes device_io as its fifth positional argument)
+            kwargs["device_io"] = device_io
+        super().__init__(model, *args, **kwargs)
+        if not self.device_io:
+            raise ValueError("KittiInferenceColor needs device_io=True: the map is coloured on the device, next to the disparity")
+        if cmap not in ("kitti", "gray"):
+            raise ValueError(f"cmap is 'kitti' or 'gray', got {cmap!r}")
+        if mask not in (None, "confidence", "lr"):
+            raise ValueError(f"mask is None, 'confidence' or 'lr', got {mask!r}")
+        if max_disp is None:
+            max_disp = getattr(self.net, "maxdisp", None)
+            if max_disp is None:
+                raise ValueError("KittiInferenceColor needs max_disp=: the model has no `maxdisp`")
+        if max_disp != "auto":
+            max_disp = float(max_disp)
+            if not 0.0 < max_disp < float("inf"):
+                raise ValueError(f"max_disp is 'auto' or a positive, finite number, got {max_disp}")
+        if int(radius) < 0 or float(mask_min) != float(mask_min):
+            raise ValueError("radius >= 0 and mask_min must not be NaN")
+        self.cmap, self.max_disp, self.mask_mode, self.mask_min = cmap, max_disp, mask, float(mask_min)
+        self.radius, self.tau = int(radius), _check_tau(tau)
+        self.confidence = mask == "confidence"
+        self._mirrored = None
+
+    @property
+    def nmaps(self):
+        """the network's maps per frame: the disparity[, the mask]"""
+        return 1 if self.mask_mode is None else 2
+
+    def _frame_maps(self, left, right, cols):
+        if self.mask_mode == "lr":
+            disp, r = _lr_maps(self, left, right, cols, ("valid",))
+            return disp, r["valid"]
+        return super()._frame_maps(left, right, cols)
+
+    def _color(self, s):
+        if getattr(s, "color", None) is None:
+            s.color = _Color(s.device, self.crop_height, self.crop_width)
+        return s.color
+
+    def _export(self, s, maps, as_uint16):
+        from . import ops
+        dst_y0, rows, cols = s.meta[3][1:]
+        out_disp, out_rgb = _Color.views(self._color(s).dev, rows, cols)
+        pred = maps[0].contiguous()
+        mask = maps[1].contiguous().view_as(pred) if len(maps) > 1 else None
+        ops.disp_export(pred, dst_y0, rows, cols, out_f32=out_disp)
+        scale = {"max_disp": self.max_disp}
+        if self.max_disp == "auto":
+            scale = {"range": ops.disp_range(pred, (dst_y0, rows, cols), mask, self.mask_min)}
+        ops.disp_colorize(pred, dst_y0, rows, cols, cmap=self.cmap, mask=mask, mask_min=self.mask_min, out=out_rgb, **scale)
+
+    def _readback(self, s, copy):
+        """`copy` stream: the disparity and the picture -> pinned, one copy"""
+        rows, cols = s.meta[3][2:]
+        c = self._color(s)
+        n = 7 * rows * cols
+        with torch.cuda.stream(copy):
+            copy.wait_event(s.computed)
+            c.pin[:n].copy_(c.dev[:n], non_blocking=True)
+            s.done.record(copy)
+
+    def _result(self, s):
+        rows, cols = s.meta[3][2:]
+        s.done.synchronize()
+        disp, rgb = _Color.views(self._color(s).pin, rows, cols)
+        return disp.numpy().copy(), rgb.numpy().copy()
+
+    def stream(self, pairs, depth: int = 2):
+        """Generator of (disp, rgb) tuples in input order, `depth` frames in flight, each equal byte for byte to the
+        one-at-a-time call."""
+        return super().stream(pairs, depth, False)
+
+    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray):
+        return self._call_device(left_rgb, right_rgb, False)
+
+
+def color_png(path: str, rgb: np.ndarray) -> None:
+    """8-bit RGB PNG of a colour image as KittiInferenceColor / `ops.disp_colorize` / `ops.disp_error_image(u8=True)` hand
+    it out: uint8 (h,w,3)."""
+    from PIL import Image
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"color_png takes a uint8 (h,w,3) image, got {rgb.dtype} {rgb.shape}")
+    Image.fromarray(np.ascontiguousarray(rgb), "RGB").save(path, format="PNG")
 
 
 def confidence_png(path: str, conf: np.ndarray) -> None:

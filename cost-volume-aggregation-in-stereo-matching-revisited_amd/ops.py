@@ -2640,3 +2640,121 @@ def point_cloud(pred, calib, rgb=None, mask=None, window=None, v0=0, stride=1, c
                                   _ptr(count), Hc, Wc, y0, rows, cols, v0, stride, f, fb, cx, cy, doffs, min_disp, max_depth,
                                   mask_min, _stream()), "dca_point_cloud")
     return out[:cap], count, offs[:tiles + 1]
+
+
+# ------------------------------------------------------------------------------------------------
+# Pictures of a disparity map (csrc/visualize.hip): the KITTI error map of a prediction against the
+# ground truth (utils/visualization.py:31-55) and the colour-coded disparity map, uint8 RGB on the device.  No launch
+# synchronises; definitions: include/dca_hip.h.
+# ------------------------------------------------------------------------------------------------
+CMAPS = {"gray": _C["DCA_CMAP_GRAY"], "kitti": _C["DCA_CMAP_KITTI"]}
+
+
+def disp_error_image(pred, gt, abs_thres=3.0, rel_thres=0.05, legend=True, f32=True, u8=False, out_f32=None, out_u8=None):
+    """The KITTI error map of a (padded) prediction against the ground truth in one launch (the reference's
+    disp_error_image_func.forward, utils/visualization.py:31-55): pred (B,Hp,Wp) or (B,1,Hp,Wp) with Hp >= H, Wp >= W (rows
+    padded on top, columns on the right, cropped by addressing as in `disp_metrics`), gt (B,H,W).  Returns (float32 planar
+    (B,3,H,W) in [0,1] -- the reference's result -- or None, uint8 interleaved (B,H,W,3) or None); out_f32 / out_u8: buffers
+    of those shapes to write into.  legend: the colour key in the top-left corner (the reference always draws it)."""
+    name = "disp_error_image"
+    pred, gt = _req(pred, name), _req(gt, name)
+    if pred.dim() == 4 and pred.shape[1] == 1:
+        pred = pred[:, 0]
+    if pred.dim() != 3 or gt.dim() != 3 or pred.shape[0] != gt.shape[0] or gt.numel() == 0:
+        raise RuntimeError(f"{name}: expected pred (B,Hp,Wp) and gt (B,H,W), got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    (B, Hp, Wp), (H, W) = pred.shape, gt.shape[1:]
+    if Hp < H or Wp < W:
+        raise RuntimeError(f"{name}: the prediction is smaller than the ground truth")
+    if B * Hp * Wp >= 1 << 31:
+        raise RuntimeError(f"{name}: B * Hp * Wp must stay below 2^31")
+    abs_thres, rel_thres = float(abs_thres), float(rel_thres)
+    if not (0.0 < abs_thres < math.inf and 0.0 < rel_thres < math.inf):
+        raise RuntimeError(f"{name}: abs_thres and rel_thres must be positive and finite, got {abs_thres} and {rel_thres}")
+    if not (f32 or u8):
+        raise RuntimeError(f"{name}: nothing to compute (f32 and u8 are both off)")
+    of = ou = None
+    if f32:
+        of = torch.empty((B, 3, H, W), device=gt.device, dtype=torch.float32) if out_f32 is None else \
+            _req_dev(out_f32, name, "out_f32", torch.float32, (B, 3, H, W))
+    if u8:
+        ou = torch.empty((B, H, W, 3), device=gt.device, dtype=torch.uint8) if out_u8 is None else \
+            _req_dev(out_u8, name, "out_u8", torch.uint8, (B, H, W, 3))
+    with torch.cuda.device_of(gt):
+        _chk(_L().dca_disp_error_image(_ptr(pred), _ptr(gt), _ptr(of), _ptr(ou), B, H, W, Hp - H, Wp - W, abs_thres, rel_thres,
+                                       1 if legend else 0, _stream()), "dca_disp_error_image")
+    return of, ou
+
+
+def _vis_maps(name, disp, mask, batched):
+    """the float32 map(s) and the optional mask of the same shape: (B, Hc, Wc) of a batch, or of ONE frame (B = 1)"""
+    _req_no_grad(name, disp, mask)
+    _req_dev(disp, name, "the disparity", torch.float32)
+    if disp.dim() < 2 or disp.numel() == 0:
+        raise RuntimeError(f"{name}: expected a (Hc,Wc) map{' or a (B,Hc,Wc) batch' if batched else ''}, got {tuple(disp.shape)}")
+    Hc, Wc = int(disp.shape[-2]), int(disp.shape[-1])
+    B = disp.numel() // (Hc * Wc)
+    if not batched and B != 1:
+        raise RuntimeError(f"{name}: expected the (Hc,Wc) map of one frame, got {tuple(disp.shape)}")
+    if mask is not None:
+        _req_f32_same(name, disp, mask, "the disparity and the mask")
+    if B > 65535 or B * Hc * Wc >= 1 << 31:
+        raise RuntimeError(f"{name}: at most 65535 maps and fewer than 2^31 pixels")
+    return B, Hc, Wc
+
+
+def _vis_mask_min(name, mask, mask_min):
+    mask_min = float(mask_min)
+    if mask is not None and math.isnan(mask_min):
+        raise RuntimeError(f"{name}: mask_min must not be NaN")
+    return mask_min
+
+
+def disp_range(disp, window=None, mask=None, mask_min=0.5):
+    """(lo, hi) of the valid pixels of the window (y0, rows, cols) (default: everything) of every map of disp (Hc,Wc) /
+    (B,Hc,Wc) / (B,1,Hc,Wc): finite, > 0 and, with a float32 mask shaped like disp, mask >= mask_min.  Returns (B,2)
+    float32 on the device, (0, 0) for a map without a valid pixel; two launches, nothing is read back; bitwise
+    reproducible."""
+    name = "disp_range"
+    B, Hc, Wc = _vis_maps(name, disp, mask, True)
+    y0, rows, cols = (0, Hc, Wc) if window is None else (int(v) for v in window)
+    if y0 < 0 or rows <= 0 or cols <= 0 or y0 + rows > Hc or cols > Wc:
+        raise RuntimeError(f"{name}: the {rows} x {cols} window at row {y0} does not fit the {Hc} x {Wc} map")
+    mask_min = _vis_mask_min(name, mask, mask_min)
+    out = torch.empty((B, 2), device=disp.device, dtype=torch.float32)
+    with torch.cuda.device_of(disp):
+        ws = torch.empty(_L().dca_disp_range_workspace(B, rows, cols), device=disp.device, dtype=torch.uint8)
+        _chk(_L().dca_disp_range(_ptr(disp), _ptr(mask), _ptr(out), _ptr(ws), B, Hc, Wc, y0, rows, cols, mask_min, _stream()),
+             "dca_disp_range")
+    return out
+
+
+def disp_colorize(disp, y0, rows, cols, max_disp=None, range=None, cmap="kitti", mask=None, mask_min=0.5, out=None):
+    """The rows x cols window at row y0, column 0 of ONE map (Hc,Wc) / (1,1,Hc,Wc) as a colour image, one launch: uint8
+    (rows,cols,3) on the device.  Exactly one of max_disp (a host number: t = min(d / max_disp, 1), the KITTI devkit's
+    scaling) and range (the (1,2) / (2,) device tensor (lo, hi) of `disp_range`: auto-ranging without a read-back) must be
+    given.  cmap: "kitti" (the devkit's disp_to_color) or "gray".  Pixels that are not finite, not > 0 or, with a float32 mask
+    shaped like disp, below mask_min are black.  out: a (rows,cols,3) uint8 buffer to write into."""
+    name = "disp_colorize"
+    if cmap not in CMAPS:
+        raise ValueError(f"{name}: cmap is one of {sorted(CMAPS)}, got {cmap!r}")
+    _, Hc, Wc = _vis_maps(name, disp, mask, False)
+    y0, rows, cols = int(y0), int(rows), int(cols)
+    if y0 < 0 or rows <= 0 or cols <= 0 or y0 + rows > Hc or cols > Wc:
+        raise RuntimeError(f"{name}: the {rows} x {cols} window at row {y0} does not fit the {Hc} x {Wc} map")
+    if (max_disp is None) == (range is None):
+        raise RuntimeError(f"{name}: give exactly one of max_disp and range")
+    if range is not None:
+        _req_dev(range, name, "range", torch.float32)
+        if range.numel() != 2 or range.device != disp.device:
+            raise RuntimeError(f"{name}: range must hold (lo, hi) on the map's device, got {tuple(range.shape)}")
+        max_disp = 0.0
+    elif not 0.0 < float(max_disp) < math.inf:
+        raise RuntimeError(f"{name}: max_disp must be positive and finite, got {max_disp}")
+    mask_min = _vis_mask_min(name, mask, mask_min)
+    if out is None:
+        out = torch.empty((rows, cols, 3), device=disp.device, dtype=torch.uint8)
+    _req_dev(out, name, "out", torch.uint8, (rows, cols, 3))
+    with torch.cuda.device_of(disp):
+        _chk(_L().dca_disp_colorize(_ptr(disp), _ptr(mask), _ptr(range), _ptr(out), Hc, Wc, y0, rows, cols, float(max_disp),
+                                    mask_min, CMAPS[cmap], _stream()), "dca_disp_colorize")
+    return out

@@ -1,5 +1,6 @@
 """Mirror of the reference's `utils` package for what the training scripts use on this path
-(`from utils import *`, main_dca.py:11): the learning-rate schedule, the disparity metrics and `loss_disp_smoothness` (util.py:76-86, which the
+(`from utils import *`, main_dca.py:11): the learning-rate schedule, the disparity metrics, the KITTI error map of
+utils/visualization.py (with the colour-coded disparity map next to it) and `loss_disp_smoothness` (util.py:76-86, which the
 reference defines and never calls)."""
 from .experiment import adjust_learning_rate, learning_rate_adjust  # noqa: F401
 from .metrics import D1_metric, EPE_metric, Thres_metric  # noqa: F401
@@ -17,6 +18,10 @@ def _package():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod.ensure()
+
+
+from .visualization import (disp_error_image, disp_error_image_func, disp_to_color, error_colormap,  # noqa: E402,F401
+                            gen_error_colormap)
 
 
 def loss_disp_smoothness(disp, img):

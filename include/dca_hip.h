@@ -734,6 +734,72 @@ int dca_rectify_pair(const unsigned char* left, const unsigned char* right, cons
                      unsigned char* out_left, unsigned char* out_right, int Hs, int Ws, int Hd, int Wd, int C,
                      hipStream_t stream);
 
+/* ---- pictures of a disparity map (visualize.hip): uint8 RGB next to the maps, no host round trip -----
+ * Everything below is evaluated in fp32, every operation rounded on its own (no fused multiply-adds), IEEE division, so the
+ * results are bitwise defined; tests/_vis_reference.py is the numpy restatement.  No atomics.
+ *
+ * dca_disp_error_image: ONE launch, the reference's disp_error_image_func.forward (utils/visualization.py:31-55).  pred
+ * (B,H+top_pad,W+right_pad) fp32 -- the padded frame, cropped `[:, top_pad:, :W]` by addressing as dca_disp_metrics does --
+ * gt (B,H,W) fp32.  Per pixel:
+ *   mask = gt > 0;   e = |gt - pred|;   err = min(e / abs_thres, (e / gt) / rel_thres)      (a NaN stays a NaN, as np.minimum)
+ *   bin i of DCA_ERRMAP_BINS has 2^(i-5) <= err < 2^(i-4), bin 0 starting at 0 and the last one open: the edges
+ *   0, 1/16, 1/8, 1/4, 1/2, 1, 2, 4, 8, 16, +inf of visualization.py:13-22; its colour is DCA_ERRMAP_RGB_i (0xRRGGBB)
+ * A pixel outside the mask, or whose err lies in no bin (NaN; +inf, because inf < inf is false) is black.  With legend = 1
+ * the pixels of rows < DCA_ERRMAP_LEGEND_ROWS and columns < DCA_ERRMAP_BINS DCA_ERRMAP_LEGEND_STEP take the colour of bin
+ * column / DCA_ERRMAP_LEGEND_STEP, over everything else, clipped to the image (visualization.py:51-53).  The reference's
+ * dilate_radius is a TODO there and has no counterpart here.
+ * out_f32: planar (B,3,H,W), float(byte) / 255.0f (the reference's layout and values); out_u8: interleaved (B,H,W,3), the
+ * byte itself (what an image encoder takes).  Either may be NULL, not both.  Refused: NULL inputs, non-positive sizes,
+ * negative pads, B (H + top_pad) (W + right_pad) >= 2^31, thresholds that are not positive and finite, legend outside {0, 1}. */
+#define DCA_ERRMAP_BINS 10
+#define DCA_ERRMAP_RGB_0 0x313695
+#define DCA_ERRMAP_RGB_1 0x4575B4
+#define DCA_ERRMAP_RGB_2 0x74ADD1
+#define DCA_ERRMAP_RGB_3 0xABD9E9
+#define DCA_ERRMAP_RGB_4 0xE0F3F8
+#define DCA_ERRMAP_RGB_5 0xFEE090
+#define DCA_ERRMAP_RGB_6 0xFDAE61
+#define DCA_ERRMAP_RGB_7 0xF46D43
+#define DCA_ERRMAP_RGB_8 0xD73027
+#define DCA_ERRMAP_RGB_9 0xA50026
+#define DCA_ERRMAP_LEGEND_ROWS 10
+#define DCA_ERRMAP_LEGEND_STEP 20
+int dca_disp_error_image(const float* pred, const float* gt, float* out_f32, unsigned char* out_u8, int B, int H, int W,
+                         int top_pad, int right_pad, float abs_thres, float rel_thres, int legend, hipStream_t stream);
+/* dca_disp_range: disp (B,Hc,Wc) fp32, mask (B,Hc,Wc) fp32 or NULL; the window is rows x cols pixels from row y0, column 0
+ * of every image, as in dca_disp_export.  range: (B,2) fp32 = (lo, hi), the minimum and maximum over the window's VALID
+ * pixels: finite, > 0 and, with a mask, mask >= mask_min; (0, 0) for an image without one.  TWO launches: one (min, max) pair
+ * per workgroup into workspace (dca_disp_range_workspace(B, rows, cols) bytes), then one wave per image; min and max do not
+ * depend on the order, so the result is bitwise reproducible.  B <= 65535, B Hc Wc < 2^31. */
+long dca_disp_range_workspace(int B, int rows, int cols);
+int dca_disp_range(const float* disp, const float* mask, float* range, void* workspace, int B, int Hc, int Wc, int y0,
+                   int rows, int cols, float mask_min, hipStream_t stream);
+/* dca_disp_colorize: ONE launch colours the rows x cols window at row y0, column 0 of ONE map disp (Hc,Wc) fp32 into out_u8
+ * (rows,cols,3) interleaved.  The range is the device pair range = (lo, hi) dca_disp_range wrote (nothing is read back), or,
+ * with range NULL, lo = 0 and hi = max_disp (> 0, finite: the KITTI devkit's min(D / max_disp, 1)).  A pixel that is not
+ * valid (as in dca_disp_range) is (0,0,0); for the others, in this operation order,
+ *   t = min(max((d - lo) / max(hi - lo, 1e-5f), 0), 1)
+ *   DCA_CMAP_GRAY:   r = g = b = rintf(t * 255)
+ *   DCA_CMAP_KITTI:  the devkit's disp_to_color.  s = t * 1000; C[k] = DCA_KITTI_EDGE_k, k = 0..7; ind = the number of k in
+ *                    1..6 with s > C[k];  w = (s - C[ind]) / (C[ind + 1] - C[ind])  (the widths 114, 185, 114, 174, 114, 185,
+ *                    114 are exact);  corner k is nibble k of DCA_KITTI_CORNERS, bits (r g b): 000, 001, 100, 101, 010, 011,
+ *                    110, 111;  a channel whose corners ind and ind + 1 agree has that value v, a rising one v = w, a falling
+ *                    one v = 1 - w;  byte = rintf(v * 255)
+ * A range that is not finite gives unspecified colours, never a fault. */
+#define DCA_CMAP_GRAY 0
+#define DCA_CMAP_KITTI 1
+#define DCA_KITTI_EDGE_0 0
+#define DCA_KITTI_EDGE_1 114
+#define DCA_KITTI_EDGE_2 299
+#define DCA_KITTI_EDGE_3 413
+#define DCA_KITTI_EDGE_4 587
+#define DCA_KITTI_EDGE_5 701
+#define DCA_KITTI_EDGE_6 886
+#define DCA_KITTI_EDGE_7 1000
+#define DCA_KITTI_CORNERS 0x76325410
+int dca_disp_colorize(const float* disp, const float* mask, const float* range, unsigned char* out_u8, int Hc, int Wc, int y0,
+                      int rows, int cols, float max_disp, float mask_min, int cmap, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
