@@ -35,9 +35,7 @@ constexpr int MAXCH = 8;   // 16-channel chunks over both inputs (Cin <= 128)
 // S % 4 == 0 and 8-byte aligned bases (the caller checks); OUT32: fp32 output and residuals
 // two workgroups per CU (<= 256 registers per lane): 59.6 -> 41.9 us (32->32) and 66.5 -> 53.4 us (64->32, two inputs) at
 // 48x136x240 -- 4.8 / 5.6 TB/s; three or four per CU make hipcc spill (82 / 161 us)
-#ifndef C1_OCC
-#define C1_OCC 2
-#endif
+constexpr int C1_OCC = 2;
 template <typename MT, bool OUT32>
 __global__ __launch_bounds__(256, C1_OCC) void conv1_lp_kernel(C1LpArgs a) {
   typedef typename Lp<MT>::vec8 vec8;

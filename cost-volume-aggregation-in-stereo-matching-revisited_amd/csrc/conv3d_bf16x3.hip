@@ -22,28 +22,17 @@
 // channel chunk is three phases of 108 MFMAs per wave with one barrier each; the next slab / next halo tile are
 // fetched into registers (hardware-predicated buffer loads) while the current phase's MFMAs run.
 #include "dca_frag.h"
+#include "dca_tiles.h"
 #include "bn_fused_stats.h"
 #include <type_traits>
 
-// Non-temporal output stores (X3_NT=1): y is written once, so it need not displace the halo lines the neighbouring tiles
-// re-read from this XCD's L2 -- 591 -> 568 us on the fused-epilogue 32->32 launch at 48x136x240 in isolation
-// (tools/nt_ablate.sh).  In the network the consumer of y (BatchNorm statistics + apply in training, the next convolution
-// in inference) runs right behind and finds a 200 MB output partly in the 256 MB infinity cache when it was stored with
-// the default policy: training step 37.86 -> 37.38 ms per pair at batch 1, eval forward 7.63 -> 7.51 ms, batch-4 step
-// 143.7 -> 143.4 ms (tools/nt_bench_ab.sh).  So the default is plain stores.
-#ifndef X3_NT
-#define X3_NT 0
-#endif
-// X3_STAMP (debug build, tools/x3_stamps.py): res_post is reinterpreted as an unsigned long long buffer that receives
-// s_memtime stamps of the first 96 phases (8 per phase) of workgroup 0, wave 0
-#ifndef X3_STAMP
-#define X3_STAMP 0
-#endif
-#if X3_STAMP
-#define X3_MARK(i) do { if (stamp_on && stamp_k < 96) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) stamps[stamp_k * 8 + (i)] = t_; } } while (0)
-#else
-#define X3_MARK(i) do { } while (0)
-#endif
+// The output stores of this family (this kernel, conv3d_f16x2.hip, conv3d_lp.hip, deconv3d_x3.hip) are PLAIN stores.
+// Non-temporal ones were measured here: y is written once, so it need not displace the halo lines the neighbouring tiles
+// re-read from this XCD's L2 -- 591 -> 568 us on the fused-epilogue 32->32 launch at 48x136x240 in isolation.  In the
+// network the consumer of y (BatchNorm statistics + apply in training, the next convolution in inference) runs right
+// behind and finds a 200 MB output partly in the 256 MB infinity cache when it was stored with the default policy: with
+// non-temporal stores the training step went 37.38 -> 37.86 ms per pair at batch 1, the eval forward 7.51 -> 7.63 ms, the
+// batch-4 step 143.4 -> 143.7 ms.  (The switchable builds and their scripts are in history before this commit.)
 
 namespace {
 
@@ -96,10 +85,8 @@ __global__ __launch_bounds__(512) void conv3_bf16x3_kernel(X3Args a) {
   // over the 8 XCDs, each with its own L2); inside its XCD's range, workgroup j of cnt takes tiles j, j + cnt, ... so
   // at any time the CUs of an XCD work on neighbouring tiles and share their halos in that L2.  The load / MFMA
   // pipeline runs straight across tile boundaries.
-  const long T = (long)a.N * a.nTD * a.nTH * a.nTW;
-  const int nx = gridDim.x >= 8 ? 8 : 1, xcd = blockIdx.x % nx;
-  const int cnt = (gridDim.x - xcd + nx - 1) / nx;          // workgroups on this XCD
-  const int t_begin = (int)(T * xcd / nx) + blockIdx.x / nx, t_end = (int)(T * (xcd + 1) / nx), t_step = cnt;
+  const DcaTileWalk walk = dca_my_tile_walk((long)a.N * a.nTD * a.nTH * a.nTW);   // dca_tiles.h
+  const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
   float* stat_w = stat_lds + wv * FS_WAVE_FLOATS;   // this wave's slots
   bool stat_first = true;
   if constexpr (STATS) {
@@ -131,12 +118,6 @@ __global__ __launch_bounds__(512) void conv3_bf16x3_kernel(X3Args a) {
   const long wbytes = (long)P * A_SLAB;
   const __amdgpu_buffer_rsrc_t wr = dca_rsrc((const char*)a.wx + (long)cblk * wbytes, wbytes);
 
-#if X3_STAMP
-  unsigned long long* stamps = (unsigned long long*)a.res_post;
-  a.res_post = nullptr;
-  const bool stamp_on = blockIdx.x == 0 && blockIdx.y == 0 && wv == 0;
-  int stamp_k = 0;
-#endif
   const bool has_aff = a.scale != nullptr, has_pre = a.res_pre != nullptr, has_post = a.res_post != nullptr;
   float4 ra[KA];
   auto load_A = [&](int p) __attribute__((always_inline)) {
@@ -243,11 +224,7 @@ __global__ __launch_bounds__(512) void conv3_bf16x3_kernel(X3Args a) {
     }
   };
   auto decode = [&](int tile, int& n, int& d0, int& h0, int& w0) __attribute__((always_inline)) {
-    const int tw = tile % a.nTW; tile /= a.nTW;
-    const int th = tile % a.nTH; tile /= a.nTH;
-    const int td = tile % a.nTD;
-    n = tile / a.nTD;
-    d0 = td * TD; h0 = th * TH; w0 = tw * TW;
+    dca_tile_decode<TD, TH, TW>(tile, a.nTD, a.nTH, a.nTW, n, d0, h0, w0);
   };
 
   int n, d0, h0, w0;
@@ -276,7 +253,6 @@ __global__ __launch_bounds__(512) void conv3_bf16x3_kernel(X3Args a) {
       const bool last_of_chunk = kd == 2;
       const bool next_chunk = last_of_chunk && (chunk + 1 < a.NCH);
       const bool next_tile = last_of_chunk && !next_chunk && more_tiles;
-      X3_MARK(0);
       // slab p+1 (in registers since the previous phase) -> the buffer phase p-1 used; then fetch slab p+2
       if (p + 1 < P || more_tiles) store_A(buf ^ 1);
       if (p + 2 < P || more_tiles) load_A(p + 2 < P ? p + 2 : p + 2 - P);
@@ -330,22 +306,13 @@ __global__ __launch_bounds__(512) void conv3_bf16x3_kernel(X3Args a) {
           }
         }
       };
-      X3_MARK(1);
       if (stage) phase(std::true_type{}); else phase(std::false_type{});
-      X3_MARK(2);
       if (stage) {
         __syncthreads();  // every wave is done reading the halo tile of this chunk
-        X3_MARK(3);
         store_B();
-        X3_MARK(4);
       }
       __syncthreads();
-      X3_MARK(5);
-#if X3_STAMP
-      if (p + 1 < P) ++stamp_k;
-#endif
     }
-    X3_MARK(6);
 
     // Epilogue (same contract as conv3d_mfma.hip): y = act(acc * scale + shift + res_pre) + res_post.  The stores
     // drain while the next tile's first phase runs.
@@ -404,11 +371,7 @@ __global__ __launch_bounds__(512) void conv3_bf16x3_kernel(X3Args a) {
           st_s[r] += dlt;
           st_q[r] = fmaf(dlt, dlt, st_q[r]);
         }
-#if X3_NT
-        dca_bstore1_nt(yr, v, voff + cu * cstride * 4, ok & (int)(cblk * 32 + cu + 4 * half < a.Cout));
-#else
         dca_bstore1(yr, v, voff + cu * cstride * 4, ok & (int)(cblk * 32 + cu + 4 * half < a.Cout));
-#endif
       }
     }
     if constexpr (STATS) {
@@ -424,10 +387,6 @@ __global__ __launch_bounds__(512) void conv3_bf16x3_kernel(X3Args a) {
       if ((lane & 31) == 0) atomicAdd(stat_w + 96 + half, rn);
       stat_first = false;
     }
-    X3_MARK(7);
-#if X3_STAMP
-    ++stamp_k;
-#endif
     n = nn; d0 = nd0; h0 = nh0; w0 = nw0;
   }
   if constexpr (STATS) {
@@ -466,15 +425,14 @@ namespace {
 // launch geometry: persistent, one workgroup per CU (the LDS footprint allows no more; gx per block of 32 output channels),
 // each looping over its share of the tiles; gx is also the number of statistics partials per channel
 struct X3Geom {
-  int nTD, nTH, nTW, cblks, gx;
-  long tiles;
+  DcaTileGrid t;
+  int cblks, gx;
 };
 X3Geom x3_geometry(int N, int Cout, int D, int H, int W) {
   X3Geom g;
-  g.nTD = cdiv(D, TD); g.nTH = cdiv(H, TH); g.nTW = cdiv(W, TW);
-  g.tiles = (long)N * g.nTD * g.nTH * g.nTW;
+  g.t = dca_tile_grid<TD, TH, TW>(N, D, H, W);
   g.cblks = (Cout + 31) / 32;
-  g.gx = dca_persistent_grid(g.tiles, g.cblks);
+  g.gx = dca_persistent_grid(g.t.tiles, g.cblks);
   return g;
 }
 
@@ -491,9 +449,9 @@ int x3_launch(const float* x, const void* wx, float* y, const float* scale, cons
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.NCH = (Cin + 15) / 16;
   a.D = D; a.H = H; a.W = W;
   const X3Geom g = x3_geometry(N, Cout, D, H, W);
-  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW;
+  a.nTD = g.t.nTD; a.nTH = g.t.nTH; a.nTW = g.t.nTW;
   a.stat_part = stat_part;
-  DCA_REQUIRE(g.tiles < 0x7fffffffL && g.cblks <= 65535);
+  DCA_REQUIRE(g.t.fits() && g.cblks <= 65535);
   const bool vec = (W % 4 == 0) && ((((uintptr_t)x) & 15) == 0);
   const bool stats = stat_part != nullptr;
   auto kern = stats ? (vec ? conv3_bf16x3_kernel<true, true> : conv3_bf16x3_kernel<false, true>)

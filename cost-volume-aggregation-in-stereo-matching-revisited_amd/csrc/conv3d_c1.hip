@@ -6,6 +6,7 @@
 // taps become the GEMM's output axis (see "tap expansion" below) for forward and weight gradient, and the
 // backward-data pass is a VALU kernel (dy halo tile in LDS, 4 consecutive W positions per thread).
 #include "dca_common.h"
+#include "dca_tiles.h"
 #include "../../include/dca_hip.h"
 
 namespace {
@@ -59,11 +60,7 @@ __device__ __forceinline__ void stage_tile(const float* __restrict__ src, float*
 }
 
 __device__ __forceinline__ void tile_coords(const C1Args& a, int tile, int& n, int& d0, int& h0, int& w0) {
-  const int tw = tile % a.nTW; tile /= a.nTW;
-  const int th = tile % a.nTH; tile /= a.nTH;
-  const int td = tile % a.nTD;
-  n = tile / a.nTD;
-  d0 = td * TD; h0 = th * TH; w0 = tw * TW;
+  dca_tile_decode<TD, TH, TW>(tile, a.nTD, a.nTH, a.nTW, n, d0, h0, w0);
 }
 
 // ------------------------------------------------------------------------------------------ backward-data

@@ -36,30 +36,14 @@
 // fragments (28 KB, pre-scaled, pre-split and pre-swizzled by x2_prep_weight_kernel); both are double buffered (126 KB), so the
 // loads, the [split and] LDS stores of the next chunk and the MFMAs of this one need no ordering among themselves.  The
 // staging steps sit at compile-time positions between the tap pairs (one global load or one LDS store per pair): issued as a
-// burst they held the matrix pipe for 1-2.4 k cycles per chunk (s_memtime stamps, tools/x2_stamps.py).
+// burst they held the matrix pipe for 1-2.4 k cycles per chunk (s_memtime stamps; the instrumented build is in history
+// before this commit).
 #include "dca_frag.h"
+#include "dca_tiles.h"
 #include "bn_fused_stats.h"
 #include <type_traits>
 
-// Non-temporal output stores (X2_NT=1; measured on the bf16x3 kernel, whose epilogue this is): y is written once, so it need not displace the halo lines the neighbouring tiles
-// re-read from this XCD's L2 -- 591 -> 568 us on the fused-epilogue 32->32 launch at 48x136x240 in isolation
-// (tools/nt_ablate.sh).  In the network the consumer of y (BatchNorm statistics + apply in training, the next convolution
-// in inference) runs right behind and finds a 200 MB output partly in the 256 MB infinity cache when it was stored with
-// the default policy: training step 37.86 -> 37.38 ms per pair at batch 1, eval forward 7.63 -> 7.51 ms, batch-4 step
-// 143.7 -> 143.4 ms (tools/nt_bench_ab.sh).  So the default is plain stores.
-#ifndef X2_NT
-#define X2_NT 0
-#endif
-// X2_STAMP (debug build, tools/x2_stamps.py): dca_x2_debug_set_stamps(ptr) names a buffer of 2 x 96 x 8 unsigned long long that
-// receives s_memtime stamps of the first 96 chunks (8 marks per chunk) of workgroup 0, waves 0 and 7
-#ifndef X2_STAMP
-#define X2_STAMP 0
-#endif
-#if X2_STAMP
-#define X2_MARK(i) do { if (stamp_on && stamp_k < 96) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) stamps[stamp_k * 8 + (i)] = t_; } } while (0)
-#else
-#define X2_MARK(i) do { } while (0)
-#endif
+// Output stores are plain, not non-temporal: measured on the bf16x3 kernel, whose epilogue this is (conv3d_bf16x3.hip).
 
 namespace {
 
@@ -99,9 +83,6 @@ struct X2Args {
   const int* xexps;          // fp32 x: the scale exponent of every input channel (Cin ints); unused for packed x
   const int* ofo;            // behind the packed weight image: f_o of every output channel (dca_conv3d_x2_prep_weight)
   unsigned* y_cmax;          // optional (EPI 1): per-channel slots [c][blockIdx.x] that receive max |y| (dca_common.h)
-#if X2_STAMP
-  unsigned long long* stamps;   // debug build: s_memtime stamps of workgroup 0, waves 0 and 7 (2 x 96 x 8 words)
-#endif
 };
 
 constexpr int STAT_LDS = 8 * FS_WAVE_FLOATS * 4;
@@ -131,10 +112,8 @@ __global__ __launch_bounds__(512) void conv3_f16x2_kernel(X2Args a) {
   // over the 8 XCDs, each with its own L2); inside its XCD's range, workgroup j of cnt takes tiles j, j + cnt, ... so
   // at any time the CUs of an XCD work on neighbouring tiles and share their halos in that L2.  The load / MFMA
   // pipeline runs straight across tile boundaries.
-  const long T = (long)a.N * a.nTD * a.nTH * a.nTW;
-  const int nx = gridDim.x >= 8 ? 8 : 1, xcd = blockIdx.x % nx;
-  const int cnt = (gridDim.x - xcd + nx - 1) / nx;          // workgroups on this XCD
-  const int t_begin = (int)(T * xcd / nx) + blockIdx.x / nx, t_end = (int)(T * (xcd + 1) / nx), t_step = cnt;
+  const DcaTileWalk walk = dca_my_tile_walk((long)a.N * a.nTD * a.nTH * a.nTW);   // dca_tiles.h
+  const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
   float* stat_w = stat_lds + wv * FS_WAVE_FLOATS;   // this wave's slots
   bool stat_first = true;
   // STATS: per-lane running sums of (y - K) and (y - K)^2 over all tiles of the workgroup (the epilogue-free variants have
@@ -188,12 +167,6 @@ __global__ __launch_bounds__(512) void conv3_f16x2_kernel(X2Args a) {
   const long wbytes = (long)NC * A_CHUNK;
   const __amdgpu_buffer_rsrc_t wr = dca_rsrc((const char*)a.wx + (long)cblk * wbytes, wbytes);
 
-#if X2_STAMP
-  unsigned long long* stamps = a.stamps;
-  const bool stamp_on = stamps != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && (wv == 0 || wv == 7);
-  if (stamp_on && wv == 7) stamps += 96 * 8;
-  int stamp_k = 0;
-#endif
   const bool has_aff = EPI == 1 && a.scale != nullptr, has_pre = EPI == 1 && a.res_pre != nullptr;
   const bool has_post = EPI == 2 || (EPI == 1 && a.res_post != nullptr);
   // weight fragments of a chunk: global -> registers (load_A) -> the A image that is not being read (store_A)
@@ -345,11 +318,7 @@ __global__ __launch_bounds__(512) void conv3_f16x2_kernel(X2Args a) {
     }
   };
   auto decode = [&](int tile, int& n, int& d0, int& h0, int& w0) __attribute__((always_inline)) {
-    const int tw = tile % a.nTW; tile /= a.nTW;
-    const int th = tile % a.nTH; tile /= a.nTH;
-    const int td = tile % a.nTD;
-    n = tile / a.nTD;
-    d0 = td * TD; h0 = th * TH; w0 = tw * TW;
+    dca_tile_decode<TD, TH, TW>(tile, a.nTD, a.nTH, a.nTW, n, d0, h0, w0);
   };
 
   int n, d0, h0, w0;
@@ -382,11 +351,10 @@ __global__ __launch_bounds__(512) void conv3_f16x2_kernel(X2Args a) {
       // phase and the halo image written between two extra barriers after every third).
       const bool stage = !last_chunk || more_tiles;
       const bool next_tile = last_chunk && more_tiles;
-      X2_MARK(0);
       // staging steps ride between the MFMAs (one global load / one LDS store per tap pair, see the pair loop): issued as a
       // burst in front of the chunk, 9 loads and their address arithmetic kept BOTH waves of a SIMD -- and the matrix pipe --
-      // busy for 1.0-2.4 k of a chunk's 8.7 k cycles, and the stores behind the MFMAs cost another 0.6 k (s_memtime stamps,
-      // tools/x2_stamps.py); only the unaligned fp32 path (W % 4 != 0) still stages that way
+      // busy for 1.0-2.4 k of a chunk's 8.7 k cycles, and the stores behind the MFMAs cost another 0.6 k (s_memtime
+      // stamps); only the unaligned fp32 path (W % 4 != 0) still stages that way
       const int s_n = next_tile ? nn : n, s_d0 = next_tile ? nd0 : d0, s_h0 = next_tile ? nh0 : h0, s_w0 = next_tile ? nw0 : w0;
       const int s_chunk = next_tile ? 0 : chunk + 1, s_on = stage ? 1 : 0;
       const __amdgpu_buffer_rsrc_t s_xr = dca_rsrc(a.x + (long)s_n * sample, sample * 4);
@@ -416,7 +384,6 @@ __global__ __launch_bounds__(512) void conv3_f16x2_kernel(X2Args a) {
           for (int term = 0; term < NT; ++term)
             fb[slot][t][term] = *(const f16x8*)(bb + boff[t] + toff + term * B_TERM);
       };
-      X2_MARK(1);
       load_frag(0, 0);
 #pragma unroll
       for (int p = 0; p < NPAIR; ++p) {
@@ -448,24 +415,17 @@ __global__ __launch_bounds__(512) void conv3_f16x2_kernel(X2Args a) {
         }
         __builtin_amdgcn_sched_barrier(0);     // nothing moves across pairs: the staging steps stay where they are written
       }
-      X2_MARK(2);
       if constexpr (!PIN && !VEC) {
         if (stage) {
           store_B(s_chunk, buf ^ 1);
           store_A(buf ^ 1);
         }
       }
-      X2_MARK(3);
       // the barrier of a tile's last chunk comes AFTER the epilogue: the epilogue touches neither image pair, so the older
       // wave of a SIMD (which wins the matrix pipe and finishes its 84 MFMAs ~2 k cycles early) stores its results while the
       // younger one still computes
       if (!last_chunk) __syncthreads();
-      X2_MARK(5);
-#if X2_STAMP
-      if (chunk + 1 < NC) ++stamp_k;
-#endif
     }
-    X2_MARK(6);
 
     // Epilogue (same contract as conv3d_mfma.hip): y = act(acc * scale + shift + res_pre) + res_post.  The stores
     // drain while the next tile's first phase runs.
@@ -534,19 +494,11 @@ __global__ __launch_bounds__(512) void conv3_f16x2_kernel(X2Args a) {
         }
         const int okc = ok & (int)(cblk * 32 + cu + 4 * half < a.Cout);
         if constexpr (EPI == 1) ycm[r] = fmaxf(ycm[r], okc ? fabsf(v) : 0.f);
-#if X2_NT
-        dca_bstore1_nt(yr, v, voff + cu * cstride * 4, okc);
-#else
         dca_bstore1(yr, v, voff + cu * cstride * 4, okc);
-#endif
       }
     }
     if constexpr (STATS) stat_first = false;
-    X2_MARK(7);
     __syncthreads();     // (the last chunk's barrier: the next tile's first images are complete, this tile's are free)
-#if X2_STAMP
-    ++stamp_k;
-#endif
     n = nn; d0 = nd0; h0 = nh0; w0 = nw0;
   }
   if constexpr (STATS) {
@@ -654,25 +606,19 @@ extern "C" int dca_conv3d_x2_prep_weight(const float* w, void* wx, int A, int B,
   return dca_launch_status();
 }
 
-#if X2_STAMP
-static unsigned long long* g_stamps = nullptr;
-extern "C" void dca_x2_debug_set_stamps(unsigned long long* p) { g_stamps = p; }
-#endif
-
 namespace {
 
 // launch geometry: persistent, one workgroup per CU (gx per block of 32 output channels), each looping over its share of the
 // tiles; gx is also the number of statistics partials and of y_cmax slots per channel
 struct X2Geom {
-  int nTD, nTH, nTW, cblks, gx;
-  long tiles;
+  DcaTileGrid t;
+  int cblks, gx;
 };
 X2Geom x2_geometry(int N, int Cout, int D, int H, int W) {
   X2Geom g;
-  g.nTD = cdiv(D, TD); g.nTH = cdiv(H, TH); g.nTW = cdiv(W, TW);
-  g.tiles = (long)N * g.nTD * g.nTH * g.nTW;
+  g.t = dca_tile_grid<TD, TH, TW>(N, D, H, W);
   g.cblks = (Cout + 31) / 32;
-  g.gx = dca_persistent_grid(g.tiles, g.cblks);
+  g.gx = dca_persistent_grid(g.t.tiles, g.cblks);
   if (g.gx > DCA_AMAX_CSLOTS) g.gx = DCA_AMAX_CSLOTS;  // a workgroup index is also a slot of the per-channel output maxima
   return g;
 }
@@ -700,16 +646,13 @@ int x2_launch(const void* x, int packed, const int* xexps, const void* wx, float
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.NCH = (Cin + 7) / 8;
   a.D = D; a.H = H; a.W = W;
   const X2Geom g = x2_geometry(N, Cout, D, H, W);
-  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW;
+  a.nTD = g.t.nTD; a.nTH = g.t.nTH; a.nTW = g.t.nTW;
   a.stat_part = stat_part;
   a.xexps = xexps;
   a.y_cmax = y_cmax;
-#if X2_STAMP
-  a.stamps = g_stamps;
-#endif
   const int cblks = g.cblks, gx = g.gx;
   a.ofo = (const int*)((const char*)wx + (long)cblks * a.NCH * A_CHUNK);
-  DCA_REQUIRE(g.tiles < 0x7fffffffL && cblks <= 65535);
+  DCA_REQUIRE(g.t.fits() && cblks <= 65535);
   const bool vec = (W % 4 == 0) && ((((uintptr_t)x) & 15) == 0);
   const bool stats = stat_part != nullptr;
   const bool full = scale != nullptr || res_pre != nullptr || slope != 1.f || y_cmax != nullptr;

@@ -19,23 +19,15 @@
 //   MODE 2  Cin <= 64: resident weights (108 KB), single halo image (two barriers per chunk);
 //   MODE 0  wider inputs: weights stream through a double-buffered 27-tap slab next to the double-buffered halo image.
 #include "dca_frag.h"
+#include "dca_tiles.h"
 #include "../../include/dca_hip.h"
 #include <type_traits>
 
-// compile-time ablation switches for tools/lp_ablate.sh (never set in the shipped library):
-// 1 no halo loads, 2 no MFMAs, 4 no epilogue stores, 8 no LDS fragment reads, 16 no LDS halo writes
-#ifndef LP_ABL
-#define LP_ABL 0
-#endif
-#ifndef LP_LOOK    // LDS fragment reads run this many taps ahead of their MFMAs (measured 1..4: 3 is best by ~2 %)
-#define LP_LOOK 3
-#endif
-#ifndef LP_SGB
-#define LP_SGB 1
-#endif
-#ifndef LP_NT      // non-temporal output stores
-#define LP_NT 0
-#endif
+constexpr int LP_LOOK = 3;    // LDS fragment reads run this many taps ahead of their MFMAs (measured 1..4: 3 is best by ~2 %)
+constexpr int LP_SGB = 1;     // pin "one MFMA, then the reads" with sched_group_barrier (see the tap loop)
+// (The compile-time ablation build behind DESIGN.md's conv3_lp_kernel history -- no halo loads / MFMAs / epilogue stores /
+// LDS fragment reads / LDS halo writes -- is in history before this commit.  Output stores are plain: non-temporal 4-byte
+// pair stores measured 118 -> 150 us, profiles/README.md.)
 
 namespace {
 
@@ -94,10 +86,8 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, half = lane >> 5;
   const int cblk = blockIdx.y;
-  const long T = (long)a.N * a.nTD * a.nTH * a.nTW;
-  const int nx = gridDim.x >= 8 ? 8 : 1, xcd = blockIdx.x % nx;
-  const int cnt = (gridDim.x - xcd + nx - 1) / nx;
-  const int t_begin = (int)(T * xcd / nx) + blockIdx.x / nx, t_end = (int)(T * (xcd + 1) / nx), t_step = cnt;
+  const DcaTileWalk walk = dca_my_tile_walk((long)a.N * a.nTD * a.nTH * a.nTW);   // dca_tiles.h
+  const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
   if (t_begin >= t_end) return;
 
   // ds_read_b128 is served in four NON-contiguous 16-lane groups ({0-3,12-15,20-27}, {4-11,16-19,28-31}, ...:
@@ -252,11 +242,7 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
     }
   };
   auto decode = [&](int tile, int& n, int& d0, int& h0, int& w0) __attribute__((always_inline)) {
-    const int tw = tile % a.nTW; tile /= a.nTW;
-    const int th = tile % a.nTH; tile /= a.nTH;
-    const int td = tile % a.nTD;
-    n = tile / a.nTD;
-    d0 = td * TD; h0 = th * TH; w0 = tw * TW;
+    dca_tile_decode<TD, TH, TW>(tile, a.nTD, a.nTH, a.nTW, n, d0, h0, w0);
   };
 
   // MODE 1 runs a deeper software pipeline: the halo tile of step s+2 (a step = one chunk of one tile) is requested in
@@ -264,12 +250,9 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
   // a full step of latency tolerance, and the pack + ds_write work overlaps the second half of the step's MFMAs.
   constexpr bool PIPE = MODE == 1;
   constexpr int SPLIT = 13;
-  struct Cursor { int tile, chunk, n, d0, h0, w0; };
+  typedef DcaTileStep Cursor;
   auto advance = [&](Cursor& c) __attribute__((always_inline)) {   // next step; c.tile >= t_end marks "none"
-    if (c.chunk + 1 < a.NCH) { ++c.chunk; return; }
-    c.chunk = 0;
-    c.tile += t_step;
-    if (c.tile < t_end) decode(c.tile, c.n, c.d0, c.h0, c.w0);
+    dca_tile_advance<TD, TH, TW>(c, a.NCH, walk, a.nTD, a.nTH, a.nTW);
   };
 
   int n, d0, h0, w0;
@@ -312,7 +295,7 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int r0 = (wv * 2 + t) * 2 + (l31 >> 4), d = d0 + (r0 >> 3), h = h0 + (r0 & 7), w = w0 + wlane;
-      const int ok = (int)(d < a.D) & (int)(h < a.H) & (int)(w < a.W) & (int)!((LP_ABL & 4) && eacc[t][1] != 12345.f);
+      const int ok = (int)(d < a.D) & (int)(h < a.H) & (int)(w < a.W);
       // Byte offsets: ONE hardware-predicated base per lane; register r adds the uniform cu(r) * cstride.  An output
       // channel >= Cout lands beyond the descriptor's range (Cout * cstride elements) and is dropped / read as zero by
       // the range check, so partial channel blocks need no per-register predicate.
@@ -369,7 +352,7 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
           const unsigned P = lp_pack2<MT>(v0, v1), Q = lp_swap1(P);
           // even lane: [my v0 | partner's v0]; odd lane: [partner's v1 | my v1]
           const unsigned word = __builtin_amdgcn_perm(P, Q, sel);
-          __builtin_amdgcn_raw_buffer_store_b32(word, yr, base + ((r & 3) + 8 * (r >> 2)) * cstride * 2, 0, LP_NT ? 2 : 0);
+          __builtin_amdgcn_raw_buffer_store_b32(word, yr, base + ((r & 3) + 8 * (r >> 2)) * cstride * 2, 0, 0);
         }
       }
     }
@@ -392,7 +375,7 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
       const bool stage = next_chunk || more_tiles;
       const char* ab = a_lds + (RES ? chunk : buf) * A_SLAB + lane * 16;
       const char* bb = b_lds + buf * B_IMG;
-      if (!PIPE && stage && !(LP_ABL & 1)) {
+      if (!PIPE && stage) {
         if (next_chunk) load_B(n, d0, h0, w0, chunk + 1); else load_B(nn, nd0, nh0, nw0, 0);
         if constexpr (!RES) load_A(next_chunk ? chunk + 1 : 0);
       }
@@ -409,23 +392,18 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
       };
 #pragma unroll
       for (int t0 = 0; t0 < LOOK; ++t0) load_frag(t0, t0);
-      if (LP_ABL & 8) load_frag(LOOK, LOOK);
 #pragma unroll
       for (int tap = 0; tap < 27; ++tap) {
         const int cur = tap % NS;
         if (PIPE && tap == SPLIT) {
-          if (c1.tile < t_end && !(LP_ABL & 16)) store_B(buf ^ 1);                                  // step s+1 -> other image
-          if (c2.tile < t_end && !(LP_ABL & 1)) load_B(c2.n, c2.d0, c2.h0, c2.w0, c2.chunk);        // request step s+2
+          if (c1.tile < t_end) store_B(buf ^ 1);                                  // step s+1 -> other image
+          if (c2.tile < t_end) load_B(c2.n, c2.d0, c2.h0, c2.w0, c2.chunk);        // request step s+2
           c1 = c2;
           advance(c2);
         }
-        if (tap + LOOK < 27 && !(LP_ABL & 8)) load_frag(tap + LOOK, (tap + LOOK) % NS);
-        if (!(LP_ABL & 2)) {
+        if (tap + LOOK < 27) load_frag(tap + LOOK, (tap + LOOK) % NS);
 #pragma unroll
-          for (int t = 0; t < 2; ++t) acc[t] = Lp<MT>::mfma(fa[cur], fb[cur][t], acc[t]);
-        } else {
-          acc[0][0] += (float)fa[cur][0] + (float)fb[cur][0][0] + (float)fb[cur][1][0];
-        }
+        for (int t = 0; t < 2; ++t) acc[t] = Lp<MT>::mfma(fa[cur], fb[cur][t], acc[t]);
         if (LP_SGB && tap + LOOK < 27 && tap != SPLIT) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
           __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
@@ -436,7 +414,7 @@ __global__ __launch_bounds__(512) void conv3_lp_kernel(LpArgs a) {
       if constexpr (PIPE) {
         __syncthreads();
       } else if constexpr (DBUF) {
-        if (stage && !(LP_ABL & 16)) {
+        if (stage) {
           store_B(buf ^ 1);
           if constexpr (!RES) store_A(buf ^ 1);
         }
@@ -534,12 +512,12 @@ extern "C" int dca_conv3d_lp_forward(const void* x, const void* wx, void* y, con
   a.scale = scale; a.shift = shift; a.res_pre = res_pre; a.res_post = res_post; a.slope = slope;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.NCH = (Cin + 15) / 16;
   a.D = D; a.H = H; a.W = W;
-  a.nTD = cdiv(D, TD); a.nTH = cdiv(H, TH); a.nTW = cdiv(W, TW);
-  const long tiles = (long)N * a.nTD * a.nTH * a.nTW;
-  DCA_REQUIRE(tiles < 0x7fffffffL && (Cout + 31) / 32 <= 65535);
+  const DcaTileGrid t = dca_tile_grid<TD, TH, TW>(N, D, H, W);
+  a.nTD = t.nTD; a.nTH = t.nTH; a.nTW = t.nTW;
+  DCA_REQUIRE(t.fits() && (Cout + 31) / 32 <= 65535);
   const bool vec = (W % 4 == 0) && ((((uintptr_t)x) & (in_f32 ? 15 : 7)) == 0);
   const int cblks = (Cout + 31) / 32;
-  const int gx = dca_persistent_grid(tiles, cblks);
+  const int gx = dca_persistent_grid(t.tiles, cblks);
   if (dtype == DCA_BF16) {
     if (in_f32) return out_f32 ? launch_lp<__bf16, true, true>(a, vec, gx, cblks, stream)
                                : launch_lp<__bf16, true, false>(a, vec, gx, cblks, stream);

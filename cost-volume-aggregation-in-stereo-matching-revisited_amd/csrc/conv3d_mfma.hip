@@ -467,9 +467,7 @@ __global__ __launch_bounds__(256, 2) void deconv3_mfma_kernel(ConvArgs a) {
 // output rows at a time (124 -> 120 us for 32->32 at 48x136x240).  Forcing two workgroups per CU (CONV1_OCC=2) still
 // spills (131 us): a wave's 64 fp32 MFMAs (4096 matrix-pipe cycles per 128 voxels) are the latency this kernel cannot
 // hide, which is what the reduced-precision conv1_lp.hip (1536 cycles, 4.8-5.6 TB/s) does not have.
-#ifndef CONV1_OCC
-#define CONV1_OCC 1
-#endif
+constexpr int CONV1_OCC = 1;
 template <int NG, bool VEC>
 __global__ __launch_bounds__(256, CONV1_OCC) void conv1_mfma_kernel(ConvArgs a) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l31 = lane & 31, half = lane >> 5;

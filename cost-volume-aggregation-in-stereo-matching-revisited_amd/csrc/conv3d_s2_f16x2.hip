@@ -30,17 +30,12 @@
 // K-steps 3-5 (compile-time schedule, as in conv3d_f16x2.hip).
 //
 // Measured (tools/s2_time.py, 32 -> 64 at 48x136x240, batch 4): 0.45 ms against 0.87 ms for the fp32 MFMA kernel.  Ablations
-// (S2_ABL): without staging loads 0.34, without split + LDS stores 0.38, with neither 0.24 ms -- the MFMAs alone need 0.14 ms
-// at the clock held.  The kernel moves 1 KB of LDS reads per MFMA (a 32 x 32 accumulator tile reuses nothing) and 78 KB of LDS
-// stores per chunk of 42 MFMAs per wave (the weights' 28 KB are re-staged for every tile): LDS traffic, not the matrix pipe,
-// sets its speed.
+// (compile-time switches, in history before this commit): without staging loads 0.34, without split + LDS stores 0.38, with
+// neither 0.24 ms -- the MFMAs alone need 0.14 ms at the clock held.  The kernel moves 1 KB of LDS reads per MFMA (a 32 x 32
+// accumulator tile reuses nothing) and 78 KB of LDS stores per chunk of 42 MFMAs per wave (the weights' 28 KB are re-staged
+// for every tile): LDS traffic, not the matrix pipe, sets its speed.
 #include "dca_frag.h"
-
-// compile-time ablation switches for the measurements above (DCA_EXTRA_CFLAGS=-DS2_ABL=..., never set in the shipped
-// library): 1 no staging loads, 2 no LDS stores, 4 no split
-#ifndef S2_ABL
-#define S2_ABL 0
-#endif
+#include "dca_tiles.h"
 
 namespace {
 
@@ -79,11 +74,6 @@ struct S2Args {
   unsigned* y_cmax;          // EPI: optional per-channel slots [c][blockIdx.x] <- max |y| (dca_common.h)
 };
 
-__device__ __forceinline__ void s2_split_abl(float v, int e, _Float16& h, _Float16& l) {
-  if (S2_ABL & 4) { h = (_Float16)v; l = h; return; }
-  x2_split(v, e, h, l);
-}
-
 // byte offset inside a term image of tap t's fragment relative to the lane's base (2 dl, 2 hl, slot w)
 __device__ __forceinline__ constexpr int s2_toff(int t) {
   const int tt = t < 27 ? t : 26;          // the 28th tap has zero weights: any finite data
@@ -106,10 +96,8 @@ __global__ __launch_bounds__(512) void conv3s2_f16x2_kernel(S2Args a) {
   // tid >> 6 stays a per-lane value on purpose (no readfirstlane): see conv3d_wgrad_f16x2.hip
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, half = lane >> 5;
   const int cblk = blockIdx.y;
-  const long T = (long)a.N * a.nTD * a.nTH * a.nTW;
-  const int nx = gridDim.x >= 8 ? 8 : 1, xcd = blockIdx.x % nx;
-  const int cnt = (gridDim.x - xcd + nx - 1) / nx;
-  const int t_begin = (int)(T * xcd / nx) + blockIdx.x / nx, t_end = (int)(T * (xcd + 1) / nx), t_step = cnt;
+  const DcaTileWalk walk = dca_my_tile_walk((long)a.N * a.nTD * a.nTH * a.nTW);   // dca_tiles.h
+  const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
   if (t_begin >= t_end) {
     if constexpr (EPI) {   // a workgroup without tiles still owns its slot of the per-channel maxima
       if (a.y_cmax && tid < 64 && cblk * 64 + tid < a.Cout) a.y_cmax[(long)(cblk * 64 + tid) * DCA_AMAX_CSLOTS + blockIdx.x] = 0u;
@@ -194,8 +182,8 @@ __global__ __launch_bounds__(512) void conv3s2_f16x2_kernel(S2Args a) {
       for (int j = 0; j < 4; ++j) {
         const float* c = (const float*)&rq[k][j];
         _Float16 h, l;
-        s2_split_abl(c[va], e[j], h, l); hv[j] = h; lv[j] = l;
-        s2_split_abl(c[vb], e[j], h, l); hv[4 + j] = h; lv[4 + j] = l;
+        x2_split(c[va], e[j], h, l); hv[j] = h; lv[j] = l;
+        x2_split(c[vb], e[j], h, l); hv[4 + j] = h; lv[4 + j] = l;
       }
       char* dst = img + (par ? B_PLANE + (2 * qq[k]) * 8 : (2 * qq[k] + 2) * 8);
       *(f16x8*)dst = hv;
@@ -217,11 +205,7 @@ __global__ __launch_bounds__(512) void conv3s2_f16x2_kernel(S2Args a) {
     *(f16x4*)(dst + B_TERM) = lv;
   };
   auto decode = [&](int tile, int& n, int& d0, int& h0, int& w0) __attribute__((always_inline)) {
-    const int tw = tile % a.nTW; tile /= a.nTW;
-    const int th = tile % a.nTH; tile /= a.nTH;
-    const int td = tile % a.nTD;
-    n = tile / a.nTD;
-    d0 = td * TD; h0 = th * TH; w0 = tw * TW;
+    dca_tile_decode<TD, TH, TW>(tile, a.nTD, a.nTH, a.nTW, n, d0, h0, w0);
   };
 
   // Three cursors walk the workgroup's chunk sequence (tile by tile, NC chunks each): cur = the chunk being computed, cur + 1 =
@@ -229,18 +213,12 @@ __global__ __launch_bounds__(512) void conv3s2_f16x2_kernel(S2Args a) {
   // the chunk whose loads are issued during cur, once the registers are free.  A global load thus has a whole chunk (~3 k
   // cycles) to arrive; requested and consumed inside ONE chunk of 42 MFMAs per wave (the schedule of conv3d_f16x2.hip, whose
   // chunks are 84 MFMAs long) the kernel waited for memory in every chunk: 67 k cycles per tile against 21.5 k of MFMAs.
-  struct Cursor { int tile, chunk, n, d0, h0, w0; };
+  typedef DcaTileStep Cursor;
   auto advance = [&](Cursor& c) __attribute__((always_inline)) {
-    if (c.chunk + 1 < NC) {
-      ++c.chunk;
-    } else {
-      c.chunk = 0;
-      c.tile += t_step;
-      if (c.tile < t_end) decode(c.tile, c.n, c.d0, c.h0, c.w0);
-    }
+    dca_tile_advance<TD, TH, TW>(c, NC, walk, a.nTD, a.nTH, a.nTW);
   };
   auto load_all = [&](const Cursor& c, int part) __attribute__((always_inline)) {     // part 0: quad 0; 1: quad 1 + edge; 2: weights
-    const int on = (c.tile < t_end && !(S2_ABL & 1)) ? 1 : 0;
+    const int on = c.tile < t_end ? 1 : 0;
     const __amdgpu_buffer_rsrc_t xr = dca_rsrc(a.x + (long)c.n * sample, sample * 4);
     if (part == 0) load_quad(0, xr, c.d0, c.h0, c.w0, c.chunk, on);
     if (part == 1) { load_quad(1, xr, c.d0, c.h0, c.w0, c.chunk, on); load_edge(xr, c.d0, c.h0, c.w0, c.chunk, on); }
@@ -272,7 +250,7 @@ __global__ __launch_bounds__(512) void conv3s2_f16x2_kernel(S2Args a) {
   for (; cur.tile < t_end; buf ^= 1) {
     const char* ab = a_lds + buf * A_CHUNK + lane * 16;
     const char* bb = b_lds + buf * B_BYTES + lanebase;
-    const bool st_on = st.tile < t_end && !(S2_ABL & 2);
+    const bool st_on = st.tile < t_end;
     f16x8 fa[2][2][2], fb[2][2];      // [slot][channel block][term], [slot][term]
     auto load_frag = [&](int s, int slot) __attribute__((always_inline)) {
       const int oa = half ? s2_toff(4 * s + 2) : s2_toff(4 * s), ob = half ? s2_toff(4 * s + 3) : s2_toff(4 * s + 1);
@@ -429,16 +407,15 @@ extern "C" int dca_conv3d_s2x2_prep_weight(const float* w, void* wx, int A, int 
 // over its share of the tiles; gx is also the number of y_cmax slots per channel
 namespace {
 struct S2Geom {
-  int Do, Ho, Wo, nTD, nTH, nTW, cblks, gx;
-  long tiles;
+  int Do, Ho, Wo, cblks, gx;
+  DcaTileGrid t;
 };
 S2Geom s2x2_geometry(int N, int Cout, int Di, int Hi, int Wi) {
   S2Geom g;
   g.Do = (Di + 1) / 2; g.Ho = (Hi + 1) / 2; g.Wo = (Wi + 1) / 2;
-  g.nTD = cdiv(g.Do, TD); g.nTH = cdiv(g.Ho, TH); g.nTW = cdiv(g.Wo, TW);
-  g.tiles = (long)N * g.nTD * g.nTH * g.nTW;
+  g.t = dca_tile_grid<TD, TH, TW>(N, g.Do, g.Ho, g.Wo);
   g.cblks = (Cout + 63) / 64;
-  g.gx = dca_persistent_grid(g.tiles, g.cblks);
+  g.gx = dca_persistent_grid(g.t.tiles, g.cblks);
   return g;
 }
 }  // namespace
@@ -467,10 +444,10 @@ extern "C" int dca_conv3d_s2x2_forward(const float* x, const int* xexps, const v
   const S2Geom g = s2x2_geometry(N, Cout, Di, Hi, Wi);
   a.Do = g.Do; a.Ho = g.Ho; a.Wo = g.Wo;
   DCA_REQUIRE((long)(Cin + 3) * Di * Hi * Wi * 4 < 0x7ffffff0L && (long)(Cout + 63) * a.Do * a.Ho * a.Wo * 4 < 0x7ffffff0L);
-  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW;
+  a.nTD = g.t.nTD; a.nTH = g.t.nTH; a.nTW = g.t.nTW;
   a.xexps = xexps;
   a.ofo = (const int*)((const char*)wx + (long)g.cblks * a.NC4 * A_CHUNK);
-  DCA_REQUIRE(g.tiles < 0x7fffffffL && g.cblks <= 65535);
+  DCA_REQUIRE(g.t.fits() && g.cblks <= 65535);
   const int lds = LDS_BYTES + TAB_BYTES;
   const bool epi = scale != nullptr || slope != 1.f || y_cmax != nullptr;
   DCA_REQUIRE(y_cmax == nullptr || g.gx <= DCA_AMAX_CSLOTS);

@@ -14,6 +14,7 @@
 // LDS: the chunk's fine 5 x 17 x 34 halo image as [voxel][8 x 2 B] (45 KB) + the chunk's 36 KB of pre-swizzled weight
 // fragments; the next chunk's image and weights are fetched into registers while the current chunk's MFMAs run.
 #include "dca_frag.h"
+#include "dca_tiles.h"
 #include "../../include/dca_hip.h"
 
 namespace {
@@ -52,10 +53,8 @@ __global__ __launch_bounds__(512) void conv3_s2_lp_kernel(S2Args a) {
   __shared__ float aff_lds[128];    // scale[64] | shift[64]
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, half = lane >> 5;
-  const long T = (long)a.N * a.nTD * a.nTH * a.nTW;
-  const int nx = gridDim.x >= 8 ? 8 : 1, xcd = blockIdx.x % nx;
-  const int cnt = (gridDim.x - xcd + nx - 1) / nx;
-  const int t_begin = (int)(T * xcd / nx) + blockIdx.x / nx, t_end = (int)(T * (xcd + 1) / nx), t_step = cnt;
+  const DcaTileWalk walk = dca_my_tile_walk((long)a.N * a.nTD * a.nTH * a.nTW);   // dca_tiles.h
+  const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
   if (t_begin >= t_end) return;
 
   const bool has_aff = a.scale != nullptr;
@@ -135,11 +134,7 @@ __global__ __launch_bounds__(512) void conv3_s2_lp_kernel(S2Args a) {
     }
   };
   auto decode = [&](int tile, int& n, int& d0, int& h0, int& w0) __attribute__((always_inline)) {
-    const int tw = tile % a.nTW; tile /= a.nTW;
-    const int th = tile % a.nTH; tile /= a.nTH;
-    const int td = tile % a.nTD;
-    n = tile / a.nTD;
-    d0 = td * TD; h0 = th * TH; w0 = tw * TW;
+    dca_tile_decode<TD, TH, TW>(tile, a.nTD, a.nTH, a.nTW, n, d0, h0, w0);
   };
 
   int n, d0, h0, w0;
@@ -265,9 +260,9 @@ extern "C" int dca_conv3d_s2_lp_forward(const void* x, const void* wx, float* y,
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.NCH = (Cin + 7) / 8;
   a.D = D; a.H = H; a.W = W; a.Do = (D + 1) / 2; a.Ho = (H + 1) / 2; a.Wo = (W + 1) / 2;
   DCA_REQUIRE(64L * a.Do * a.Ho * a.Wo * 4 < 0x7ffffff0L);
-  a.nTD = cdiv(a.Do, TD); a.nTH = cdiv(a.Ho, TH); a.nTW = cdiv(a.Wo, TW);
-  const long tiles = (long)N * a.nTD * a.nTH * a.nTW;
-  DCA_REQUIRE(tiles < 0x7fffffffL);
-  const int gx = dca_persistent_grid(tiles, 1);
+  const DcaTileGrid t = dca_tile_grid<TD, TH, TW>(N, a.Do, a.Ho, a.Wo);
+  a.nTD = t.nTD; a.nTH = t.nTH; a.nTW = t.nTW;
+  DCA_REQUIRE(t.fits());
+  const int gx = dca_persistent_grid(t.tiles, 1);
   return dtype == DCA_BF16 ? launch_s2<__bf16>(a, gx, stream) : launch_s2<_Float16>(a, gx, stream);
 }

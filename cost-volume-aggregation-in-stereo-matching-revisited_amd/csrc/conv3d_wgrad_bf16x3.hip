@@ -22,18 +22,8 @@
 // groups are summed through LDS and the workgroup writes one slab of partial sums; wgrad_reduce_kernel
 // (conv3d_wgrad.hip) adds the slabs in a fixed order: bitwise reproducible, no atomics.
 #include "dca_frag.h"
+#include "dca_tiles.h"
 #include <type_traits>
-
-// WX3_STAMP (debug build, tools/wx3_stamps.py): `part` is followed by an unsigned long long stamp buffer (the tool
-// allocates it) that receives s_memtime stamps of the first 64 tiles of workgroup 0, waves 0 and 3
-#ifndef WX3_STAMP
-#define WX3_STAMP 0
-#endif
-#if WX3_STAMP
-#define WX3_MARK(i) do { if (stamp_on && stamp_k < 64) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) stamps[((wq == 3) * 64 + stamp_k) * 8 + (i)] = t_; } } while (0)
-#else
-#define WX3_MARK(i) do { } while (0)
-#endif
 
 namespace {
 
@@ -65,10 +55,8 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
   const int grp = wv >> 2, wq = wv & 3;
   const int ct = blockIdx.y, cy0 = (ct / a.nCxT) * 32, cx0 = (ct % a.nCxT) * 32;
 
-  const long T = (long)a.N * a.nTD * a.nTH * a.nTW;
-  const int nx = gridDim.x >= 8 ? 8 : 1, xcd = blockIdx.x % nx;
-  const int cnt = (gridDim.x - xcd + nx - 1) / nx;
-  const int t_begin = (int)(T * xcd / nx) + blockIdx.x / nx, t_end = (int)(T * (xcd + 1) / nx), t_step = cnt;
+  const DcaTileWalk walk = dca_my_tile_walk((long)a.N * a.nTD * a.nTH * a.nTW);   // dca_tiles.h
+  const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
 
   f32x16 acc[7];
 #pragma unroll
@@ -83,11 +71,7 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
   float4 rx[KX][2], ry[KY][2];
   float re[KE];
   auto decode = [&](int tile, int& n, int& d0, int& h0, int& w0) __attribute__((always_inline)) {
-    const int tw = tile % a.nTW; tile /= a.nTW;
-    const int th = tile % a.nTH; tile /= a.nTH;
-    const int td = tile % a.nTD;
-    n = tile / a.nTD;
-    d0 = td * TD; h0 = th * TH; w0 = tw * TW;
+    dca_tile_decode<TD, TH, TW>(tile, a.nTD, a.nTH, a.nTW, n, d0, h0, w0);
   };
   auto load_tile = [&](int n, int d0, int h0, int w0) __attribute__((always_inline)) {
     const __amdgpu_buffer_rsrc_t xr = dca_rsrc(a.x + (long)n * xsample, xsample * 4);
@@ -153,7 +137,7 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
   // The MFMA phase of one tile for tap group WQ (taps 7*WQ .. 7*WQ+6, < 27).  The next tile's global loads are issued
   // BEHIND the first K-step's MFMAs: in front of the phase the address arithmetic and the memory pipe's back-pressure of
   // 11 load instructions per thread kept all eight waves -- and the matrix pipe -- busy for 1600-1900 of a tile's 18.9 k
-  // cycles (s_memtime stamps, tools/wx3_stamps.py).
+  // cycles (s_memtime stamps; the instrumented build is in history before this commit).
   auto mfma_tile = [&](auto WQC, bool more, int next_tile) __attribute__((always_inline)) {
     constexpr int WQ = decltype(WQC)::value;
     constexpr int TAP0 = 7 * WQ, TAP1 = (TAP0 + 7 < 27) ? TAP0 + 7 : 27;
@@ -217,11 +201,6 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
     }
   };
 
-#if WX3_STAMP
-  unsigned long long* stamps = (unsigned long long*)(a.part + (long)gridDim.x * gridDim.y * 27 * 1024);
-  const bool stamp_on = blockIdx.x == 0 && blockIdx.y == 0 && grp == 0 && (wq == 0 || wq == 3);
-  int stamp_k = 0;
-#endif
   if (t_begin < t_end) {
     int n, d0, h0, w0;
     decode(t_begin, n, d0, h0, w0);
@@ -231,24 +210,15 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
 #pragma unroll 1
     for (int tile = t_begin; tile < t_end; tile += t_step) {
       const bool more = tile + t_step < t_end;
-      WX3_MARK(0);
-      WX3_MARK(1);
       switch (wq) {
         case 0: mfma_tile(std::integral_constant<int, 0>{}, more, tile + t_step); break;
         case 1: mfma_tile(std::integral_constant<int, 1>{}, more, tile + t_step); break;
         case 2: mfma_tile(std::integral_constant<int, 2>{}, more, tile + t_step); break;
         default: mfma_tile(std::integral_constant<int, 3>{}, more, tile + t_step); break;
       }
-      WX3_MARK(2);
       __syncthreads();  // every wave is done reading this tile
-      WX3_MARK(3);
       if (more) store_tile();
-      WX3_MARK(4);
       __syncthreads();
-      WX3_MARK(5);
-#if WX3_STAMP
-      ++stamp_k;
-#endif
     }
   }
 
@@ -278,28 +248,12 @@ __global__ __launch_bounds__(512) void wgrad3_bf16x3_kernel(WX3Args a) {
   }
 }
 
-// launch geometry: nblk persistent workgroups per channel-tile pair, each writing one slab of 27 * 1024 floats
-struct WX3Geom {
-  int nTD, nTH, nTW, nCxT, nCT, nblk;
-  long ntiles, part_floats;
-};
-WX3Geom wx3_geometry(int N, int Cx, int Cy, int D, int H, int W) {
-  WX3Geom g;
-  g.nTD = cdiv(D, TD); g.nTH = cdiv(H, TH); g.nTW = cdiv(W, TW);
-  g.ntiles = (long)N * g.nTD * g.nTH * g.nTW;
-  g.nCxT = cdiv(Cx, 32);
-  g.nCT = g.nCxT * cdiv(Cy, 32);
-  g.nblk = dca_persistent_grid(g.ntiles, g.nCT);
-  g.part_floats = (long)g.nblk * g.nCT * 27 * 1024;
-  return g;
-}
-
 }  // namespace
 
 // floats of scratch `part` dca_conv3d_wgrad_x3 needs
 extern "C" long dca_conv3d_wgrad_x3_workspace(int N, int Cx, int Cy, int D, int H, int W) {
   if (N <= 0 || Cx <= 0 || Cy <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-  return wx3_geometry(N, Cx, Cy, D, H, W).part_floats;
+  return dca_wgrad_split_geometry<TD, TH, TW>(N, Cx, Cy, D, H, W).part_floats;
 }
 
 // dw[cy*s_cy + cx*s_cx + tap] = sum dy[cy] * x[cx] shifted by the tap (3x3x3, stride 1, pad 1); x (N,Cx,D,H,W),
@@ -311,9 +265,9 @@ extern "C" int dca_conv3d_wgrad_x3(const float* x, const float* dy, float* part,
   DCA_REQUIRE((long)Cx * D * H * W * 4 < 0x7ffffff0L && (long)Cy * D * H * W * 4 < 0x7ffffff0L);
   WX3Args a;
   a.x = x; a.dy = dy; a.part = part; a.N = N; a.Cx = Cx; a.Cy = Cy; a.D = D; a.H = H; a.W = W;
-  const WX3Geom g = wx3_geometry(N, Cx, Cy, D, H, W);
-  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW; a.nCxT = g.nCxT;
-  DCA_REQUIRE(g.ntiles < 0x7fffffffL && g.nCT <= 65535);
+  const DcaWgradSplitGeom g = dca_wgrad_split_geometry<TD, TH, TW>(N, Cx, Cy, D, H, W);
+  a.nTD = g.t.nTD; a.nTH = g.t.nTH; a.nTW = g.t.nTW; a.nCxT = g.nCxT;
+  DCA_REQUIRE(g.t.fits() && g.nCT <= 65535);
   hipError_t e = hipFuncSetAttribute((const void*)wgrad3_bf16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      LDS_BYTES);
   if (e != hipSuccess) return (int)e;

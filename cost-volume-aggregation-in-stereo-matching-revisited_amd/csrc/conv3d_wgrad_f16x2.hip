@@ -25,6 +25,7 @@
 // one slab of partial sums; wgrad_reduce_kernel (conv3d_wgrad.hip) adds the slabs in a fixed order: bitwise
 // reproducible, no atomics.
 #include "dca_frag.h"
+#include "dca_tiles.h"
 #include <type_traits>
 
 namespace {
@@ -70,10 +71,8 @@ __global__ __launch_bounds__(512) void wgrad3_f16x2_kernel(WX2Args a) {
   const int grp = wv >> 2, wq = wv & 3;
   const int ct = blockIdx.y, cy0 = (ct / a.nCxT) * 32, cx0 = (ct % a.nCxT) * 32;
 
-  const long T = (long)a.N * a.nTD * a.nTH * a.nTW;
-  const int nx = gridDim.x >= 8 ? 8 : 1, xcd = blockIdx.x % nx;
-  const int cnt = (gridDim.x - xcd + nx - 1) / nx;
-  const int t_begin = (int)(T * xcd / nx) + blockIdx.x / nx, t_end = (int)(T * (xcd + 1) / nx), t_step = cnt;
+  const DcaTileWalk walk = dca_my_tile_walk((long)a.N * a.nTD * a.nTH * a.nTW);   // dca_tiles.h
+  const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
 
   f32x16 acc[NACC];
 #pragma unroll
@@ -126,11 +125,7 @@ __global__ __launch_bounds__(512) void wgrad3_f16x2_kernel(WX2Args a) {
     }
   }
   auto decode = [&](int tile, int& n, int& d0, int& h0, int& w0) __attribute__((always_inline)) {
-    const int tw = tile % a.nTW; tile /= a.nTW;
-    const int th = tile % a.nTH; tile /= a.nTH;
-    const int td = tile % a.nTD;
-    n = tile / a.nTD;
-    d0 = td * TD; h0 = th * TH; w0 = tw * TW;
+    dca_tile_decode<TD, TH, TW>(tile, a.nTD, a.nTH, a.nTW, n, d0, h0, w0);
   };
   // part 0: the first half of the x loads (packed: words 0-3; fp32: the quad), part 1: the rest of x and dy; -1: everything
   auto load_tile = [&](int n, int d0, int h0, int w0, int part = -1) __attribute__((always_inline)) {
@@ -417,28 +412,12 @@ __global__ __launch_bounds__(512) void wgrad3_f16x2_kernel(WX2Args a) {
   }
 }
 
-// launch geometry: nblk persistent workgroups per channel-tile pair, each writing one slab of 27 * 1024 floats
-struct WX2Geom {
-  int nTD, nTH, nTW, nCxT, nCT, nblk;
-  long ntiles, part_floats;
-};
-WX2Geom wx2_geometry(int N, int Cx, int Cy, int D, int H, int W) {
-  WX2Geom g;
-  g.nTD = cdiv(D, TD); g.nTH = cdiv(H, TH); g.nTW = cdiv(W, TW);
-  g.ntiles = (long)N * g.nTD * g.nTH * g.nTW;
-  g.nCxT = cdiv(Cx, 32);
-  g.nCT = g.nCxT * cdiv(Cy, 32);
-  g.nblk = dca_persistent_grid(g.ntiles, g.nCT);
-  g.part_floats = (long)g.nblk * g.nCT * 27 * 1024;
-  return g;
-}
-
 }  // namespace
 
 // floats of scratch `part` dca_conv3d_wgrad_x2 needs
 extern "C" long dca_conv3d_wgrad_x2_workspace(int N, int Cx, int Cy, int D, int H, int W) {
   if (N <= 0 || Cx <= 0 || Cy <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-  return wx2_geometry(N, Cx, Cy, D, H, W).part_floats;
+  return dca_wgrad_split_geometry<TD, TH, TW>(N, Cx, Cy, D, H, W).part_floats;
 }
 
 // dw[cy*s_cy + cx*s_cx + tap] = sum dy[cy] * x[cx] shifted by the tap (3x3x3, stride 1, pad 1); x (N,Cx,D,H,W),
@@ -455,9 +434,9 @@ extern "C" int dca_conv3d_wgrad_x2(const void* x, int x_packed, const int* xexps
   WX2Args a;
   a.x = (const float*)x; a.dy = (const float*)dy; a.part = part; a.xexps = xexps; a.yexps = yexps;
   a.N = N; a.Cx = Cx; a.Cy = Cy; a.D = D; a.H = H; a.W = W;
-  const WX2Geom g = wx2_geometry(N, Cx, Cy, D, H, W);
-  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW; a.nCxT = g.nCxT;
-  DCA_REQUIRE(g.ntiles < 0x7fffffffL && g.nCT <= 65535);
+  const DcaWgradSplitGeom g = dca_wgrad_split_geometry<TD, TH, TW>(N, Cx, Cy, D, H, W);
+  a.nTD = g.t.nTD; a.nTH = g.t.nTH; a.nTW = g.t.nTW; a.nCxT = g.nCxT;
+  DCA_REQUIRE(g.t.fits() && g.nCT <= 65535);
   const int lds = LDS_BYTES + 128;     // + the 32 exponents of the block's dy channels (end of kernel)
   auto kern = x_packed ? (dy_packed ? wgrad3_f16x2_kernel<true, true> : wgrad3_f16x2_kernel<true, false>)
                        : (dy_packed ? wgrad3_f16x2_kernel<false, true> : wgrad3_f16x2_kernel<false, false>);

@@ -25,6 +25,7 @@
 // slab of partial sums; wgrad_reduce_kernel (conv3d_wgrad.hip) adds the slabs in a fixed order: bitwise reproducible, no
 // atomics.
 #include "dca_frag.h"
+#include "dca_tiles.h"
 #include <type_traits>
 
 namespace {
@@ -66,10 +67,8 @@ __global__ __launch_bounds__(512) void wgrad3s2_f16x2_kernel(WS2Args a) {
   const int ct = blockIdx.y, cyp = ct / a.nCxT, cx0 = (ct % a.nCxT) * 32, cy0 = cyp * 64;
   const bool blk_on = cy0 + 32 * blk < a.Cy;          // a coarse tensor with one 32-channel block: waves 4-7 only stage
 
-  const long T = (long)a.N * a.nTD * a.nTH * a.nTW;
-  const int nx = gridDim.x >= 8 ? 8 : 1, xcd = blockIdx.x % nx;
-  const int cnt = (gridDim.x - xcd + nx - 1) / nx;
-  const int t_begin = (int)(T * xcd / nx) + blockIdx.x / nx, t_end = (int)(T * (xcd + 1) / nx), t_step = cnt;
+  const DcaTileWalk walk = dca_my_tile_walk((long)a.N * a.nTD * a.nTH * a.nTW);   // dca_tiles.h
+  const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
 
   f32x16 acc[7];
 #pragma unroll
@@ -98,11 +97,7 @@ __global__ __launch_bounds__(512) void wgrad3s2_f16x2_kernel(WS2Args a) {
   __syncthreads();
   const int yu = tid - (NXQ - 512);               // coarse item of this thread (second round), valid for 0 <= yu < NYQ
   auto decode = [&](int tile, int& n, int& d0, int& h0, int& w0) __attribute__((always_inline)) {
-    const int tw = tile % a.nTW; tile /= a.nTW;
-    const int th = tile % a.nTH; tile /= a.nTH;
-    const int td = tile % a.nTD;
-    n = tile / a.nTD;
-    d0 = td; h0 = th * TH; w0 = tw * TW;            // coarse coordinates
+    dca_tile_decode<1, TH, TW>(tile, a.nTD, a.nTH, a.nTW, n, d0, h0, w0);     // coarse coordinates
   };
   // part 0: the first round of fine items, part 1: the rest (second round, edge voxels, coarse items), part -1: all
   auto load_tile = [&](int n, int d0, int h0, int w0, int part = -1) __attribute__((always_inline)) {
@@ -270,18 +265,18 @@ __global__ __launch_bounds__(512) void wgrad3s2_f16x2_kernel(WS2Args a) {
 // launch geometry from the FINE dims D, H, W: nblk persistent workgroups per (32 x channels, 64 dy channels) block pair, each
 // writing its two slabs of 27 * 1024 floats per 32 x 32 channel tile (nCT of them)
 struct WS2Geom {
-  int Do, Ho, Wo, nTD, nTH, nTW, nCxT, nCyP, nWG, nCT, nblk;
-  long ntiles, part_floats;
+  int Do, Ho, Wo, nCxT, nCyP, nWG, nCT, nblk;
+  DcaTileGrid t;             // tiles of 1 x TH x TW coarse voxels
+  long part_floats;
 };
 WS2Geom ws2_geometry(int N, int Cx, int Cy, int D, int H, int W) {
   WS2Geom g;
   g.Do = (D + 1) / 2; g.Ho = (H + 1) / 2; g.Wo = (W + 1) / 2;
-  g.nTD = g.Do; g.nTH = cdiv(g.Ho, TH); g.nTW = cdiv(g.Wo, TW);
-  g.ntiles = (long)N * g.nTD * g.nTH * g.nTW;
+  g.t = dca_tile_grid<1, TH, TW>(N, g.Do, g.Ho, g.Wo);
   g.nCxT = cdiv(Cx, 32); g.nCyP = cdiv(Cy, 64);
   g.nWG = g.nCxT * g.nCyP;
   g.nCT = g.nCxT * cdiv(Cy, 32);
-  g.nblk = dca_persistent_grid(g.ntiles, g.nWG);
+  g.nblk = dca_persistent_grid(g.t.tiles, g.nWG);
   g.part_floats = (long)g.nblk * g.nCT * 27 * 1024;
   return g;
 }
@@ -308,8 +303,8 @@ extern "C" int dca_conv3d_wgrad_s2_x2(const float* f, const int* f_exps, const f
   a.Do = g.Do; a.Ho = g.Ho; a.Wo = g.Wo;
   DCA_REQUIRE(W % 4 == 0 && a.Wo % 4 == 0 && ((((uintptr_t)f | (uintptr_t)c) & 15) == 0));
   DCA_REQUIRE((long)Cx * D * H * W * 4 < 0x7ffffff0L && (long)Cy * a.Do * a.Ho * a.Wo * 4 < 0x7ffffff0L);
-  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW; a.nCxT = g.nCxT; a.nCyP = g.nCyP;
-  DCA_REQUIRE(g.ntiles < 0x7fffffffL && g.nWG <= 65535);
+  a.nTD = g.t.nTD; a.nTH = g.t.nTH; a.nTW = g.t.nTW; a.nCxT = g.nCxT; a.nCyP = g.nCyP;
+  DCA_REQUIRE(g.t.fits() && g.nWG <= 65535);
   const int lds = LDS_BYTES + 96 * 4;      // + the exponents of the block's channels
   hipError_t e = hipFuncSetAttribute((const void*)wgrad3s2_f16x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (e != hipSuccess) return (int)e;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dca_hip.h"  // every translation unit that defines an entry point is compiled against its declaration
+#include "dca_tiles.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -37,6 +38,23 @@ static inline int dca_num_cus() {
 static inline int dca_persistent_grid(long tiles, int share) {
   const int ncu = dca_num_cus(), g = ncu > share ? ncu / share : 1;
   return (int)(tiles < g ? tiles : g);
+}
+// the stride-1 split weight gradients (conv3d_wgrad_f16x2.hip, conv3d_wgrad_bf16x3.hip): nblk persistent workgroups per
+// channel-tile pair, each writing one slab of 27 * 1024 floats
+struct DcaWgradSplitGeom {
+  DcaTileGrid t;
+  int nCxT, nCT, nblk;
+  long part_floats;
+};
+template <int TD, int TH, int TW>
+static inline DcaWgradSplitGeom dca_wgrad_split_geometry(int N, int Cx, int Cy, int D, int H, int W) {
+  DcaWgradSplitGeom g;
+  g.t = dca_tile_grid<TD, TH, TW>(N, D, H, W);
+  g.nCxT = cdiv(Cx, 32);
+  g.nCT = g.nCxT * cdiv(Cy, 32);
+  g.nblk = dca_persistent_grid(g.t.tiles, g.nCT);
+  g.part_floats = (long)g.nblk * g.nCT * 27 * 1024;
+  return g;
 }
 // sums the weight-gradient slabs part[blk][ct][tap][32 x 32] of nblk workgroups into dw (conv3d_wgrad.hip)
 int dca_internal_wgrad_reduce(const float* part, float* dw, int nblk, int nCxT, int nCT, int K, int Cy, int Cx, long s_cy,
@@ -97,11 +115,6 @@ __device__ __forceinline__ float dca_bload1(__amdgpu_buffer_rsrc_t r, int byte_o
 // masked store: an out-of-range offset is dropped by the hardware
 __device__ __forceinline__ void dca_bstore1(__amdgpu_buffer_rsrc_t r, float v, int byte_off, int ok) {
   __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, dca_pred_off(byte_off, ok), 0, 0);
-}
-// non-temporal variant (gfx950 cache-policy bit 1 = nt): for outputs that are written once and read much later, so that
-// they do not displace the halo / weight lines the kernel re-reads from L2
-__device__ __forceinline__ void dca_bstore1_nt(__amdgpu_buffer_rsrc_t r, float v, int byte_off, int ok) {
-  __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, dca_pred_off(byte_off, ok), 0, 2);
 }
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float2 dca_bload2(__amdgpu_buffer_rsrc_t r, int byte_off, int ok) {

@@ -18,6 +18,7 @@
 // epilogue packs them into one dword per (d-parity, h-parity, channel): 64 coalesced dword stores per lane, no lane
 // exchange; residuals come in the same way.
 #include "dca_frag.h"
+#include "dca_tiles.h"
 #include "../../include/dca_hip.h"
 
 namespace {
@@ -58,10 +59,8 @@ __global__ __launch_bounds__(512) void deconv3_lp_kernel(DlArgs a) {
   __shared__ float aff_lds[64];
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, half = lane >> 5;
-  const long T = (long)a.N * a.nTD * a.nTH * a.nTW;
-  const int nx = gridDim.x >= 8 ? 8 : 1, xcd = blockIdx.x % nx;
-  const int cnt = (gridDim.x - xcd + nx - 1) / nx;
-  const int t_begin = (int)(T * xcd / nx) + blockIdx.x / nx, t_end = (int)(T * (xcd + 1) / nx), t_step = cnt;
+  const DcaTileWalk walk = dca_my_tile_walk((long)a.N * a.nTD * a.nTH * a.nTW);   // dca_tiles.h
+  const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
   if (t_begin >= t_end) return;
 
   const bool has_aff = a.scale != nullptr, has_pre = a.res_pre != nullptr, has_post = a.res_post != nullptr;
@@ -165,18 +164,11 @@ __global__ __launch_bounds__(512) void deconv3_lp_kernel(DlArgs a) {
     }
   };
   auto decode = [&](int tile, int& n, int& d0, int& h0, int& w0) __attribute__((always_inline)) {
-    const int tw = tile % a.nTW; tile /= a.nTW;
-    const int th = tile % a.nTH; tile /= a.nTH;
-    const int td = tile % a.nTD;
-    n = tile / a.nTD;
-    d0 = td * TD; h0 = th * TH; w0 = tw * TW;
+    dca_tile_decode<TD, TH, TW>(tile, a.nTD, a.nTH, a.nTW, n, d0, h0, w0);
   };
-  struct Cursor { int tile, chunk, n, d0, h0, w0; };
+  typedef DcaTileStep Cursor;
   auto advance = [&](Cursor& c) __attribute__((always_inline)) {
-    if (c.chunk + 1 < a.NCH) { ++c.chunk; return; }
-    c.chunk = 0;
-    c.tile += t_step;
-    if (c.tile < t_end) decode(c.tile, c.n, c.d0, c.h0, c.w0);
+    dca_tile_advance<TD, TH, TW>(c, a.NCH, walk, a.nTD, a.nTH, a.nTW);
   };
 
   int n, d0, h0, w0;
@@ -301,10 +293,10 @@ extern "C" int dca_deconv3d_lp_forward(const float* x, const void* wx, void* y, 
   a.res_pre = res_pre; a.res_post = res_post; a.slope = slope;
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.NCH = (Cin + 15) / 16;
   a.Di = Di; a.Hi = Hi; a.Wi = Wi;
-  a.nTD = cdiv(Di, TD); a.nTH = cdiv(Hi, TH); a.nTW = cdiv(Wi, TW);
-  const long tiles = (long)N * a.nTD * a.nTH * a.nTW;
-  DCA_REQUIRE(tiles < 0x7fffffffL);
+  const DcaTileGrid t = dca_tile_grid<TD, TH, TW>(N, Di, Hi, Wi);
+  a.nTD = t.nTD; a.nTH = t.nTH; a.nTW = t.nTW;
+  DCA_REQUIRE(t.fits());
   const bool vec = (Wi % 4 == 0) && ((((uintptr_t)x) & 15) == 0);
-  const int gx = dca_persistent_grid(tiles, 1);
+  const int gx = dca_persistent_grid(t.tiles, 1);
   return dtype == DCA_BF16 ? launch_dl<__bf16>(a, vec, gx, stream) : launch_dl<_Float16>(a, vec, gx, stream);
 }

@@ -25,7 +25,7 @@
 // Instead the workgroup runs as two half-groups in opposite phases (MI355X_MICROARCH.md, "Two waves per SIMD"): in
 // slot 2s waves 0-3 issue the MFMAs of step s while waves 4-7 are in their "load slot" -- write their half of step
 // s+1's data (fetched into registers one slot earlier) into the idle LDS buffers and request their half of step s+2
-// -- and in slot 2s+1 the roles swap; one barrier per slot.  In-kernel s_memtime stamps (DX3_STAMP, tools/dx3_stamps.py)
+// -- and in slot 2s+1 the roles swap; one barrier per slot.  In-kernel s_memtime stamps (the instrumented build is in history)
 // showed what a load slot can afford: beside the partner's MFMA stream a vector instruction of the loading wave takes
 // ~18 cycles, so splitting the halo into bf16 terms there (90 instructions) made the load slot (2500 cycles) longer
 // than the compute slot (2250); the computing wave's own vector instructions between its MFMAs are nearly free.  Hence
@@ -33,24 +33,11 @@
 // with the MFMAs (11 instructions per channel pair), the pass epilogue runs at the end of the compute slot, and a load
 // slot is nothing but waits, register moves and LDS stores.
 #include "dca_frag.h"
+#include "dca_tiles.h"
 #include "bn_fused_stats.h"
 #include "../../include/dca_hip.h"
 
-// non-temporal output stores: off, as in conv3d_bf16x3.hip (the consumer finds y in the infinity cache)
-#ifndef DX3_NT
-#define DX3_NT 0
-#endif
-
-// DX3_STAMP (debug build, tools/dx3_stamps.py): res_post is reinterpreted as an unsigned long long buffer that receives
-// s_memtime stamps of the first 96 slots of workgroup 0, waves 0 and 4
-#ifndef DX3_STAMP
-#define DX3_STAMP 0
-#endif
-#if DX3_STAMP
-#define DX3_MARK(i) do { if (stamp_on && k < 96) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) stamps[(grp * 96 + k) * 6 + (i)] = t_; } } while (0)
-#else
-#define DX3_MARK(i) do { } while (0)
-#endif
+// output stores are plain, not non-temporal, as in conv3d_bf16x3.hip (the consumer finds y in the infinity cache)
 
 namespace {
 
@@ -124,10 +111,8 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: the slot role and the cursors stay scalar
   const int grp = wv >> 2, gt = tid & 255;
-  const long T = (long)a.N * a.nTD * a.nTH * a.nTW;
-  const int nx = gridDim.x >= 8 ? 8 : 1, xcd = blockIdx.x % nx;
-  const int cnt = (gridDim.x - xcd + nx - 1) / nx;
-  const int t_begin = (int)(T * xcd / nx) + blockIdx.x / nx, t_end = (int)(T * (xcd + 1) / nx), t_step = cnt;
+  const DcaTileWalk walk = dca_my_tile_walk((long)a.N * a.nTD * a.nTH * a.nTW);   // dca_tiles.h
+  const int t_begin = walk.begin, t_end = walk.end, t_step = walk.step;
   float* stat_w = stat_lds + wv * FS_WAVE_FLOATS;   // this wave's slots
   bool stat_first = true;
   float st_s[STATS ? 16 : 1], st_q[STATS ? 16 : 1], st_n = 0.f;
@@ -157,11 +142,6 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
     return;
   }
 
-#if DX3_STAMP
-  unsigned long long* stamps = (unsigned long long*)a.res_post;
-  a.res_post = nullptr;
-  const bool stamp_on = blockIdx.x == 0 && (wv == 0 || wv == 4);
-#endif
   const bool has_aff = a.scale != nullptr, has_pre = a.res_pre != nullptr, has_post = a.res_post != nullptr;
   if (tid < 64) {
     const int co = min(tid & 31, a.Cout - 1);
@@ -245,32 +225,22 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
     }
   };
   auto decode = [&](int tile, int& n, int& d0, int& h0, int& w0) __attribute__((always_inline)) {
-    const int tw = tile % a.nTW; tile /= a.nTW;
-    const int th = tile % a.nTH; tile /= a.nTH;
-    const int td = tile % a.nTD;
-    n = tile / a.nTD;
-    d0 = td * TD; h0 = th * TH; w0 = tw * TW;
+    dca_tile_decode<TD, TH, TW>(tile, a.nTD, a.nTH, a.nTW, n, d0, h0, w0);
   };
   // a step and the LDS buffers it lives in (pa: weight slab buffer, toggles every step; pb: halo image, toggles when
   // the step brings a new chunk)
-  struct Cursor { int tile, s, n, d0, h0, w0, pa, pb; };
+  struct Cursor : DcaTileStep { int pa, pb; };     // `chunk` of the record counts the steps of the tile (S per tile)
   auto advance = [&](Cursor& c) __attribute__((always_inline)) {
     c.pa ^= 1;
-    if (c.s + 1 < S) {
-      ++c.s;
-    } else {
-      c.s = 0;
-      c.tile += t_step;
-      if (c.tile < t_end) decode(c.tile, c.n, c.d0, c.h0, c.w0);
-    }
-    if (step_newb(c.s)) c.pb ^= 1;
+    dca_tile_advance<TD, TH, TW>(c, S, walk, a.nTD, a.nTH, a.nTW);
+    if (step_newb(c.chunk)) c.pb ^= 1;
   };
 
   const int Do = 2 * a.Di, Ho = 2 * a.Hi, Wo = 2 * a.Wi;
   const int ostride = Do * Ho * Wo;
   const long osample = (long)a.Cout * ostride;
 
-  Cursor cur{t_begin, 0, 0, 0, 0, 0, 0, 0}, st, ld;
+  Cursor cur{{t_begin, 0, 0, 0, 0, 0}, 0, 0}, st, ld;
   decode(t_begin, cur.n, cur.d0, cur.h0, cur.w0);
   load_B(cur.n, cur.d0, cur.h0, cur.w0, 0);
   load_A(0);
@@ -278,8 +248,8 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
   store_A(0);
   st = cur;
   advance(st);       // S >= 3: the second step always exists
-  load_A(st.s);
-  if (step_newb(st.s)) load_B(st.n, st.d0, st.h0, st.w0, step_chunk(st.s));
+  load_A(st.chunk);
+  if (step_newb(st.chunk)) load_B(st.n, st.d0, st.h0, st.w0, step_chunk(st.chunk));
   ld = st;
   advance(ld);
   __syncthreads();
@@ -295,12 +265,11 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
   // slot k: half-group 0 computes at even k and is in its load slot at odd k; half-group 1 the other way round
 #pragma unroll 1
   for (int k = 0; k < nslots; ++k) {
-    DX3_MARK(0);
     if (((k + grp) & 1) == 0) {
       // ---- compute slot: fragment reads, in-register split, 54 MFMAs.  The computing wave outranks its loading partner
       // on the SIMD's vector issue (waves 4-7 otherwise lose the age arbitration and run ~12 % longer slots).
       __builtin_amdgcn_s_setprio(1);
-      const int kd = step_kd(cur.s);
+      const int kd = step_kd(cur.chunk);
       const char* ab = a_lds + cur.pa * A_SLAB + lane * 16;
       const char* bb = b_lds + cur.pb * B_IMG + boff + (kd == 0 ? IH * IW * 16 : 0);   // taps kd = 0 read x[m + 1] along d
       // the four (h, w) neighbours x[m + delta] of this lane's position, raw fp32.  Taps are visited grouped by neighbour --
@@ -372,13 +341,12 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
         __builtin_amdgcn_sched_barrier(0);
       }
       __builtin_amdgcn_s_setprio(0);
-      DX3_MARK(3);
-      if (cur.s == a.NCH - 1 || cur.s == S - 1) {
+      if (cur.chunk == a.NCH - 1 || cur.chunk == S - 1) {
         // end of a pass: y = act(acc * scale + shift + res_pre) + res_post on output planes 2m + pd; a lane holds the two
         // w-parities of (h-parity, channel) = 8 contiguous bytes, 16 lanes 128 contiguous bytes.  With all 32 output
         // channels present the channel part of a plain store's address is a scalar offset (no vector instruction per store);
         // otherwise it stays in the vector offset, where the hardware range check drops channels >= Cout.
-        const int pd = cur.s == S - 1;
+        const int pd = cur.chunk == S - 1;
         const int md = cur.d0 + dl, mh = cur.h0 + hl, mw = cur.w0 + wl;
         const int ok = (int)(md < a.Di) & (int)(mh < a.Hi) & (int)(mw < a.Wi);
         const __amdgpu_buffer_rsrc_t yr = dca_rsrc(a.y + (long)cur.n * osample, osample * 4);
@@ -392,8 +360,8 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
             for (int r = 0; r < 16; ++r) {
               const u32x2 o = {__float_as_uint(acc[ph * 2][r]), __float_as_uint(acc[ph * 2 + 1][r])};
               const int coff = ((r & 3) + 8 * (r >> 2)) * ostride * 4;
-              if (cout_full) __builtin_amdgcn_raw_buffer_store_b64(o, yr, base, coff, DX3_NT ? 2 : 0);
-              else __builtin_amdgcn_raw_buffer_store_b64(o, yr, base + coff, 0, DX3_NT ? 2 : 0);
+              if (cout_full) __builtin_amdgcn_raw_buffer_store_b64(o, yr, base, coff, 0);
+              else __builtin_amdgcn_raw_buffer_store_b64(o, yr, base + coff, 0, 0);
             }
           }
           if constexpr (STATS) {   // per-lane running sums (reduced over lanes and waves once, at the end of the kernel)
@@ -444,7 +412,7 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
                 const float v0 = act_apply(acc[ph * 2][r] * sc + sh + __uint_as_float(wp[q].x), a.slope) + __uint_as_float(wq[q].x);
                 const float v1 = act_apply(acc[ph * 2 + 1][r] * sc + sh + __uint_as_float(wp[q].y), a.slope) + __uint_as_float(wq[q].y);
                 const u32x2 o = {__float_as_uint(v0), __float_as_uint(v1)};
-                __builtin_amdgcn_raw_buffer_store_b64(o, yr, base + ((r & 3) + 8 * (r >> 2)) * ostride * 4, 0, DX3_NT ? 2 : 0);
+                __builtin_amdgcn_raw_buffer_store_b64(o, yr, base + ((r & 3) + 8 * (r >> 2)) * ostride * 4, 0, 0);
               }
             }
           }
@@ -454,29 +422,21 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
       }
-      DX3_MARK(2);
       advance(cur);
     } else {
       // ---- load slot: this half-group's share of the next step -> LDS, request the step after
-#if DX3_STAMP
-      __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0)
-      DX3_MARK(4);
-#endif
       if (st.tile < t_end) {
         store_A(st.pa);
-        if (step_newb(st.s)) store_B(st.pb);
+        if (step_newb(st.chunk)) store_B(st.pb);
       }
-      DX3_MARK(1);
       if (ld.tile < t_end) {
-        load_A(ld.s);
-        if (step_newb(ld.s)) load_B(ld.n, ld.d0, ld.h0, ld.w0, step_chunk(ld.s));
+        load_A(ld.chunk);
+        if (step_newb(ld.chunk)) load_B(ld.n, ld.d0, ld.h0, ld.w0, step_chunk(ld.chunk));
       }
       st = ld;
       advance(ld);
-      DX3_MARK(3);
     }
     __syncthreads();
-    DX3_MARK(5);
   }
   if constexpr (STATS) flush_stats();
 }
@@ -484,14 +444,13 @@ __global__ __launch_bounds__(512) void deconv3_bf16x3_kernel(DxArgs a) {
 // launch geometry (Di, Hi, Wi = input dims): persistent, one workgroup per CU; gx is also the number of statistics partials
 // per channel
 struct DxGeom {
-  int nTD, nTH, nTW, gx;
-  long tiles;
+  DcaTileGrid t;
+  int gx;
 };
 DxGeom dx_geometry(int N, int Di, int Hi, int Wi) {
   DxGeom g;
-  g.nTD = cdiv(Di, TD); g.nTH = cdiv(Hi, TH); g.nTW = cdiv(Wi, TW);
-  g.tiles = (long)N * g.nTD * g.nTH * g.nTW;
-  g.gx = dca_persistent_grid(g.tiles, 1);
+  g.t = dca_tile_grid<TD, TH, TW>(N, Di, Hi, Wi);
+  g.gx = dca_persistent_grid(g.t.tiles, 1);
   return g;
 }
 
@@ -509,9 +468,9 @@ int dx_launch(const float* x, const void* wx, float* y, const float* scale, cons
   a.N = N; a.Cin = Cin; a.Cout = Cout; a.NCH = (Cin + 15) / 16;
   a.Di = Di; a.Hi = Hi; a.Wi = Wi;
   const DxGeom g = dx_geometry(N, Di, Hi, Wi);
-  a.nTD = g.nTD; a.nTH = g.nTH; a.nTW = g.nTW;
+  a.nTD = g.t.nTD; a.nTH = g.t.nTH; a.nTW = g.t.nTW;
   a.stat_part = stat_part;
-  DCA_REQUIRE(g.tiles < 0x7fffffffL);
+  DCA_REQUIRE(g.t.fits());
   const bool stats = stat_part != nullptr;
   auto kern = stats ? deconv3_bf16x3_kernel<true> : deconv3_bf16x3_kernel<false>;
   const int lds = LDS_BYTES + (stats ? STAT_LDS : 0);

@@ -37,9 +37,7 @@ template <typename OT> struct Out;
 // feature rows in L2 -- measured 67.5 -> 57.4 us for the 251 MB fp32 volume at 544x960 / D=192 (4.95 -> 5.82 TB/s).
 // (The 2-byte volume, 8-byte stores per lane, measures 58 us with plain stores and 61-64 with non-temporal ones; packing
 // lane pairs into 16-byte stores interleaves two rows per store instruction and was slower still, 88 us: left plain.)
-#ifndef VF_NT
-#define VF_NT 1
-#endif
+constexpr int VF_NT = 1;
 template <> struct Out<float> {
   static __device__ __forceinline__ void store4(float* p, const float (&o)[4]) {
     const f32x4 v = {o[0], o[1], o[2], o[3]};

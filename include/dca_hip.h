@@ -151,6 +151,12 @@ int dca_conv1_x3_forward(const float* x, const float* x2, const void* wfrag, flo
  * kind 3 = dca_conv3d_x2_prep_weight with the fields of kind 1 and total = (dca_conv3d_x2_weight_bytes - 16)/2). */
 int dca_conv3d_prep_many(const void* table, int n, hipStream_t stream);
 
+/* The tile walk of the persistent 3x3x3 kernels (csrc/dca_tiles.h), on the HOST: of a launch of `grid` workgroups over
+ * `tiles` tiles, workgroup wg visits walk[0], walk[0] + walk[2], ... < walk[1] ({begin, end, step}; walk: 3 host ints).
+ * The very function the kernels call, so a CPU test can check that the walks of a launch visit every tile exactly once.
+ * No device is touched.  hipErrorInvalidValue unless 0 <= tiles < 0x7fffffff, grid > 0 and 0 <= wg < grid. */
+int dca_tile_walk(long tiles, int grid, int wg, int* walk);
+
 /* "bf16x3" split-precision 3x3x3 / stride-1 / pad-1 convolution (conv3d_bf16x3.hip): every fp32 operand is split exactly
  * into three bf16 terms and the six partial products >= 2^-16 run on the bf16 matrix pipe with fp32 accumulation --
  * fp32-grade results (dropped terms <= 2^-23 relative, no range restriction) at 2.67x fewer matrix-pipe cycles than

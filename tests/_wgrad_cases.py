@@ -109,8 +109,9 @@ def workgroups(family, ntiles, nCT, share, ncu):
 
 
 def split_walk(ntiles, nblk):
-    """tiles each workgroup of a split kernel visits: t_begin / t_end / t_step restated (eight XCD chunks of T * xcd / 8, each
-    shared by the `cnt` workgroups dealt to that XCD; one chunk when the grid has fewer than eight workgroups)"""
+    """tiles each workgroup of a split kernel visits: dca_tile_walk_of of csrc/dca_tiles.h restated on its own (eight XCD
+    chunks of T * xcd / 8, each shared by the `cnt` workgroups dealt to that XCD; one chunk when the grid has fewer than eight
+    workgroups); tests/test_wgrad_cases_cpu.py compares it with the library's dca_tile_walk"""
     nx = 8 if nblk >= 8 else 1
     out = []
     for b in range(nblk):

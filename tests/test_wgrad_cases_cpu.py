@@ -56,11 +56,53 @@ def test_scatter_leaves_every_other_element_alone(Cy, Cx, K, s_cy, s_cx, offset,
                 assert dest[offset + cy * s_cy + cx * s_cx + k] == ref[cy, cx, k]
 
 
+def library_walk(tiles, grid, wg):
+    """(status, [begin, end, step]) of dca_tile_walk: csrc/dca_tiles.h, the function the kernels call, run on the host"""
+    import ctypes
+    from dcanet_amd import _lib
+    out = (ctypes.c_int * 3)(-1, -1, -1)
+    return _lib.load().dca_tile_walk(tiles, grid, wg, ctypes.addressof(out)), list(out)
+
+
 @pytest.mark.parametrize("ntiles,nblk", [(96, 28), (12, 7), (75, 64), (270, 256), (120, 28), (288, 256), (9, 9), (1, 1)])
 def test_walks_visit_every_tile_once(ntiles, nblk):
     for walk in (W.split_walk, W.generic_walk):
         seen = sorted(t for w in walk(ntiles, nblk) for t in w)
         assert seen == list(range(ntiles)), walk.__name__
+    # the arithmetic the kernels run, not only its restatement
+    got = []
+    for wg in range(nblk):
+        st, (begin, end, step) = library_walk(ntiles, nblk, wg)
+        assert st == 0 and step >= 1, (wg, st, step)
+        got.append(list(range(begin, end, step)))
+    assert got == W.split_walk(ntiles, nblk)
+    assert sorted(t for w in got for t in w) == list(range(ntiles))
+
+
+@pytest.mark.parametrize("grid", [256, 7])
+def test_library_walk_does_not_overflow_at_the_largest_tile_count(grid):
+    """tiles = 0x7ffffffe, the largest count a launcher accepts: T * xcd and T * (xcd + 1) need 64-bit products"""
+    T = 0x7ffffffe
+    nx = 8 if grid >= 8 else 1
+    for wg in (0, 7, grid - 1):
+        if wg >= grid:     # wg 7 of a grid of 7 does not exist
+            assert library_walk(T, grid, wg)[0] == 1
+            continue
+        xcd = wg % nx
+        want = [T * xcd // nx + wg // nx, T * (xcd + 1) // nx, (grid - xcd + nx - 1) // nx]
+        assert library_walk(T, grid, wg) == (0, want), wg
+
+
+@pytest.mark.parametrize("tiles,grid,wg", [
+    (-1, 8, 0),                                  # tiles < 0
+    (0x7fffffff, 8, 0), (1 << 40, 8, 0),         # tiles >= 0x7fffffff: tile indices are ints in the kernels
+    (10, 0, 0), (10, -3, 0),                     # grid <= 0
+    (10, 8, -1), (10, 8, 8), (10, 1, 1),         # wg outside [0, grid)
+])
+def test_library_walk_refuses_invalid_arguments(tiles, grid, wg):
+    st, out = library_walk(tiles, grid, wg)
+    assert st == 1 and out == [-1, -1, -1], "hipErrorInvalidValue, nothing written"
+    assert library_walk(10, 8, 7)[0] == 0 and library_walk(0, 1, 0) == (0, [0, 0, 1])
 
 
 @pytest.mark.parametrize("case", W.EVERY, ids=IDS)
