@@ -5,7 +5,11 @@ the body of a binary PLY file -- and `depth_png` writes the KITTI 16-bit depth f
 the maps happens here.
 
 `RectifyMaps` holds the fixed-point maps that rectify a RAW stereo pair, built once per calibration in
-float64; `ops.rectify_pair` applies them on the device and `rectify_pair_host` is the numpy restatement of that kernel."""
+float64; `ops.rectify_pair` applies them on the device and `rectify_pair_host` is the numpy restatement of that kernel.
+
+`LidarCalib` holds the projection of a LiDAR scan into the rectified left image; `ops.lidar_disparity`
+turns a scan into sparse ground-truth maps on the device, `lidar_disparity_host` is its numpy restatement and
+`LidarProjector` the staging ring that feeds the device from host scans."""
 from __future__ import annotations
 
 import dataclasses
@@ -416,3 +420,277 @@ def rectify_pair_host(left, right, maps: RectifyMaps):
         res[..., :3] = (acc >> 10).astype(np.uint8)
         out.append(res)
     return out[0], out[1]
+
+
+# ---- sparse ground truth from a LiDAR scan (csrc/lidar.hip) ---------------------------------------------
+LIDAR_MAX_RADIUS = 8               # DCA_LIDAR_MAX_RADIUS of include/dca_hip.h: the largest half-size of the hidden-point window
+LIDAR_OUTPUTS = ("disp", "depth", "disp_u16", "count")
+# Default filters.  occl = (rx, ry, rel): the radii are read off the sensor's geometry (64 beams over about 27 degrees: about 5
+# image rows between scan lines at KITTI's focal length; 0.09 degrees of azimuth: about 1 column); rel = 0.1 comes from
+# nowhere, and none of the three was tuned on data.
+LIDAR_OCCL = (2, 4, 0.1)
+LIDAR_MIN_DEPTH = 1.0              # metres
+LIDAR_MAX_DEPTH = 120.0            # the range of a Velodyne HDL-64E
+LIDAR_MIN_DISP = 0.0
+LIDAR_MAX_DISP = 192.0             # the model's default maxdisp: mask = gt > 0 && gt < maxdisp
+
+
+def _kitti_rows(text_or_path):
+    rows = {}
+    for line in _text(text_or_path).splitlines():
+        key, sep, rest = line.partition(":")
+        if sep:
+            rows[key.strip()] = rest.split()
+    return rows
+
+
+def _kitti_numbers(rows, key, count):
+    if key not in rows:
+        raise ValueError(f"from_kitti_raw: no {key} in the calibration text")
+    if len(rows[key]) != count:
+        raise ValueError(f"from_kitti_raw: {key} has {len(rows[key])} numbers, expected {count}")
+    try:
+        a = np.array([float(x) for x in rows[key]], np.float64)
+    except ValueError:
+        raise ValueError(f"from_kitti_raw: {key} holds something that is not a number") from None
+    if not np.isfinite(a).all():
+        raise ValueError(f"from_kitti_raw: {key} holds a number that is not finite")
+    return a
+
+
+class LidarCalib:
+    """What `ops.lidar_disparity` needs to project a LiDAR scan into the rectified left image:
+      M       float32 (3,4): LiDAR coordinates -> homogeneous pixels (x, y, z) of the rectified left camera, u = x / z,
+              v = y / z, z the depth in metres; formed in float64 and rounded ONCE to 12 float32
+      stereo  the StereoCalib of the rectified pair: disparity d = stereo.fb / z - stereo.doffs
+      hw      (H, W) of the rectified image"""
+
+    def __init__(self, M, stereo, hw):
+        M = np.asarray(M, np.float64)
+        if M.shape != (3, 4) or not np.isfinite(M).all():
+            raise ValueError(f"LidarCalib: M must be a finite 3 x 4 array, got shape {M.shape}")
+        with np.errstate(over="ignore"):
+            M = M.astype(np.float32)
+        if not np.isfinite(M).all():
+            raise ValueError("LidarCalib: M does not fit float32")
+        if not isinstance(stereo, StereoCalib):
+            raise ValueError(f"LidarCalib: stereo must be a StereoCalib, got {type(stereo)}")
+        h, w = (int(v) for v in hw)
+        if h <= 0 or w <= 0 or h * w >= 1 << 31:
+            raise ValueError(f"LidarCalib: hw must be positive with H * W below 2^31, got {h} x {w}")
+        M.setflags(write=False)
+        self.M, self.stereo, self.hw = M, stereo, (h, w)
+
+    @classmethod
+    def from_matrix(cls, M, stereo, hw) -> "LidarCalib":
+        """M: any (3,4) array (rounded once from float64), stereo: a StereoCalib, hw: (H, W)"""
+        return cls(M, stereo, hw)
+
+    @classmethod
+    def from_kitti_raw(cls, cam_to_cam, velo_to_cam, left: str = "02", right: str = "03") -> "LidarCalib":
+        """KITTI raw `calib_cam_to_cam.txt` and `calib_velo_to_cam.txt` (texts or paths):
+          M = P_rect_<left> . [R_rect_00 0; 0 1] . [R T; 0 1]
+        with R (9 numbers) and T (3) of the velo-to-cam file, hw from S_rect_<left> (width height) and `stereo` from the two
+        P_rect matrices by the formulas of `StereoCalib.from_kitti`.  `RectifyMaps.from_kitti_raw` rectifies into this very
+        frame (KITTI's own rectified images), so the same M serves the dataset's rectified images and pairs rectified by
+        `ops.rectify_pair`: `hw == maps.dst_hw`."""
+        cam, velo = _kitti_rows(cam_to_cam), _kitti_rows(velo_to_cam)
+        Pl = _kitti_numbers(cam, f"P_rect_{left}", 12).reshape(3, 4)
+        Pr = _kitti_numbers(cam, f"P_rect_{right}", 12).reshape(3, 4)
+        R0 = np.eye(4)
+        R0[:3, :3] = _kitti_numbers(cam, "R_rect_00", 9).reshape(3, 3)
+        S = _kitti_numbers(cam, f"S_rect_{left}", 2)
+        if (S != np.round(S)).any():
+            raise ValueError(f"from_kitti_raw: S_rect_{left} must be an integer size, got {S}")
+        Tr = np.eye(4)
+        Tr[:3, :3] = _kitti_numbers(velo, "R", 9).reshape(3, 3)
+        Tr[:3, 3] = _kitti_numbers(velo, "T", 3)
+        stereo = StereoCalib(Pl[0, 0], Pl[0, 3] / Pl[0, 0] - Pr[0, 3] / Pr[0, 0], Pl[0, 2], Pl[1, 2], Pr[0, 2] - Pl[0, 2])
+        return cls(Pl @ R0 @ Tr, stereo, (int(S[1]), int(S[0])))
+
+
+def read_velodyne(path) -> np.ndarray:
+    """a KITTI `velodyne_points/data/*.bin` scan -> (N,4) float32 (x, y, z in metres, reflectance), the file as it is"""
+    a = np.fromfile(path, dtype="<f4")
+    if a.size % 4:
+        raise ValueError(f"{path}: {a.size} floats are no whole number of (x, y, z, reflectance) records")
+    return a.reshape(-1, 4)
+
+
+def _lidar_scalars(name, err, calib, N, S, n, occl, min_depth, max_depth, min_disp, max_disp, outputs):
+    """The scalar arguments of dca_lidar_disparity, checked as its launcher checks them (on the float32 values it is
+    handed) -> (n, rx, ry, rel, fb, doffs, min_depth, max_depth, min_disp, max_disp) with the floats already rounded to
+    float32 (rel stays a double: occl_scale = float32(1 + rel)); raises `err` otherwise."""
+    if not isinstance(calib, LidarCalib):
+        raise err(f"{name}: calib must be a geometry.LidarCalib, got {type(calib)}")
+    n = N if n is None else int(n)
+    if S < 3 or not 0 <= n <= N or n * S >= 1 << 31:
+        raise err(f"{name}: expected (N,S) points with S >= 3, 0 <= n <= N and n * S below 2^31, got N = {N}, S = {S}, n = {n}")
+    try:
+        rx, ry, rel = int(occl[0]), int(occl[1]), float(occl[2])
+        if len(occl) != 3 or rx != occl[0] or ry != occl[1]:
+            raise ValueError
+    except (TypeError, ValueError, IndexError):
+        raise err(f"{name}: occl must be (rx, ry, rel) with integer radii, got {occl!r}") from None
+    if not (0 <= rx <= LIDAR_MAX_RADIUS and 0 <= ry <= LIDAR_MAX_RADIUS):
+        raise err(f"{name}: the radii of occl must lie in [0, {LIDAR_MAX_RADIUS}], got {rx} and {ry}")
+    if not 0.0 <= rel < np.inf:
+        raise err(f"{name}: rel of occl must be finite and >= 0, got {rel}")
+    with np.errstate(over="ignore"):
+        fb, doffs = float(np.float32(calib.stereo.fb)), float(np.float32(calib.stereo.doffs))
+        min_depth, max_depth = float(np.float32(min_depth)), float(np.float32(max_depth))
+        min_disp, max_disp = float(np.float32(min_disp)), float(np.float32(max_disp))
+    if not (0.0 < fb < np.inf and np.isfinite(doffs)):
+        raise err(f"{name}: the calibration needs a positive finite f * baseline and a finite doffs in float32")
+    if not 0.0 < min_depth <= max_depth < np.inf:
+        raise err(f"{name}: 0 < min_depth <= max_depth < inf in float32, got {min_depth} and {max_depth}")
+    if not (np.isfinite(min_disp) and np.isfinite(max_disp) and min_disp <= max_disp):
+        raise err(f"{name}: min_disp <= max_disp, both finite in float32, got {min_disp} and {max_disp}")
+    outputs = tuple(outputs)
+    if not outputs or len(set(outputs)) != len(outputs) or any(o not in LIDAR_OUTPUTS for o in outputs):
+        raise err(f"{name}: outputs must be distinct names out of {LIDAR_OUTPUTS}, at least one, got {outputs!r}")
+    return n, rx, ry, rel, fb, doffs, min_depth, max_depth, min_disp, max_disp, outputs
+
+
+def lidar_disparity_host(points, calib: LidarCalib, n=None, occl=LIDAR_OCCL, min_depth=LIDAR_MIN_DEPTH,
+                         max_depth=LIDAR_MAX_DEPTH, min_disp=LIDAR_MIN_DISP, max_disp=LIDAR_MAX_DISP, outputs=("disp",)):
+    """numpy restatement of dca_lidar_disparity (include/dca_hip.h), float32 operation for float32 operation in the same
+    order, with `np.minimum.at` as the z-buffer: points (N,S) float32, S >= 3, of which the leading n rows are read -> a
+    dict with the keys of `outputs`: disp, depth float32 (H,W), disp_u16 uint16 (H,W), count int64 (2,) = (pixels written,
+    points kept).  Equal to `ops.lidar_disparity` bit for bit."""
+    points = np.asarray(points)
+    if points.dtype != np.float32 or points.ndim != 2:
+        raise ValueError(f"lidar_disparity_host: expected (N,S) float32 points, got {points.dtype} {points.shape}")
+    n, rx, ry, rel, fb, doffs, min_depth, max_depth, min_disp, max_disp, outputs = _lidar_scalars(
+        "lidar_disparity_host", ValueError, calib, points.shape[0], points.shape[1], n, occl, min_depth, max_depth, min_disp,
+        max_disp, outputs)
+    f32 = np.float32
+    H, W = calib.hw
+    m = calib.M
+    X, Y, Z = (np.ascontiguousarray(points[:n, k]) for k in range(3))
+    with np.errstate(all="ignore"):
+        x, y, z = (((m[r, 0] * X + m[r, 1] * Y) + m[r, 2] * Z) + m[r, 3] for r in range(3))
+        u, v = x / z, y / z
+        uf, vf = np.floor(u + f32(0.5)), np.floor(v + f32(0.5))
+        keep = (z >= f32(min_depth)) & (z <= f32(max_depth)) & (uf >= 0) & (uf < f32(W)) & (vf >= 0) & (vf < f32(H))
+    zbuf = np.full(H * W, np.inf, f32)
+    np.minimum.at(zbuf, vf[keep].astype(np.int64) * W + uf[keep].astype(np.int64), z[keep])
+    zbuf = zbuf.reshape(H, W)
+    pad = np.full((H + 2 * ry, W + 2 * rx), np.inf, f32)
+    pad[ry:ry + H, rx:rx + W] = zbuf
+    rowmin = pad[:, :W].copy()
+    for k in range(1, 2 * rx + 1):
+        np.minimum(rowmin, pad[:, k:k + W], out=rowmin)
+    zmin = rowmin[:H].copy()
+    for k in range(1, 2 * ry + 1):
+        np.minimum(zmin, rowmin[k:k + H], out=zmin)
+    with np.errstate(all="ignore"):
+        d = f32(fb) / zbuf - f32(doffs)
+        valid = np.isfinite(zbuf) & (zbuf <= zmin * f32(1.0 + rel)) & (d >= f32(min_disp)) & (d < f32(max_disp))
+        q = d * f32(256.0) + f32(0.5)
+    res = {}
+    for key in outputs:
+        if key == "disp":
+            res[key] = np.where(valid, d, f32(0))
+        elif key == "depth":
+            res[key] = np.where(valid, zbuf, f32(0))
+        elif key == "disp_u16":
+            code = np.where(q >= 1, np.minimum(q, f32(65535)), f32(1))       # truncated below, saturated, at least 1
+            res[key] = np.where(valid, code, f32(0)).astype(np.uint16)
+        else:
+            res[key] = np.array([int(valid.sum()), int(keep.sum())], np.int64)
+    return res
+
+
+class _LidarSlot:
+    """one scan in flight: its pinned and device copies, its outputs and the two events that order them (training._Stage)"""
+
+    def __init__(self, torch, device, capacity, S, hw, outputs):
+        self.pin = torch.empty((capacity, S), dtype=torch.float32).pin_memory()
+        self.dev = torch.empty((capacity, S), device=device, dtype=torch.float32)
+        kinds = {"disp": (hw, torch.float32), "depth": (hw, torch.float32), "disp_u16": (hw, torch.uint16),
+                 "count": ((2,), torch.int64)}
+        self.out = {k: torch.empty(kinds[k][0], device=device, dtype=kinds[k][1]) for k in outputs}
+        self.uploaded, self.computed = torch.cuda.Event(), torch.cuda.Event()
+        self.n = 0
+
+
+class LidarProjector:
+    """`proj = LidarProjector(calib, "cuda"); maps = proj(read_velodyne(path))` -- `ops.lidar_disparity` behind a staging
+    ring, as `TrainInput(device_io=True)` stages its samples: the scan is copied into a pinned buffer, uploaded on a copy
+    stream, and the three launches are enqueued on the current stream behind the upload's event.  Everything is allocated
+    here (`depth` slots of `capacity` points of `point_stride` floats, their outputs, one z-buffer): a call allocates
+    nothing and waits for nothing but the upload that last left the slot's pinned buffer, `depth` scans ago.
+    Returns the dict of `ops.lidar_disparity`; its maps are the slot's own and stay valid until `depth` more scans were
+    projected.  `stream(scans)` yields the maps scan by scan with the upload of scan i + 1 enqueued before the kernels of
+    scan i.  filters: occl, min_depth, max_depth, min_disp, max_disp and outputs of `ops.lidar_disparity`.  No queue
+    setting is changed."""
+
+    def __init__(self, calib, device="cuda", capacity=1 << 18, depth=2, point_stride=4, **filters):
+        import torch
+        unknown = set(filters) - {"occl", "min_depth", "max_depth", "min_disp", "max_disp", "outputs"}
+        if unknown:
+            raise ValueError(f"LidarProjector: unknown filters {sorted(unknown)}")
+        self.capacity, self.depth, self.S = int(capacity), int(depth), int(point_stride)
+        if self.capacity < 1 or self.depth < 1:
+            raise ValueError("LidarProjector: capacity >= 1 and depth >= 1")
+        outputs = filters.setdefault("outputs", ("disp",))
+        _lidar_scalars("LidarProjector", ValueError, calib, self.capacity, self.S, 0, filters.get("occl", LIDAR_OCCL),
+                       filters.get("min_depth", LIDAR_MIN_DEPTH), filters.get("max_depth", LIDAR_MAX_DEPTH),
+                       filters.get("min_disp", LIDAR_MIN_DISP), filters.get("max_disp", LIDAR_MAX_DISP), outputs)
+        self.calib, self.filters = calib, filters
+        self.device = torch.device(device)
+        self._ring = [_LidarSlot(torch, self.device, self.capacity, self.S, calib.hw, tuple(outputs)) for _ in range(self.depth)]
+        self._zbuf = torch.empty(calib.hw[0] * calib.hw[1], device=self.device, dtype=torch.int32)
+        self._copy = torch.cuda.Stream(self.device)
+        self._copy.wait_stream(torch.cuda.current_stream(self.device))
+        self._cur = 0
+
+    def _upload(self, points):
+        import torch
+        points = np.asarray(points)
+        if points.dtype != np.float32 or points.ndim != 2 or points.shape[1] != self.S:
+            raise ValueError(f"LidarProjector: expected (n,{self.S}) float32 points, got {points.dtype} {points.shape}")
+        n = points.shape[0]
+        if n > self.capacity:
+            raise ValueError(f"LidarProjector: a scan of {n} points exceeds the capacity of {self.capacity}")
+        s = self._ring[self._cur]
+        self._cur = (self._cur + 1) % self.depth
+        s.uploaded.synchronize()                         # the previous copy out of the pinned buffer
+        s.pin.numpy()[:n] = points
+        s.n = n
+        with torch.cuda.stream(self._copy):
+            self._copy.wait_event(s.computed)            # the previous scan of this slot has been read
+            s.dev[:n].copy_(s.pin[:n], non_blocking=True)
+            s.uploaded.record(self._copy)
+        return s
+
+    def _project(self, s):
+        import torch
+        from . import ops
+        compute = torch.cuda.current_stream(self.device)
+        compute.wait_event(s.uploaded)
+        with torch.cuda.device(self.device):
+            res = ops.lidar_disparity(s.dev, self.calib, n=s.n, out=s.out, workspace=self._zbuf, **self.filters)
+        s.computed.record(compute)
+        return res
+
+    def __call__(self, points):
+        return self._project(self._upload(points))
+
+    def stream(self, scans):
+        """yields the maps of every scan in turn; with depth >= 2 the next scan's upload is enqueued first"""
+        it = iter(scans)
+        if self.depth < 2:
+            for points in it:
+                yield self(points)
+            return
+        try:
+            cur = self._upload(next(it))
+        except StopIteration:
+            return
+        for points in it:
+            nxt = self._upload(points)
+            yield self._project(cur)
+            cur = nxt
+        yield self._project(cur)

@@ -15,6 +15,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from . import geometry as _geometry
 
 _C = _lib.CONSTANTS       # the integer #define DCA_* of include/dca_hip.h
 _vp = ctypes.c_void_p
@@ -2640,6 +2641,67 @@ def point_cloud(pred, calib, rgb=None, mask=None, window=None, v0=0, stride=1, c
                                   _ptr(count), Hc, Wc, y0, rows, cols, v0, stride, f, fb, cx, cy, doffs, min_disp, max_depth,
                                   mask_min, _stream()), "dca_point_cloud")
     return out[:cap], count, offs[:tiles + 1]
+
+
+# ------------------------------------------------------------------------------------------------
+# Sparse ground truth from a LiDAR scan (csrc/lidar.hip): the points of one scan, projected into the
+# rectified left image through a z-buffer and a hidden-point test.  No counterpart in the reference.  No launch
+# synchronises; with `out` and `workspace` passed in nothing is allocated either.
+# ------------------------------------------------------------------------------------------------
+LIDAR_MAX_RADIUS = _C["DCA_LIDAR_MAX_RADIUS"]
+_LIDAR_KINDS = {"disp": torch.float32, "depth": torch.float32, "disp_u16": torch.uint16, "count": torch.int64}
+
+
+def lidar_disparity(points, calib, n=None, occl=_geometry.LIDAR_OCCL, min_depth=_geometry.LIDAR_MIN_DEPTH,
+                    max_depth=_geometry.LIDAR_MAX_DEPTH, min_disp=_geometry.LIDAR_MIN_DISP,
+                    max_disp=_geometry.LIDAR_MAX_DISP, outputs=("disp",), out=None, workspace=None):
+    """One LiDAR scan -> sparse ground-truth maps in the rectified left image, three launches (definitions:
+    include/dca_hip.h, dca_lidar_disparity; `geometry.lidar_disparity_host` is the numpy restatement, equal bit for bit).
+    points: (N,S) float32 on the device, S >= 3 (a KITTI scan: S = 4); the leading n rows (default all) and their first three
+    columns are read.  calib: a geometry.LidarCalib.  A point is kept with min_depth <= z <= max_depth inside the image;
+    the nearest point of a pixel wins (integer atomicMin on the depth's bits: the same bits for every order of the points);
+    occl = (rx, ry, rel) drops a pixel whose z exceeds (1 + rel) times the smallest z within rx columns and ry rows,
+    (0, 0, rel) switches that off; a pixel is written where min_disp <= d < max_disp, d = fb / z - doffs.
+    Returns a dict with the keys of `outputs`:
+      disp      (H,W) float32: d, +0.0 where there is no measurement (the KITTI convention)
+      depth     (H,W) float32: z in metres, +0.0 elsewhere
+      disp_u16  (H,W) uint16: the KITTI disparity PNG payload, trunc(d * 256 + 0.5) saturated, >= 1 where written, 0 elsewhere
+      count     (2,) int64 on the device: pixels written, points kept
+    out: a dict of buffers for some or all of them; workspace: an int32 buffer of at least H * W words (the z-buffer)."""
+    name = "lidar_disparity"
+    _req_no_grad(name, points)
+    _req_dev(points, name, "points", torch.float32)
+    if points.dim() != 2:
+        raise RuntimeError(f"{name}: expected (N,S) points, got {tuple(points.shape)}")
+    N, S = int(points.shape[0]), int(points.shape[1])
+    n, rx, ry, rel, fb, doffs, min_depth, max_depth, min_disp, max_disp, outputs = _geometry._lidar_scalars(
+        name, RuntimeError, calib, N, S, n, occl, min_depth, max_depth, min_disp, max_disp, outputs)
+    H, W = calib.hw
+    dev = points.device
+    out = {} if out is None else out
+    if not isinstance(out, dict) or set(out) - set(_LIDAR_KINDS):
+        raise RuntimeError(f"{name}: out must be a dict with keys out of {tuple(_LIDAR_KINDS)}")
+    res = {}
+    for key in outputs:
+        shape = (2,) if key == "count" else (H, W)
+        if key in out:
+            res[key] = _req_dev(out[key], name, f"out[{key!r}]", _LIDAR_KINDS[key], shape)
+            if res[key].device != dev:
+                raise RuntimeError(f"{name}: out[{key!r}] must be on the points' device")
+        else:
+            res[key] = torch.empty(shape, device=dev, dtype=_LIDAR_KINDS[key])
+    if workspace is None:
+        workspace = torch.empty(H * W, device=dev, dtype=torch.int32)
+    _req_dev(workspace, name, "workspace", torch.int32)
+    if workspace.numel() < H * W or workspace.device != dev:
+        raise RuntimeError(f"{name}: workspace must hold {H * W} int32 on the points' device, got {workspace.numel()}")
+    m = [float(v) for v in calib.M.reshape(-1)]
+    with torch.cuda.device_of(points):
+        _chk(_L().dca_lidar_disparity(_ptr(points) if N else None, N, S, n, *m, H, W, fb, doffs, min_depth, max_depth, min_disp,
+                                      max_disp, rx, ry, rel, _ptr(res.get("disp")), _ptr(res.get("depth")),
+                                      _ptr(res.get("disp_u16")), _ptr(res.get("count")), _ptr(workspace), _stream()),
+             "dca_lidar_disparity")
+    return res
 
 
 # ------------------------------------------------------------------------------------------------

@@ -806,6 +806,47 @@ int dca_disp_range(const float* disp, const float* mask, float* range, void* wor
 int dca_disp_colorize(const float* disp, const float* mask, const float* range, unsigned char* out_u8, int Hc, int Wc, int y0,
                       int rows, int cols, float max_disp, float mask_min, int cmap, hipStream_t stream);
 
+/* ---- sparse ground truth from a LiDAR scan (lidar.hip); no counterpart in the reference ----------------
+ * dca_lidar_disparity: ONE scan -> sparse maps in the rectified left image.  points: (N,S) fp32 on the device, S >= 3 floats
+ * per row; only the leading n <= N rows and their first three columns (X, Y, Z in the LiDAR frame) are read (a KITTI scan
+ * has S = 4, the fourth column being the reflectance).  m00 .. m23: the 3x4 matrix of geometry.LidarCalib, LiDAR
+ * coordinates -> homogeneous pixels of the rectified left camera, formed in fp64 and rounded once by the host.  In fp32,
+ * every operation rounded on its own (no fused multiply-adds), IEEE division, per point:
+ *   x = ((m00 X + m01 Y) + m02 Z) + m03        (y and z likewise from rows 1 and 2)
+ *   u = x / z;  v = y / z;  uf = floorf(u + 0.5f);  vf = floorf(v + 0.5f)
+ *   keep = z >= min_depth && z <= max_depth && uf >= 0 && uf < float(W) && vf >= 0 && vf < float(H)
+ * All comparisons are made in float before anything is converted to int: a NaN fails them, an infinity or 1e30 fails
+ * them without overflowing an int.  Kept points go into a z-buffer, zbuf[vf W + uf] = the minimum z over the points of
+ * the pixel, cleared to the bits of +inf; the minimum is the INTEGER atomicMin on the bit pattern (positive floats order
+ * as their bits do), which does not depend on the order of arrival: the maps are the same bits on every run and for
+ * every order of the points.
+ * Hidden points, per pixel (r, c) with a finite z = zbuf[r, c]: zmin = the minimum of zbuf over rows r-ry .. r+ry and
+ * columns c-rx .. c+rx clipped to the image (the pixel itself included);  visible = z <= zmin * occl_scale  with
+ * occl_scale = float(1.0 + rel), formed in fp64 and rounded once.  rx = ry = 0 switches the test off (zmin = z).
+ *   d = fb / z - doffs;   valid = visible && d >= min_disp && d < max_disp
+ * Outputs, (H,W) each; any may be NULL, not all four:
+ *   disp      fp32: d at a valid pixel, +0.0 elsewhere (the KITTI convention: mask = gt > 0 && gt < maxdisp)
+ *   depth     fp32: z at a valid pixel, +0.0 elsewhere
+ *   disp_u16  the KITTI disparity PNG payload: q = d * 256.0f + 0.5f truncated toward zero, saturated to 65535 and at least
+ *             1 at a valid pixel; 0 elsewhere
+ *   count     2 words: count[0] = valid pixels, count[1] = points that passed keep; integer atomics, one per workgroup
+ *             (wave ballots, summed in LDS: thousands of atomics on one word serialise)
+ * zbuf: H W words of workspace, 4-byte aligned, the caller's; after the call it holds the z-buffer.
+ * THREE launches on the stream: fill zbuf and zero count; scatter the points; resolve every pixel (a workgroup stages
+ * a tile of zbuf with the halo in LDS and takes the window minimum along rows, then along columns; eight workgroups per CU
+ * walk the tiles).  Everything is
+ * passed by value; the host never waits.
+ * Refused: n > N, negative n or N, S < 3, n S >= 2^31, non-positive H or W, H W >= 2^31, rx or ry outside
+ * [0, DCA_LIDAR_MAX_RADIUS], rel < 0 or not finite, min_depth <= 0, max_depth < min_depth or not finite, min_disp or max_disp
+ * not finite, max_disp < min_disp, fb not positive and finite, doffs not finite, a matrix entry that is not finite, NULL
+ * points with n > 0, NULL zbuf, four NULL outputs. */
+#define DCA_LIDAR_MAX_RADIUS 8
+int dca_lidar_disparity(const float* points, long N, int S, long n, float m00, float m01, float m02, float m03, float m10,
+                        float m11, float m12, float m13, float m20, float m21, float m22, float m23, int H, int W, float fb,
+                        float doffs, float min_depth, float max_depth, float min_disp, float max_disp, int rx, int ry,
+                        double rel, float* disp, float* depth, unsigned short* disp_u16, long long* count, unsigned* zbuf,
+                        hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
