@@ -35,7 +35,8 @@ CASES = [  # N, Cin, Cout, (D,H,W), in_f32, out_f32, affine, slope, pre, post
     (1, 32, 32, (9, 17, 33), False, False, True, 0.0, True, False),    # odd sizes, partial tiles everywhere
     (1, 128, 64, (4, 8, 20), False, False, True, 0.0, False, False),   # 8 chunks: streaming-weights mode
     (1, 80, 32, (5, 9, 17), True, False, False, 1.0, False, True),     # streaming mode, unaligned
-    (2, 32, 32, (8, 16, 32), False, False, True, 0.0, True, True),     # several tiles per workgroup range, both residuals
+    # 16 tiles, one per workgroup on 256 CUs (two or more per workgroup: tests/test_gpu_conv_tiles_fp64.py); both residuals
+    (2, 32, 32, (8, 16, 32), False, False, True, 0.0, True, True),
 ]
 
 
@@ -111,7 +112,9 @@ DC_CASES = [  # N, Cin, Cout, coarse dims, affine, slope, pre, post
     (1, 64, 32, (2, 8, 16), True, 0.0, True, False),       # exactly one tile, cost_agg.conv3 form
     (2, 64, 32, (3, 5, 12), True, 0.0, True, True),        # partial tiles, both residuals (cva1: + cost0)
     (1, 16, 27, (2, 3, 5), False, 1.0, False, False),      # unaligned W, partial channel block, one chunk
-    (1, 48, 32, (5, 17, 36), True, 0.1, False, True),      # several tiles per workgroup range, 3 chunks
+    # 27 tiles on 27 workgroups (256 CUs): one each but for two that get two and two that get none, as the eight XCD chunks
+    # fall; the many-tile regime proper is gated in tests/test_gpu_conv_tiles_fp64.py.  3 chunks
+    (1, 48, 32, (5, 17, 36), True, 0.1, False, True),
 ]
 
 
@@ -151,7 +154,9 @@ S2_CASES = [  # N, Cin, Cout, fine dims, affine, slope
     (1, 32, 64, (4, 16, 32), True, 0.0),       # exactly one tile, cost_agg.conv1 form
     (2, 32, 64, (6, 10, 24), True, 0.0),       # partial tiles
     (1, 40, 27, (5, 9, 20), False, 1.0),       # odd D / H (ceil), partial channel blocks, 5 chunks
-    (1, 8, 64, (10, 36, 72), True, 0.1),       # several tiles per workgroup range, one chunk
+    # 27 tiles on 27 workgroups (256 CUs): one each but for two that get two and two that get none, as the eight XCD chunks
+    # fall; the many-tile regime proper is gated in tests/test_gpu_conv_tiles_fp64.py.  One chunk
+    (1, 8, 64, (10, 36, 72), True, 0.1),
 ]
 
 

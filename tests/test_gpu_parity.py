@@ -3,7 +3,8 @@ inputs, then whole modules against the golden vectors generated from the referen
 its unfused op here; the fused launches of the shipped path (alias / pair / fork nodes with `res_post` or `res`, the fused
 volume builder) have their own fp64 gates in tests/test_gpu_fused_nodes.py.  The weight-gradient kernels run here with at most
 two tiles per workgroup; their many-tile regime (tile loop, cross-tile prefetch, slab reduction) is gated in
-tests/test_gpu_wgrad_fp64.py.
+tests/test_gpu_wgrad_fp64.py.  The forward / backward-data convolution kernels get one tile per workgroup here (two at a few
+20- and 27-tile shapes); two, three and more tiles per workgroup are gated in tests/test_gpu_conv_tiles_fp64.py.
 
 Tolerances (fp32 path, north_star: 1e-3 abs on the disparity): kernel-level max-abs <= 2e-5 * scale for
 forward results (fp32 MFMA is an exact fma chain; only summation order differs), relative-L2 <= 1e-4
