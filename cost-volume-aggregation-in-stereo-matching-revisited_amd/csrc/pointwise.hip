@@ -251,8 +251,8 @@ __global__ __launch_bounds__(256) void bn_apply_pack_kernel(const float* __restr
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         v[j] = yb[j * S + i];
-        rp[j] = res_pre ? res_pre[cb + j * S + i] : 0.f;
-        rq[j] = res_post ? res_post[cb + j * S + i] : 0.f;
+        rp[j] = res_pre ? res_pre[cb + j * S + i] : -0.f;     // -0: x + -0 = x for every x, so without residuals the fp32
+        rq[j] = res_post ? res_post[cb + j * S + i] : -0.f;   // copy has bn_apply_kernel's bits (ReLU of v < 0 is -0 there)
       }
       u16x8 hv, lv;
 #pragma unroll
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(256) void bn_apply_pack4_kernel(const float* __rest
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float4 v4 = *(const float4*)(y + cb + j * S + i);
-        float4 p4 = make_float4(0.f, 0.f, 0.f, 0.f), q4 = p4;
+        float4 p4 = make_float4(-0.f, -0.f, -0.f, -0.f), q4 = p4;   // -0: see bn_apply_pack_kernel
         if (res_pre) p4 = *(const float4*)(res_pre + cb + j * S + i);
         if (res_post) q4 = *(const float4*)(res_post + cb + j * S + i);
         const float v[4] = {v4.x, v4.y, v4.z, v4.w}, rp[4] = {p4.x, p4.y, p4.z, p4.w}, rq[4] = {q4.x, q4.y, q4.z, q4.w};

@@ -4,7 +4,9 @@ its unfused op here; the fused launches of the shipped path (alias / pair / fork
 volume builder) have their own fp64 gates in tests/test_gpu_fused_nodes.py.  The weight-gradient kernels run here with at most
 two tiles per workgroup; their many-tile regime (tile loop, cross-tile prefetch, slab reduction) is gated in
 tests/test_gpu_wgrad_fp64.py.  The forward / backward-data convolution kernels get one tile per workgroup here (two at a few
-20- and 27-tile shapes); two, three and more tiles per workgroup are gated in tests/test_gpu_conv_tiles_fp64.py.
+20- and 27-tile shapes); two, three and more tiles per workgroup are gated in tests/test_gpu_conv_tiles_fp64.py.  The
+BatchNorm kernels get one chunk of a channel's voxels per launch here (two in the packed training chains); chunk boundaries,
+the finalize loops past 64 partials and the slot counts of the two chunkings are gated in tests/test_gpu_bn_chunks_fp64.py.
 
 Tolerances (fp32 path, north_star: 1e-3 abs on the disparity): kernel-level max-abs <= 2e-5 * scale for
 forward results (fp32 MFMA is an exact fma chain; only summation order differs), relative-L2 <= 1e-4
