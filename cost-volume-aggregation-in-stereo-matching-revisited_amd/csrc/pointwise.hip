@@ -165,6 +165,21 @@ __global__ __launch_bounds__(64) void bn_finalize_centered_kernel(const double* 
 // the way: block (chunk ch, channel c) stores its maximum into slot [c][ch] (nchunk <= DCA_AMAX_CSLOTS), or they write the
 // operand in the packed px2 format directly (the *_pack kernels), scaled by exponents the finalize kernels derive from bounds.
 
+// scale*y + shift of every apply and backward kernel below: ONE rounding, written as an explicit fma so that no two kernels (and
+// no two forms of one kernel) can contract it differently.
+__device__ __forceinline__ float bn_affine(float y, float sc, float sh) { return __fmaf_rn(y, sc, sh); }
+// What bn_apply_kernel writes for a slope-1 BatchNorm without residuals: the value of the folded skip branch, which the
+// *_pack and backward kernels form in registers from (y_r, stats_r) instead of reading it as res_pre -- same bits, so the
+// output and the ReLU mask of the backward pass are those of the route that stores it.
+__device__ __forceinline__ float bn_skip(float y, float sc, float sh) { return act_apply(bn_affine(y, sc, sh), 1.f); }
+// One element's terms of the backward sums (sum g, sum g*xhat).  Not contracted: every reduction over the same (g, y, stats)
+// -- bn_bwd_reduce_kernel's own pair and the second pair it forms for a folded skip BatchNorm -- rounds alike.
+__device__ __forceinline__ void bn_bwd_acc(float g, float y, float mean, float invstd, float& a0, float& a1) {
+#pragma clang fp contract(off)
+  a0 += g;
+  a1 += g * (y - mean) * invstd;
+}
+
 // z = act(scale[c]*y + shift[c] + res_pre) + res_post.  Block (ch, c): chunk ch of channel c, all samples.
 // zmax / ymax (may be null): per-channel slots that receive max |z| and max |y - mean| (the latter bounds |xhat| for the
 // gradient's scale in the backward pass).
@@ -183,7 +198,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
       for (long i = s0 + 4 * tid; i < s1; i += 1024) {
         float4 v = *(const float4*)(y + base + i);
         ym = fmaxf(fmaxf(ym, fmaxf(fabsf(v.x - mean), fabsf(v.y - mean))), fmaxf(fabsf(v.z - mean), fabsf(v.w - mean)));
-        v.x = v.x * sc + sh; v.y = v.y * sc + sh; v.z = v.z * sc + sh; v.w = v.w * sc + sh;
+        v.x = bn_affine(v.x, sc, sh); v.y = bn_affine(v.y, sc, sh); v.z = bn_affine(v.z, sc, sh); v.w = bn_affine(v.w, sc, sh);
         if (res_pre) { const float4 r = *(const float4*)(res_pre + base + i); v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
         v.x = act_apply(v.x, slope); v.y = act_apply(v.y, slope); v.z = act_apply(v.z, slope); v.w = act_apply(v.w, slope);
         if (res_post) { const float4 r = *(const float4*)(res_post + base + i); v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
@@ -194,7 +209,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
       for (long i = s0 + tid; i < s1; i += 256) {
         const float yv = y[base + i];
         ym = fmaxf(ym, fabsf(yv - mean));
-        float v = yv * sc + sh;
+        float v = bn_affine(yv, sc, sh);
         if (res_pre) v += res_pre[base + i];
         v = act_apply(v, slope);
         if (res_post) v += res_post[base + i];
@@ -221,16 +236,20 @@ typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 // its 8 channels (eight 4-byte loads, each 256 contiguous bytes per wave; two 16-byte stores, 1 KB contiguous per wave).
 // stats == null: identity (plain packing of an fp32 tensor, dca_pack_x2).
 // res_pre / res_post / zf (may be null): the residual adds of bn_apply_kernel and a second, fp32, copy of z for readers
-// other than the f16x2 convolution.
+// other than the f16x2 convolution.  y_r / stats_r (may be null; then no res_pre): the pre-activation residual is the slope-1
+// BatchNorm bn_skip(y_r) with the statistics stats_r, formed here instead of being read (SKIP: an instantiation of its own, so
+// the plain form keeps its registers -- three waves per SIMD instead of two).
+template <bool SKIP>
 __global__ __launch_bounds__(256) void bn_apply_pack_kernel(const float* __restrict__ y, const float* __restrict__ stats,
                                                             const int* __restrict__ zexps, char* __restrict__ zp, int N,
                                                             int C, long S, long chunk_len, float slope,
                                                             unsigned* __restrict__ ymax, const float* __restrict__ res_pre,
                                                             const float* __restrict__ res_post, float* __restrict__ zf,
-                                                            unsigned* __restrict__ zmax) {
+                                                            unsigned* __restrict__ zmax, const float* __restrict__ y_r,
+                                                            const float* __restrict__ stats_r) {
   const int cg = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x;
   const long s0 = ch * chunk_len, s1 = min(S, s0 + chunk_len);
-  float mean[8], sc[8], sh[8], ym[8], zm[8];
+  float mean[8], sc[8], sh[8], scr[8], shr[8], ym[8], zm[8];
   int ex[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -238,6 +257,8 @@ __global__ __launch_bounds__(256) void bn_apply_pack_kernel(const float* __restr
     mean[j] = stats ? stats[c] : 0.f;
     sc[j] = stats ? stats[2 * C + c] : 1.f;
     sh[j] = stats ? stats[3 * C + c] : 0.f;
+    scr[j] = SKIP ? stats_r[2 * C + c] : 0.f;
+    shr[j] = SKIP ? stats_r[3 * C + c] : 0.f;
     ex[j] = dca_coherent_loadi(zexps + c);
     ym[j] = zm[j] = 0.f;
   }
@@ -251,14 +272,15 @@ __global__ __launch_bounds__(256) void bn_apply_pack_kernel(const float* __restr
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         v[j] = yb[j * S + i];
-        rp[j] = res_pre ? res_pre[cb + j * S + i] : -0.f;     // -0: x + -0 = x for every x, so without residuals the fp32
+        rp[j] = (!SKIP && res_pre) ? res_pre[cb + j * S + i] : -0.f;     // -0: x + -0 = x for every x, so without residuals the fp32
         rq[j] = res_post ? res_post[cb + j * S + i] : -0.f;   // copy has bn_apply_kernel's bits (ReLU of v < 0 is -0 there)
+        if (SKIP) rp[j] = bn_skip(y_r[cb + j * S + i], scr[j], shr[j]);
       }
       u16x8 hv, lv;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         ym[j] = fmaxf(ym[j], fabsf(v[j] - mean[j]));
-        const float zz = act_apply(v[j] * sc[j] + sh[j] + rp[j], slope) + rq[j];
+        const float zz = act_apply(bn_affine(v[j], sc[j], sh[j]) + rp[j], slope) + rq[j];
         if (zf) zf[cb + j * S + i] = zz;
         zm[j] = fmaxf(zm[j], fabsf(zz));
         unsigned short h, l;
@@ -282,15 +304,17 @@ __global__ __launch_bounds__(256) void bn_apply_pack_kernel(const float* __restr
 // The same with FOUR voxels per lane (S % 4 == 0, 16-byte aligned tensors): 16-byte loads per channel, the fp32 copy as
 // 16-byte stores, the packed words of the four voxels as 64 contiguous bytes per term; used when residuals are read too
 // (dca_bn_apply_pack).
+template <bool SKIP>
 __global__ __launch_bounds__(256) void bn_apply_pack4_kernel(const float* __restrict__ y, const float* __restrict__ stats,
                                                              const int* __restrict__ zexps, char* __restrict__ zp, int N,
                                                              int C, long S, long chunk_len, float slope,
                                                              unsigned* __restrict__ ymax, const float* __restrict__ res_pre,
                                                              const float* __restrict__ res_post, float* __restrict__ zf,
-                                                             unsigned* __restrict__ zmax) {
+                                                             unsigned* __restrict__ zmax, const float* __restrict__ y_r,
+                                                             const float* __restrict__ stats_r) {
   const int cg = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x;
   const long s0 = ch * chunk_len, s1 = min(S, s0 + chunk_len);
-  float mean[8], sc[8], sh[8], ym[8], zm[8];
+  float mean[8], sc[8], sh[8], scr[8], shr[8], ym[8], zm[8];
   int ex[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -298,6 +322,8 @@ __global__ __launch_bounds__(256) void bn_apply_pack4_kernel(const float* __rest
     mean[j] = stats ? stats[c] : 0.f;
     sc[j] = stats ? stats[2 * C + c] : 1.f;
     sh[j] = stats ? stats[3 * C + c] : 0.f;
+    scr[j] = SKIP ? stats_r[2 * C + c] : 0.f;
+    shr[j] = SKIP ? stats_r[3 * C + c] : 0.f;
     ex[j] = dca_coherent_loadi(zexps + c);
     ym[j] = zm[j] = 0.f;
   }
@@ -311,14 +337,19 @@ __global__ __launch_bounds__(256) void bn_apply_pack4_kernel(const float* __rest
       for (int j = 0; j < 8; ++j) {
         const float4 v4 = *(const float4*)(y + cb + j * S + i);
         float4 p4 = make_float4(-0.f, -0.f, -0.f, -0.f), q4 = p4;   // -0: see bn_apply_pack_kernel
-        if (res_pre) p4 = *(const float4*)(res_pre + cb + j * S + i);
+        if (!SKIP && res_pre) p4 = *(const float4*)(res_pre + cb + j * S + i);
         if (res_post) q4 = *(const float4*)(res_post + cb + j * S + i);
+        if (SKIP) {
+          const float4 r4 = *(const float4*)(y_r + cb + j * S + i);
+          p4 = make_float4(bn_skip(r4.x, scr[j], shr[j]), bn_skip(r4.y, scr[j], shr[j]), bn_skip(r4.z, scr[j], shr[j]),
+                           bn_skip(r4.w, scr[j], shr[j]));
+        }
         const float v[4] = {v4.x, v4.y, v4.z, v4.w}, rp[4] = {p4.x, p4.y, p4.z, p4.w}, rq[4] = {q4.x, q4.y, q4.z, q4.w};
         float zz[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           ym[j] = fmaxf(ym[j], fabsf(v[e] - mean[j]));
-          zz[e] = act_apply(v[e] * sc[j] + sh[j] + rp[e], slope) + rq[e];
+          zz[e] = act_apply(bn_affine(v[e], sc[j], sh[j]) + rp[e], slope) + rq[e];
           zm[j] = fmaxf(zm[j], fabsf(zz[e]));
           unsigned short h, l;
           px2_split(zz[e], ex[j], h, l);
@@ -363,6 +394,31 @@ __global__ __launch_bounds__(256) void cmax_kernel(const float* __restrict__ x, 
   dca_cmax_put(m, slots + (long)c * DCA_AMAX_CSLOTS + ch);
 }
 
+// per-channel max |bn_skip(y_r)| into slots [c][ch]: the maxima bn_apply_kernel emits (zmax) when it WRITES that slope-1
+// BatchNorm, for the folded form that never writes it -- a read pass, no store.  The exponents of the packed output are
+// derived from these maxima (bn_bound_exp), so the folded route packs with the very exponents of the route that stores skip.
+__global__ __launch_bounds__(256) void bn_skip_max_kernel(const float* __restrict__ y_r, const float* __restrict__ stats_r,
+                                                          int N, int C, long S, long chunk_len, int vec,
+                                                          unsigned* __restrict__ slots) {
+  const int c = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x;
+  const long s0 = ch * chunk_len, s1 = min(S, s0 + chunk_len);
+  const float sc = stats_r[2 * C + c], sh = stats_r[3 * C + c];
+  float m = 0.f;
+  for (int n = N - 1; n >= 0; --n) {   // descending: the convolution that produced y_r wrote the last sample last
+    const float* p = y_r + ((long)n * C + c) * S;
+    if (vec) {
+      for (long i = s0 + 4 * tid; i < s1; i += 1024) {
+        const float4 v = *(const float4*)(p + i);
+        m = fmaxf(fmaxf(m, fmaxf(fabsf(bn_skip(v.x, sc, sh)), fabsf(bn_skip(v.y, sc, sh)))),
+                  fmaxf(fabsf(bn_skip(v.z, sc, sh)), fabsf(bn_skip(v.w, sc, sh))));
+      }
+    } else {
+      for (long i = s0 + tid; i < s1; i += 256) m = fmaxf(m, fabsf(bn_skip(p[i], sc, sh)));
+    }
+  }
+  dca_cmax_put(m, slots + (long)c * DCA_AMAX_CSLOTS + ch);
+}
+
 // exps[c] = exponent that brings max over the channel's nslots slot maxima into [2^14, 2^15); one wave per channel
 __global__ __launch_bounds__(64) void cmax_exps_kernel(const unsigned* __restrict__ slots, int nslots, int* __restrict__ exps) {
   const int c = blockIdx.x, lane = threadIdx.x;
@@ -376,16 +432,23 @@ __global__ __launch_bounds__(64) void cmax_exps_kernel(const unsigned* __restric
 // ------------------------------------------------------------------------------------ BN backward
 // u = scale*y + shift (+res_pre); g = dz * (u > 0 ? 1 : slope); xhat = (y - mean)*invstd
 // part = per-(channel, chunk) double sums of (g, g*xhat); gmax (may be null): per-channel slots [c][ch] with max |g|.
+// y_r / stats_r (may be null; then no res_pre): res_pre = bn_skip(y_r), formed here.  part_r (with y_r; may be null): the same
+// pair of sums for THAT BatchNorm, whose dz is g: (sum g, sum g*xhat_r), element for element and in the order of a launch of
+// this kernel over (g, y_r, stats_r) with slope 1 -- the launch it replaces -- so its dgamma / dbeta are that launch's bits.
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ dz, const float* __restrict__ y,
                                                             const float* __restrict__ res_pre,
                                                             const float* __restrict__ stats,
                                                             double* __restrict__ part, int N, int C, long S,
                                                             int nchunk, long chunk_len, float slope, int vec,
-                                                            unsigned* __restrict__ gmax) {
+                                                            unsigned* __restrict__ gmax, const float* __restrict__ y_r,
+                                                            const float* __restrict__ stats_r, double* __restrict__ part_r) {
   const int c = blockIdx.x, ch = blockIdx.y, tid = threadIdx.x;
   const long s0 = ch * chunk_len, s1 = min(S, s0 + chunk_len);
   const float mean = stats[c], invstd = stats[C + c], sc = stats[2 * C + c], sh = stats[3 * C + c];
-  float a0 = 0.f, a1 = 0.f, gm = 0.f;
+  const float mean_r = y_r ? stats_r[c] : 0.f, invstd_r = y_r ? stats_r[C + c] : 0.f;
+  const float sc_r = y_r ? stats_r[2 * C + c] : 0.f, sh_r = y_r ? stats_r[3 * C + c] : 0.f;
+  const float* rsrc = y_r ? y_r : res_pre;     // ONE residual stream either way: a single load, issued beside those of y and dz
+  float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f, gm = 0.f;
   for (int n = N - 1; n >= 0; --n) {   // the producer of dz wrote the last sample last: its tail is still in the infinity cache
     const long base = ((long)n * C + c) * S;
     if (vec) {
@@ -393,36 +456,50 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
         const float4 yv = *(const float4*)(y + base + i);
         const float4 dv = *(const float4*)(dz + base + i);
         float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (res_pre) rv = *(const float4*)(res_pre + base + i);
+        if (rsrc) rv = *(const float4*)(rsrc + base + i);
+        const float4 rr = rv;
+        if (y_r) rv = make_float4(bn_skip(rr.x, sc_r, sh_r), bn_skip(rr.y, sc_r, sh_r), bn_skip(rr.z, sc_r, sh_r), bn_skip(rr.w, sc_r, sh_r));
         const float ys[4] = {yv.x, yv.y, yv.z, yv.w}, ds[4] = {dv.x, dv.y, dv.z, dv.w}, rs[4] = {rv.x, rv.y, rv.z, rv.w};
+        const float yr[4] = {rr.x, rr.y, rr.z, rr.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float u = ys[j] * sc + sh + rs[j];
+          const float u = bn_affine(ys[j], sc, sh) + rs[j];
           const float g = ds[j] * (u > 0.f ? 1.f : slope);
-          a0 += g;
-          a1 += g * (ys[j] - mean) * invstd;
+          bn_bwd_acc(g, ys[j], mean, invstd, a0, a1);
+          if (part_r) bn_bwd_acc(g, yr[j], mean_r, invstd_r, b0, b1);
           gm = fmaxf(gm, fabsf(g));
         }
       }
     } else {
       for (long i = s0 + tid; i < s1; i += 256) {
         const float yv = y[base + i];
-        float u = yv * sc + sh;
-        if (res_pre) u += res_pre[base + i];
+        float u = bn_affine(yv, sc, sh), yrv = 0.f;
+        if (rsrc) {
+          yrv = rsrc[base + i];
+          u += y_r ? bn_skip(yrv, sc_r, sh_r) : yrv;
+        }
         const float g = dz[base + i] * (u > 0.f ? 1.f : slope);
-        a0 += g;
-        a1 += g * (yv - mean) * invstd;
+        bn_bwd_acc(g, yv, mean, invstd, a0, a1);
+        if (part_r) bn_bwd_acc(g, yrv, mean_r, invstd_r, b0, b1);
         gm = fmaxf(gm, fabsf(g));
       }
     }
   }
   double d0 = wave_sum_d((double)a0), d1 = wave_sum_d((double)a1);
-  __shared__ double red[8];
+  __shared__ double red[16];
   if ((tid & 63) == 0) { red[(tid >> 6) * 2] = d0; red[(tid >> 6) * 2 + 1] = d1; }
+  if (part_r) {
+    d0 = wave_sum_d((double)b0), d1 = wave_sum_d((double)b1);
+    if ((tid & 63) == 0) { red[8 + (tid >> 6) * 2] = d0; red[8 + (tid >> 6) * 2 + 1] = d1; }
+  }
   __syncthreads();
   if (tid == 0) {
     part[((long)c * nchunk + ch) * 2 + 0] = red[0] + red[2] + red[4] + red[6];
     part[((long)c * nchunk + ch) * 2 + 1] = red[1] + red[3] + red[5] + red[7];
+    if (part_r) {
+      part_r[((long)c * nchunk + ch) * 2 + 0] = red[8] + red[10] + red[12] + red[14];
+      part_r[((long)c * nchunk + ch) * 2 + 1] = red[9] + red[11] + red[13] + red[15];
+    }
   }
   if (gmax) dca_cmax_put(gm, gmax + (long)c * DCA_AMAX_CSLOTS + ch);
 }
@@ -471,14 +548,18 @@ __global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(const double* __res
 
 // dy = scale * (g - [training](dbeta/count + xhat*dgamma/count)); optionally g_out = g (grad of res_pre).
 // Block (ch, c) as bn_apply_kernel; dmax (may be null): per-channel slots receiving max |dy|.
+// y_r / stats_r (may be null; then no res_pre): res_pre = bn_skip(y_r), as in bn_bwd_reduce_kernel.
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dz, const float* __restrict__ y,
                                     const float* __restrict__ res_pre, const float* __restrict__ stats,
                                     const float* __restrict__ dgb, float* __restrict__ dy, float* __restrict__ g_out,
                                     int N, int C, long S, long chunk_len, float slope, int training, int vec,
-                                    unsigned* __restrict__ dmax) {
+                                    unsigned* __restrict__ dmax, const float* __restrict__ y_r,
+                                    const float* __restrict__ stats_r) {
   const int c = blockIdx.y, ch = blockIdx.x, tid = threadIdx.x;
   const long s0 = ch * chunk_len, s1 = min(S, s0 + chunk_len);
   const float mean = stats[c], invstd = stats[C + c], sc = stats[2 * C + c], sh = stats[3 * C + c];
+  const float sc_r = y_r ? stats_r[2 * C + c] : 0.f, sh_r = y_r ? stats_r[3 * C + c] : 0.f;
+  const float* rsrc = y_r ? y_r : res_pre;     // as in bn_bwd_reduce_kernel
   const float k1 = training ? dgb[2 * C + c] : 0.f, k2 = training ? dgb[3 * C + c] * invstd : 0.f;
   float am = 0.f;
   for (int n = 0; n < N; ++n) {
@@ -487,12 +568,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
       for (long i = s0 + 4 * tid; i < s1; i += 1024) {
         const float4 yv = *(const float4*)(y + base + i), dv = *(const float4*)(dz + base + i);
         float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (res_pre) rv = *(const float4*)(res_pre + base + i);
+        if (rsrc) rv = *(const float4*)(rsrc + base + i);
+        if (y_r) rv = make_float4(bn_skip(rv.x, sc_r, sh_r), bn_skip(rv.y, sc_r, sh_r), bn_skip(rv.z, sc_r, sh_r), bn_skip(rv.w, sc_r, sh_r));
         const float ys[4] = {yv.x, yv.y, yv.z, yv.w}, ds[4] = {dv.x, dv.y, dv.z, dv.w}, rs[4] = {rv.x, rv.y, rv.z, rv.w};
         float o[4], g[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float u = ys[j] * sc + sh + rs[j];
+          const float u = bn_affine(ys[j], sc, sh) + rs[j];
           g[j] = ds[j] * (u > 0.f ? 1.f : slope);
           o[j] = (g[j] - k1 - (ys[j] - mean) * k2) * sc;
         }
@@ -503,8 +585,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     } else {
       for (long i = s0 + tid; i < s1; i += 256) {
         const float yv = y[base + i];
-        float u = yv * sc + sh;
-        if (res_pre) u += res_pre[base + i];
+        float u = bn_affine(yv, sc, sh);
+        if (rsrc) {
+          const float r = rsrc[base + i];
+          u += y_r ? bn_skip(r, sc_r, sh_r) : r;
+        }
         const float g = dz[base + i] * (u > 0.f ? 1.f : slope);
         float v = g;
         if (training) v -= dgb[2 * C + c] + (yv - mean) * invstd * dgb[3 * C + c];
@@ -1043,22 +1128,39 @@ extern "C" int dca_bn_apply(const float* y, const float* stats, const float* res
   return dca_launch_status();
 }
 
-extern "C" int dca_bn_apply_pack(const float* y, const float* stats, const int* zexps, void* zp, int N, int C, long S,
-                                 float slope, unsigned* ymax, const float* res_pre, const float* res_post, float* zf,
-                                 unsigned* zmax, hipStream_t stream) {
+static int bn_apply_pack_launch(const float* y, const float* stats, const int* zexps, void* zp, int N, int C, long S,
+                                float slope, unsigned* ymax, const float* res_pre, const float* y_r, const float* stats_r,
+                                const float* res_post, float* zf, unsigned* zmax, hipStream_t stream) {
   DCA_REQUIRE(y && zexps && zp && N > 0 && C > 0 && C % 8 == 0 && S > 0 && C / 8 <= 65535 && ((((uintptr_t)zp) & 15) == 0));
   DCA_REQUIRE(stats != nullptr || (ymax == nullptr && slope == 1.f));
+  DCA_REQUIRE((y_r == nullptr) == (stats_r == nullptr) && (y_r == nullptr || (res_pre == nullptr && stats != nullptr)));
   int nchunk; long len;
   chunking(S, C / 8, &nchunk, &len);
-  const uintptr_t al = (uintptr_t)y | (uintptr_t)res_pre | (uintptr_t)res_post | (uintptr_t)zf;
+  const uintptr_t al = (uintptr_t)y | (uintptr_t)res_pre | (uintptr_t)y_r | (uintptr_t)res_post | (uintptr_t)zf;
   // four voxels per lane pay when residual streams are read beside y (batch-4 layer shape, tools/bn_time.py: 631 vs 726 us with
   // fp32 copy + one residual); without them the one-voxel form is faster (332 vs 449 us packed only, 563 vs 584 with the copy:
   // its packed stores are contiguous per instruction, the four-voxel form's are 16 of every 64 bytes)
-  const bool four = (res_pre || res_post) && S % 4 == 0 && (al & 15) == 0;       // chunks are multiples of 1024
-  auto kern = four ? bn_apply_pack4_kernel : bn_apply_pack_kernel;
+  const bool four = (res_pre || y_r || res_post) && S % 4 == 0 && (al & 15) == 0;       // chunks are multiples of 1024
+  auto kern = y_r ? (four ? bn_apply_pack4_kernel<true> : bn_apply_pack_kernel<true>)
+                  : (four ? bn_apply_pack4_kernel<false> : bn_apply_pack_kernel<false>);
   hipLaunchKernelGGL(kern, dim3(nchunk, C / 8), dim3(256), 0, stream, y, stats, zexps, (char*)zp, N, C, S, len, slope, ymax,
-                     res_pre, res_post, zf, zmax);
+                     res_pre, res_post, zf, zmax, y_r, stats_r);
   return dca_launch_status();
+}
+
+extern "C" int dca_bn_apply_pack(const float* y, const float* stats, const int* zexps, void* zp, int N, int C, long S,
+                                 float slope, unsigned* ymax, const float* res_pre, const float* res_post, float* zf,
+                                 unsigned* zmax, hipStream_t stream) {
+  return bn_apply_pack_launch(y, stats, zexps, zp, N, C, S, slope, ymax, res_pre, nullptr, nullptr, res_post, zf, zmax, stream);
+}
+
+// dca_bn_apply_pack with the pre-activation residual given as the folded skip BatchNorm: res_pre = bn_skip(y_r) with the
+// statistics stats_r, formed in registers (the kernel it would be read from, dca_bn_apply at slope 1, is not launched)
+extern "C" int dca_bn_apply_pack_skip(const float* y, const float* stats, const int* zexps, void* zp, int N, int C, long S,
+                                      float slope, unsigned* ymax, const float* y_r, const float* stats_r,
+                                      const float* res_post, float* zf, unsigned* zmax, hipStream_t stream) {
+  DCA_REQUIRE(y_r && stats_r);
+  return bn_apply_pack_launch(y, stats, zexps, zp, N, C, S, slope, ymax, nullptr, y_r, stats_r, res_post, zf, zmax, stream);
 }
 
 extern "C" int dca_cmax_f32(const float* x, int N, int C, long S, unsigned* slots, hipStream_t stream) {
@@ -1067,6 +1169,16 @@ extern "C" int dca_cmax_f32(const float* x, int N, int C, long S, unsigned* slot
   chunking(S, C, &nchunk, &len);
   const int vec = (S % 4 == 0) && ((((uintptr_t)x) & 15) == 0);
   hipLaunchKernelGGL(cmax_kernel, dim3(nchunk, C), dim3(256), 0, stream, x, N, C, S, len, vec, slots);
+  return dca_launch_status();
+}
+
+extern "C" int dca_bn_skip_max(const float* y_r, const float* stats_r, int N, int C, long S, unsigned* slots,
+                               hipStream_t stream) {
+  DCA_REQUIRE(y_r && stats_r && slots && N > 0 && C > 0 && S > 0 && C <= 65535);
+  int nchunk; long len;
+  chunking(S, C, &nchunk, &len);
+  const int vec = (S % 4 == 0) && ((((uintptr_t)y_r) & 15) == 0);
+  hipLaunchKernelGGL(bn_skip_max_kernel, dim3(nchunk, C), dim3(256), 0, stream, y_r, stats_r, N, C, S, len, vec, slots);
   return dca_launch_status();
 }
 
@@ -1085,11 +1197,38 @@ extern "C" int dca_bn_backward(const float* dz, const float* y, const float* res
   const uintptr_t al = (uintptr_t)dz | (uintptr_t)y | (uintptr_t)res_pre | (uintptr_t)dy | (uintptr_t)g_out;
   const int vec = (S % 4 == 0) && ((al & 15) == 0);
   hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, nchunk), dim3(256), 0, stream, dz, y, res_pre, stats, part, N, C, S,
-                     nchunk, len, slope, vec, (unsigned*)nullptr);
+                     nchunk, len, slope, vec, (unsigned*)nullptr, (const float*)nullptr, (const float*)nullptr,
+                     (double*)nullptr);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, stream, part, nchunk, (double)N * (double)S, dgb, C,
                      stats, training, (const unsigned*)nullptr, (const unsigned*)nullptr, 0, (int*)nullptr);
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nchunk, C), dim3(256), 0, stream, dz, y, res_pre, stats, dgb, dy, g_out, N, C,
-                     S, len, slope, training, vec, dmax);
+                     S, len, slope, training, vec, dmax, (const float*)nullptr, (const float*)nullptr);
+  return dca_launch_status();
+}
+
+// dca_bn_backward of a BatchNorm whose res_pre is the folded skip BatchNorm bn_skip(y_r) (statistics stats_r; never stored):
+// the reduce pass also forms the skip BatchNorm's own sums -- its dz is g -- into part_r, one more finalize launch gives
+// dgb_r, and g_out (required: the skip's producer reads it as its dz) is written beside dy.  dgb_r = what
+// dca_bn_backward_reduce(g_out, y_r, stats_r, ..., slope 1) gives, bit for bit, without that pass over g_out and y_r.
+extern "C" int dca_bn_backward_skip(const float* dz, const float* y, const float* y_r, const float* stats,
+                                    const float* stats_r, double* part, double* part_r, float* dgb, float* dgb_r, float* dy,
+                                    float* g_out, int N, int C, long S, float slope, int training, unsigned* dmax,
+                                    hipStream_t stream) {
+  DCA_REQUIRE(dz && y && stats && part && dgb && dy && N > 0 && C > 0 && S > 0 && C <= 65535);
+  DCA_REQUIRE(y_r && stats_r && part_r && dgb_r && g_out && part_r != part && dgb_r != dgb);
+  int nchunk; long len;
+  chunking(S, C, &nchunk, &len);
+  const uintptr_t al = (uintptr_t)dz | (uintptr_t)y | (uintptr_t)y_r | (uintptr_t)dy | (uintptr_t)g_out;
+  const int vec = (S % 4 == 0) && ((al & 15) == 0);
+  const double count = (double)N * (double)S;
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, nchunk), dim3(256), 0, stream, dz, y, (const float*)nullptr, stats, part,
+                     N, C, S, nchunk, len, slope, vec, (unsigned*)nullptr, y_r, stats_r, part_r);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, stream, part, nchunk, count, dgb, C, stats, training,
+                     (const unsigned*)nullptr, (const unsigned*)nullptr, 0, (int*)nullptr);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, stream, (const double*)part_r, nchunk, count, dgb_r, C,
+                     stats_r, training, (const unsigned*)nullptr, (const unsigned*)nullptr, 0, (int*)nullptr);
+  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(nchunk, C), dim3(256), 0, stream, dz, y, (const float*)nullptr, stats, dgb, dy,
+                     g_out, N, C, S, len, slope, training, vec, dmax, y_r, stats_r);
   return dca_launch_status();
 }
 
@@ -1102,7 +1241,8 @@ extern "C" int dca_bn_backward_reduce(const float* dz, const float* y, const flo
   chunking(S, C, &nchunk, &len);
   const int vec = (S % 4 == 0) && ((((uintptr_t)dz | (uintptr_t)y) & 15) == 0);
   hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, nchunk), dim3(256), 0, stream, dz, y, (const float*)nullptr, stats, part,
-                     N, C, S, nchunk, len, slope, vec, (unsigned*)nullptr);
+                     N, C, S, nchunk, len, slope, vec, (unsigned*)nullptr, (const float*)nullptr, (const float*)nullptr,
+                     (double*)nullptr);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, stream, part, nchunk, (double)N * (double)S, dgb, C,
                      stats, training, (const unsigned*)nullptr, (const unsigned*)nullptr, 0, (int*)nullptr);
   return dca_launch_status();
@@ -1121,7 +1261,7 @@ extern "C" int dca_bn_backward_pack(const float* dz, const float* y, const float
   const uintptr_t al = (uintptr_t)dz | (uintptr_t)y;
   const int vec = (S % 4 == 0) && ((al & 15) == 0);
   hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, nchunk), dim3(256), 0, stream, dz, y, (const float*)nullptr, stats, part,
-                     N, C, S, nchunk, len, slope, vec, gmax);
+                     N, C, S, nchunk, len, slope, vec, gmax, (const float*)nullptr, (const float*)nullptr, (double*)nullptr);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, stream, part, nchunk, (double)N * (double)S, dgb, C,
                      stats, training, (const unsigned*)gmax, ymax, ymax_slots, dyexps);
   int pchunk; long plen;

@@ -34,8 +34,10 @@ class Multi_Aggregation(nn.Module):
         # conv1 (stride 2) and redir (1x1x1) read the same x: one autograd node, so their two gradients of x are summed in
         # the second backward-data launch instead of by a separate accumulation pass (ops.convbn3d_pair)
         # (c1 has one consumer, the 3x3x3 convolution conv2: packed px2 operand in training)
+        # (redir's BatchNorm has one reader, conv3's res_pre below: in training `skip` is the raw redir output with that
+        # BatchNorm still to apply, and conv3's BatchNorm passes form it in registers -- ops._skip_fold_route)
         c1, skip = ops.convbn3d_pair(x, self.conv1[0][0], self.conv1[0][1], 0.0, self.redir[0], self.redir[1], 1.0,
-                                     pack_a=True)
+                                     pack_a=True, skip_into=self.conv3[1])
         c2 = self.conv2(c1)
         # relu(conv3(c2) + redir(x)) [+ res_post, fused: the caller's `cost0 + augmented_cost`]
         # (the block's output is read by the next classifier head's 3x3x3 convolution -- through a packed twin -- and by the

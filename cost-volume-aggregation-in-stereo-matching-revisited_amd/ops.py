@@ -336,6 +336,7 @@ C1_WGRAD_FUSED = os.environ.get("DCA_C1_WGRAD", "fused") != "expand"   # logit h
 CONV_S2_X2 = os.environ.get("DCA_CONV_S2", "x2") != "fp32"     # the stride-2 convolution itself on the f16x2 split (A/B)
 BN_FUSE = os.environ.get("DCA_BN_FUSE", "1") != "0"        # BatchNorm batch statistics from the conv epilogue (training)   # the transposed-convolution member of the family alone (A/B timing)
 C1_BWD_FUSE = os.environ.get("DCA_C1_BWD", "fused") != "split"      # 1x1x1 conv + BatchNorm backward as one launch (A/B)
+SKIP_FOLD = os.environ.get("DCA_SKIP_FOLD", "1") != "0"    # cva skip BatchNorm folded into the block's output BatchNorm (A/B)
 _X3_MIN_WORKGROUPS = 1
 
 
@@ -568,6 +569,34 @@ def _c1_bwd_fused(dz, x, x2, weight):
                                  _ptr(weight), _ptr(part), _ptr(gx), _ptr(gx2), _ptr(gw), C1 + C2, 1, N, C1, C2,
                                  weight.shape[0], S, _stream()), "dca_conv1_bwd_fused")
     return gx, gx2, gw
+
+
+class _SkipBn:
+    """The skip branch of a block on the folded route (_skip_fold_route): the raw output y of its 1x1x1 convolution, that
+    output's batch-statistics partials (or None) and the slope-1 BatchNorm still to be applied to it.  Handed to `convbn3d` as
+    res_pre, where the block's output BatchNorm applies it in registers (_BnSkipAct); it is never a tensor."""
+    __slots__ = ("y", "part", "bn", "into")
+
+    def __init__(self, y, part, bn, into):
+        self.y, self.part, self.bn, self.into = y, part, bn, into
+
+
+def _skip_fold_route(x, conv_b, bn_b, slope_b, bn_out):
+    """how act(BN_out(.) + BN_b(conv_b(x))) runs, BN_b a slope-1 BatchNorm whose only reader is BN_out's res_pre -- "fold":
+    BN_b is not applied on its own, the apply and backward passes of BN_out form it in registers and its backward reduction
+    rides in BN_out's (_BnSkipAct: a read of y_r for the skip's maxima instead of the pass that writes the skip tensor, and no
+    pass that re-reads g for BN_b's sums), or "apply":
+    two `_BnAct` nodes.  The folded kernels exist for what the training step runs: batch statistics of both BatchNorms under
+    grad, fp32, the packed px2 output with its fp32 copy (pack_out="both", promised by the caller with `bn_out`), and a
+    1x1x1 convolution whose backward takes BN_b's dz as it is (_c1_bwd_route).  Asked once, by convbn3d_pair."""
+    if not (SKIP_FOLD and PACK and CONV_X2 and bn_out is not None and torch.is_grad_enabled() and _lp_dtype() is None):
+        return "apply"
+    C = bn_b.num_features
+    if not (bn_b.training and bn_out.training) or bn_out.num_features != C or C % 8 or float(slope_b) != 1.0:
+        return "apply"
+    if x.dtype != torch.float32 or bn_b.weight is None or bn_b.bias is None:
+        return "apply"
+    return "fold" if _c1_bwd_route(x, None, conv_b.weight) == "fused" else "apply"
 
 
 def _k3s1(weight, stride, transposed, x2, head=False):
@@ -1027,10 +1056,13 @@ class _ConvPair(torch.autograd.Function):
 PAIR_FUSE = os.environ.get("DCA_PAIR_FUSE", "1") != "0"
 
 
-def convbn3d_pair(x, conv_a, bn_a, slope_a, conv_b, bn_b, slope_b, pack_a=False):
+def convbn3d_pair(x, conv_a, bn_a, slope_a, conv_b, bn_b, slope_b, pack_a=False, skip_into=None):
     """(act(BN_a(conv_a(x))), act(BN_b(conv_b(x)))) for conv_a = Conv3d(k3, s2, p1), conv_b = Conv3d(k1) over the SAME x;
     training path: one autograd node for the two convolutions (`_ConvPair`), otherwise two `convbn3d` calls.
-    pack_a: the first result has one consumer, a 3x3x3 stride-1 convolution (see convbn3d, pack_out)"""
+    pack_a: the first result has one consumer, a 3x3x3 stride-1 convolution (see convbn3d, pack_out)
+    skip_into: the caller promises that the second result has ONE reader, the res_pre of a `convbn3d` call with this
+    BatchNorm module and pack_out="both".  On the folded route (_skip_fold_route) the second result is then a `_SkipBn`
+    record for that call instead of a tensor."""
     inference = (not bn_a.training and not bn_b.training and not torch.is_grad_enabled())
     ok = (PAIR_FUSE and not inference and _lp_dtype() is None and conv_a.kernel_size[0] == 3 and conv_a.stride[0] == 2
           and conv_b.kernel_size[0] == 1 and conv_b.weight.shape[0] in (32, 64) and x.dtype == torch.float32
@@ -1038,9 +1070,12 @@ def convbn3d_pair(x, conv_a, bn_a, slope_a, conv_b, bn_b, slope_b, pack_a=False)
     if not ok:
         return convbn3d(x, conv_a, bn_a, slope_a, pack_out=pack_a), convbn3d(x, conv_b, bn_b, slope_b)
     stats = bool(BN_FUSE and bn_a.training and bn_b.training)
-    lazy = _c1_bwd_route(x, None, conv_b.weight) == "fused"
+    fold = _skip_fold_route(x, conv_b, bn_b, slope_b, skip_into) == "fold"
+    lazy = fold or _c1_bwd_route(x, None, conv_b.weight) == "fused"
     ya, pa, yb, pb = _ConvPair.apply(x, conv_a.weight, conv_b.weight, stats, lazy)
     za = bn_act(ya, bn_a, slope_a, stats_part=pa if pa.numel() else None, pack_out=pack_a)
+    if fold:
+        return za, _SkipBn(yb, pb if pb.numel() else None, bn_b, skip_into)
     zb = bn_act(yb, bn_b, slope_b, stats_part=pb if pb.numel() else None, lazy_dy=lazy)
     return za, zb
 
@@ -1198,6 +1233,69 @@ class _BnAct(torch.autograd.Function):
         return dy, dgb[:C], dgb[C:2 * C], None, None, None, None, None, None, g_pre, g_post, None, None, None, None, None
 
 
+class _BnSkipAct(torch.autograd.Function):
+    """z = act(BN(y) + BN_r(y_r)) + res_post, both BatchNorms over batch statistics, BN_r a plain affine (slope 1, no
+    residuals) that only this node reads: the folded route of _skip_fold_route.  One apply pass writes the fp32 z and its
+    packed twin (_BnAct, pack_z 2) with BN_r formed in registers (its per-channel maxima, which the twin's exponents need
+    beforehand, come from a read pass over y_r: half the traffic of the apply pass it replaces); backward's reduce pass carries BN_r's sums, its apply pass
+    writes dy and g, and g travels on as the lazy dz of the 1x1x1 convolution that produced y_r (as _BnAct, lazy_dy).
+    Saves y, y_r and the two statistics vectors -- no tensor of the skip's shape beyond the convolution outputs themselves."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, running_mean, running_var, momentum, eps, part, y_r, gamma_r, beta_r, running_mean_r,
+                running_var_r, momentum_r, eps_r, part_r, slope, res_post, zmax):
+        y, y_r = _req(y, "batch_norm"), _req(y_r, "batch_norm.skip")
+        res_post = _opt(res_post, "res_post")
+        if y_r.shape != y.shape:
+            raise RuntimeError("batch_norm: the skip branch does not have the output's shape")
+        N, C = y.shape[0], y.shape[1]
+        S = y[0, 0].numel()
+        lib = _L()
+        with torch.cuda.device_of(y):
+            stats_r = bn_stats_vector(y_r, gamma_r, beta_r, running_mean_r, running_var_r, True, momentum_r, eps_r, part_r)
+            # max |skip| per channel -- what the skip's own apply pass would have tagged it with -- from a read pass over y_r:
+            # the packed twin gets the exponents of the two-node route, bit for bit
+            nchunk = lib.dca_bn_num_chunks(C, S)
+            rslots = torch.empty((C * CSLOTS,), device=y.device, dtype=torch.int32)
+            _chk(lib.dca_bn_skip_max(_ptr(y_r), _ptr(stats_r), N, C, S, _ptr(rslots), _stream()), "dca_bn_skip_max")
+            zexps = torch.empty((C,), device=y.device, dtype=torch.int32)
+            rpost = _slots_of(res_post) if res_post is not None else None
+            stats = bn_stats_vector(y, gamma, beta, running_mean, running_var, True, momentum, eps, part, zexps,
+                                    (rslots, nchunk), rpost)
+            z, zp = torch.empty_like(y), torch.empty_like(y)
+            _chk(lib.dca_bn_apply_pack_skip(_ptr(y), _ptr(stats), _ptr(zexps), _ptr(zp), N, C, S, float(slope), None, _ptr(y_r),
+                                            _ptr(stats_r), _ptr(res_post), _ptr(z), _ptr(zmax), _stream()),
+                 "dca_bn_apply_pack_skip")
+            _tag_px2(zp, zexps)
+            _tag_twin(z, zp)
+        ctx.save_for_backward(y, stats, y_r, stats_r)
+        ctx.meta = (slope, res_post is not None)
+        return _tag_cmax(z, zmax, lib.dca_bn_pack_chunks(C, S))
+
+    @staticmethod
+    def backward(ctx, dz):
+        y, stats, y_r, stats_r = ctx.saved_tensors
+        slope, has_post = ctx.meta
+        dz = _req(dz, "batch_norm.backward")
+        N, C = y.shape[0], y.shape[1]
+        S = y[0, 0].numel()
+        lib = _L()
+        with torch.cuda.device_of(y):
+            nchunk = lib.dca_bn_num_chunks(C, S)
+            part, part_r = (torch.empty((C * nchunk * 2,), device=y.device, dtype=torch.float64) for _ in range(2))
+            dgb, dgb_r = (torch.empty((4 * C,), device=y.device, dtype=torch.float32) for _ in range(2))
+            dy, g = torch.empty_like(y), torch.empty_like(y)
+            dm = _cslots(C, y.device)                       # per-channel max |dy| for the convolution's backward kernels
+            _chk(lib.dca_bn_backward_skip(_ptr(dz), _ptr(y), _ptr(y_r), _ptr(stats), _ptr(stats_r), _ptr(part), _ptr(part_r),
+                                          _ptr(dgb), _ptr(dgb_r), _ptr(dy), _ptr(g), N, C, S, float(slope), 1, _ptr(dm),
+                                          _stream()), "dca_bn_backward_skip")
+            _tag_cmax(dy, dm, nchunk)
+            g._dca_lazy = (y_r, stats_r, dgb_r, 1.0, True)  # what _c1_bwd_fused reads, as _BnAct.backward hands it on
+        g_post = dz if (has_post and ctx.needs_input_grad[17]) else None
+        return (dy, dgb[:C], dgb[C:2 * C], None, None, None, None, None, g, dgb_r[:C], dgb_r[C:2 * C], None, None, None, None,
+                None, None, g_post, None)
+
+
 _tls = threading.local()
 
 
@@ -1353,12 +1451,34 @@ def bn_act(y, bn, slope=1.0, res_pre=None, res_post=None, stats_part=None, pack_
     z = _BnAct.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps, float(slope),
                      res_pre, res_post, stats_part if training else None, zm, pack_z, pack_dy,
                      bool(lazy_dy and res_pre is None))
+    _bn_count(bn)
+    return z
+
+
+def _bn_count(bn):
+    """the `num_batches_tracked += 1` of a train-mode BatchNorm (deferred inside batched_bn_counters)"""
     if bn.training and bn.num_batches_tracked is not None:
         pending = getattr(_tls, "pending", None)
         if pending is not None:
             pending.append(bn.num_batches_tracked)
         else:
             bn.num_batches_tracked.add_(1)
+
+
+def bn_skip_act(y, bn, slope, skip, res_post=None, stats_part=None):
+    """act(BN(y) + BN_r(y_r)) + res_post for a `_SkipBn` record `skip` (the folded route, decided in convbn3d_pair): fp32
+    result with its packed twin, as bn_act(..., res_pre=<the applied skip>, pack_out="both") gives; both modules' running
+    statistics and counters move as on the two-node route."""
+    if skip.into is not bn:
+        raise RuntimeError("bn_skip_act: this skip branch was folded for another BatchNorm (convbn3d_pair, skip_into)")
+    br = skip.bn
+    mom = lambda b: 0.1 if b.momentum is None else b.momentum
+    zm = _cslots(y.shape[1], y.device)
+    z = _BnSkipAct.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom(bn), bn.eps, stats_part, skip.y,
+                         br.weight, br.bias, br.running_mean, br.running_var, mom(br), br.eps, skip.part, float(slope),
+                         res_post, zm)
+    _bn_count(br)
+    _bn_count(bn)
     return z
 
 
@@ -1414,6 +1534,15 @@ def convbn3d(x, conv, bn, slope=1.0, res_pre=None, res_post=None, x2=None, alias
     tensor or gradient at W % 4 != 0 beside a packed one) is read as fp32 by the kernel that serves that width."""
     transposed = isinstance(conv, torch.nn.ConvTranspose3d)
     stride = conv.stride[0]
+    if isinstance(res_pre, _SkipBn):
+        # the folded route (training under grad, fp32: _skip_fold_route); the caller promised pack_out="both"
+        if pack_out != "both" or alias:
+            raise RuntimeError("convbn3d: a folded skip branch needs pack_out='both' (convbn3d_pair, skip_into)")
+        if BN_FUSE and conv.weight.shape[0 if not transposed else 1] > 1:
+            y, part = _Conv3d.apply(x, x2, conv.weight, int(stride), bool(transposed), True)
+        else:
+            y, part = conv3d(x, conv.weight, stride, transposed, x2), None
+        return bn_skip_act(y, bn, slope, res_pre, res_post, part if (part is not None and part.numel()) else None)
     if alias:
         # alias=True: returns (z, x') with x' = x for the other consumers of x (see _Conv3d.forward); plain (z, x) where the
         # fused form does not apply

@@ -338,6 +338,25 @@ int dca_bn_backward_reduce(const float* dz, const float* y, const float* stats, 
 int dca_bn_backward_pack(const float* dz, const float* y, const float* stats, double* part, float* dgb, void* dyp,
                          int* dyexps, unsigned* gmax, const unsigned* ymax, int ymax_slots, int N, int C, long S,
                          float slope, int training, hipStream_t stream);
+/* The output BatchNorm of a block whose pre-activation residual is ITSELF a slope-1 BatchNorm without residuals over batch
+ * statistics (models/augment/cva.py:26-31: relu(BN_d(deconv) + BN_r(redir))), with that skip BatchNorm folded in: the
+ * residual is never stored, every kernel forms res_pre = fma(y_r, scale_r, shift_r) in registers from the skip's input y_r
+ * and its statistics stats_r -- the bits dca_bn_apply(y_r, stats_r, slope 1) writes.
+ * dca_bn_skip_max:        slots (C * DCA_AMAX_CSLOTS words, nslots = dca_bn_num_chunks(C, S)) receive the per-channel maxima of
+ *                  |res_pre| that dca_bn_apply would emit as zmax while writing it -- a read pass over y_r, no store; handed
+ *                  to dca_bn_finalize[_centered] as rpre_slots, so zexps are those of the route that stores the residual.
+ * dca_bn_apply_pack_skip: dca_bn_apply_pack with (y_r, stats_r) in place of res_pre.
+ * dca_bn_backward_skip:   dca_bn_backward with (y_r, stats_r) in place of res_pre; g_out is required (the skip's producer
+ *                  reads it as its dz) and the reduce pass also forms the skip BatchNorm's sums (part_r, as large as part),
+ *                  so that dgb_r = the dgb of dca_bn_backward_reduce(g_out, y_r, stats_r, slope 1), bit for bit, without
+ *                  that pass. */
+int dca_bn_skip_max(const float* y_r, const float* stats_r, int N, int C, long S, unsigned* slots, hipStream_t stream);
+int dca_bn_apply_pack_skip(const float* y, const float* stats, const int* zexps, void* zp, int N, int C, long S, float slope,
+                           unsigned* ymax, const float* y_r, const float* stats_r, const float* res_post, float* zf,
+                           unsigned* zmax, hipStream_t stream);
+int dca_bn_backward_skip(const float* dz, const float* y, const float* y_r, const float* stats, const float* stats_r,
+                         double* part, double* part_r, float* dgb, float* dgb_r, float* dy, float* g_out, int N, int C,
+                         long S, float slope, int training, unsigned* dmax, hipStream_t stream);
 
 /* ---- AvgPool3d((3,3,3), stride 2, padding 1) -- models/augment/cva.py:39 ---------------------------- */
 int dca_avgpool3d_fwd(const float* x, float* y, long NC, int Di, int Hi, int Wi, hipStream_t stream);
