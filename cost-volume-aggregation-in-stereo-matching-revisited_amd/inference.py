@@ -473,6 +473,119 @@ class KittiInferenceLR(KittiInference):
         return r["filled"], r["valid"]
 
 
+def _check_post(median, speckle):
+    """the `median=` / `speckle=` keywords of the wrappers: 0, 3 or 5 and None or (max_size, max_diff)"""
+    if isinstance(median, bool) or median not in (0, 3, 5):
+        raise ValueError(f"median is 0 (off), 3 or 5, got {median!r}")
+    if speckle is not None:
+        try:
+            size, diff = speckle
+            ok = int(size) == size and 0 <= int(size) < 1 << 31 and 0.0 <= float(diff) < float("inf")
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"speckle is None or (max_size, max_diff) with an integer max_size >= 0 and a finite max_diff >= 0, "
+                             f"got {speckle!r}")
+        speckle = (int(size), float(diff))
+    return int(median), speckle
+
+
+class _Post:
+    """Per-slot buffers of the post-filter (`median=`, `speckle=`), allocated once for the frame size: four float32 maps (the
+    median's result, the mask cropped to the window, the filtered disparity, the filter's validity) and the union-find
+    workspace of `ops.speckle_filter`."""
+
+    def __init__(self, device, crop_height, crop_width):
+        from . import ops
+        self.maps = torch.empty((4, crop_height * crop_width), device=device, dtype=torch.float32)
+        self.workspace = ops.speckle_workspace(crop_height, crop_width, device)
+
+
+def _post_filter(infer, s, pred, mask, window, mask_min, speckle, out_disp=None, out_valid=None):
+    """current stream: `infer.median`, then the speckle filter (max_size, max_diff) = `speckle`, over the window
+    (y0, rows, cols) of the frame's disparity `pred`; mask (of pred's shape, or None) with mask_min
+    decides which pixels are active.  Returns (disp, valid, mask), all (rows,cols): the filtered disparity, the speckle
+    filter's validity (None with `speckle` None) and the mask cropped to the window (None without a mask).  Nothing is
+    allocated after the slot's first frame."""
+    from . import ops
+    if getattr(s, "post", None) is None:
+        s.post = _Post(s.device, infer.crop_height, infer.crop_width)
+    y0, rows, cols = window
+    med, cropped, disp, valid = (s.post.maps[k, :rows * cols].view(rows, cols) for k in range(4))
+    pred = pred.view(pred.shape[-2:])
+    if mask is not None:
+        mask = mask.view(pred.shape)
+        ops.disp_export(mask, y0, rows, cols, out_f32=cropped)
+    else:
+        cropped = None
+    if infer.median:
+        pred = ops.median_filter(pred, infer.median, mask, mask_min, window, out=med)
+        mask, window = cropped, None
+    if speckle is None:                              # (the callers have a median then)
+        return med, None, cropped
+    out = {"disp": disp if out_disp is None else out_disp, "valid": valid if out_valid is None else out_valid}
+    r = ops.speckle_filter(pred, speckle[0], speckle[1], mask, mask_min, window, outputs=("disp",), out=out,
+                           workspace=s.post.workspace)
+    return r["disp"], r["valid"], cropped
+
+
+class KittiInferenceFiltered(KittiInference):
+    """`disp, valid = KittiInferenceFiltered(model, ..., median=0, speckle=(200, 2.0), mask=None | "confidence" | "lr")(left_rgb,
+    right_rgb)`: KittiInference with device I/O (required: the filters run where the disparity lies) followed by the
+    post-filter on the same stream: `ops.median_filter` (`median` = 3 or 5; 0: off), then
+    `ops.speckle_filter` (`speckle` = (max_size, max_diff): components of at most max_size pixels of disparities chained
+    within max_diff are removed; None: only pixels that are not active are removed), both over the image's own window of
+    the padded frame -- the padding is never a neighbour.  `disp` is float32 (h,w), the filtered disparity, +0.0 where a
+    pixel was removed; `valid` float32 1.0 / 0.0.  The mask mode decides which pixels are active, with `mask_min`:
+      None          every finite pixel of KittiInference's disparity
+      "confidence"  KittiInferenceWithConfidence's disparity where the window mass (`radius`) reaches mask_min
+      "lr"          the UNFILLED left disparity where the cross-check (`tau`; two passes per frame) holds
+    The result is `ops.speckle_filter(ops.median_filter(d, ...), ...)` of the map(s) those classes hand out, bit for bit.
+    Buffers are allocated once per slot; both maps come back in one copy and one synchronisation per frame."""
+
+    nmaps = 2
+
+    def __init__(self, model, *args, median: int = 0, speckle=(200, 2.0), mask=None, mask_min: float = 0.5, radius: int = 1,
+                 tau: float = 1.0, device_io: bool = True, **kwargs):
+        if len(args) < 5:                # (KittiInference takes device_io as its fifth positional argument)
+            kwargs["device_io"] = device_io
+        super().__init__(model, *args, **kwargs)
+        if not self.device_io:
+            raise ValueError("KittiInferenceFiltered needs device_io=True: the filters run on the device, next to the disparity")
+        if mask not in (None, "confidence", "lr"):
+            raise ValueError(f"mask is None, 'confidence' or 'lr', got {mask!r}")
+        if int(radius) < 0 or float(mask_min) != float(mask_min):
+            raise ValueError("radius >= 0 and mask_min must not be NaN")
+        self.median, self.speckle = _check_post(median, speckle)
+        self.mask_mode, self.mask_min = mask, float(mask_min)
+        self.radius, self.tau = int(radius), _check_tau(tau)
+        self.confidence = mask == "confidence"
+        self._mirrored = None
+
+    def _frame_maps(self, left, right, cols):
+        if self.mask_mode == "lr":
+            disp, r = _lr_maps(self, left, right, cols, ("valid",))
+            return disp, r["valid"]
+        return super()._frame_maps(left, right, cols)
+
+    def _export(self, s, maps, as_uint16):
+        dst_y0, rows, cols = s.meta[3][1:]
+        dev = s.output(False, 2)[0]
+        out_disp, out_valid = (dev[k * rows * cols:(k + 1) * rows * cols].view(rows, cols) for k in range(2))
+        pred = maps[0].contiguous()
+        mask = maps[1].contiguous() if len(maps) > 1 else None
+        # without a speckle filter, max_size 0 keeps every active pixel: valid = active, and only the others go
+        _post_filter(self, s, pred, mask, (dst_y0, rows, cols), self.mask_min, self.speckle or (0, 0.0), out_disp, out_valid)
+
+    def stream(self, pairs, depth: int = 2):
+        """Generator of (disp, valid) tuples in input order, `depth` frames in flight, each equal byte for byte to the
+        one-at-a-time call."""
+        return super().stream(pairs, depth, False)
+
+    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray):
+        return self._call_device(left_rgb, right_rgb, False)
+
+
 Frame3D = collections.namedtuple("Frame3D", "disp mask depth vertices")
 
 
@@ -516,18 +629,26 @@ class KittiInference3D(KittiInference):
     row-major order, in the left camera's frame (`geometry.write_ply` stores it as it is).  All buffers of a frame in
     flight are allocated once per slot.  The read-back is one copy of the maps with the count in front, then -- once that
     count is on the host -- one copy of exactly count * 16 bytes of vertices: ONE more host wait per frame than the other
-    classes have, on that frame's own copy only; in `stream()` the later frames keep computing meanwhile."""
+    classes have, on that frame's own copy only; in `stream()` the later frames keep computing meanwhile.
+    `median=3 | 5` and `speckle=(max_size, max_diff)` (keywords, off by default) put the post-filter of
+    KittiInferenceFiltered in front of the geometry stage: `disp` is then the filtered disparity, and the speckle filter's
+    validity multiplies the mask exactly where `rectify`'s does -- a removed pixel gets depth 0 and no vertex (mask_min
+    must be > 0).  With the defaults every result is byte for byte what it is without the keywords."""
 
     def __init__(self, model, calib=None, *args, mask=None, mask_min: float = 0.5, min_disp: float = 0.0,
-                 max_depth: float = 80.0, stride: int = 1, radius: int = 1, tau: float = 1.0, **kwargs):
+                 max_depth: float = 80.0, stride: int = 1, radius: int = 1, tau: float = 1.0, speckle=None, median: int = 0,
+                 **kwargs):
         from . import ops
         super().__init__(model, *args, **kwargs)
+        self.median, self.speckle = _check_post(median, speckle)
         if calib is None:
             calib = getattr(self.rectify, "calib", None)
             if calib is None:
                 raise ValueError("KittiInference3D needs calib=, or rectify= maps that carry the rectified pair's calibration")
         if self.rectify is not None and not float(mask_min) > 0.0:
             raise ValueError("with rectify= the maps' validity (0 / 1) enters the mask: mask_min must be > 0")
+        if self.speckle is not None and not float(mask_min) > 0.0:
+            raise ValueError("with speckle= the filter's validity (0 / 1) enters the mask: mask_min must be > 0")
         self._valid_frame = None     # rectify=: valid[0] placed in the frame, float32 (Hc,Wc), built once
         if not self.device_io:
             raise ValueError("KittiInference3D needs device_io=True: the point colours are read from the uint8 image on the device")
@@ -568,9 +689,21 @@ class KittiInference3D(KittiInference):
         for m, out in zip((pred, mask) if mask is not None else (pred,), views):
             ops.disp_export(m, dst_y0, rows, cols, out_f32=out)
         window = (dst_y0, rows, cols)
+        valid = None
         if self.rectify is not None:     # a pixel without a full source footprint is no measurement (the maps handed out stay as they are)
-            valid = self._valid(pred.device, src_y0, dst_y0, rows, cols).view_as(pred)
-            mask = valid if mask is None else mask * valid
+            valid = self._valid(pred.device, src_y0, dst_y0, rows, cols)
+        if self.median or self.speckle is not None:
+            # the post-filter: the disparity handed out is the filtered one, and from here on the maps are the window's own
+            pred, kept, mask = _post_filter(self, s, pred, mask, window, self.filters["mask_min"], self.speckle, out_disp=views[0])
+            if kept is None:
+                views[0].copy_(pred)
+            else:                                    # a removed pixel is no measurement either: depth 0, no vertex
+                mask = kept if mask is None else mask * kept
+            window = (0, rows, cols)
+            if valid is not None:
+                valid = valid[dst_y0:dst_y0 + rows, :cols].contiguous()
+        if valid is not None:
+            mask = valid.view_as(pred) if mask is None else mask * valid.view_as(pred)
         ops.disp_to_depth(pred, self.calib, window, mask, out_f32=views[-1], **self.filters)
         ops.point_cloud(pred, self.calib, s.left, mask, window, v0=src_y0, stride=self.stride,
                         out=g.vert_dev, workspace=(g.offsets, g.count), **self.filters)
@@ -646,13 +779,15 @@ class KittiInferenceColor(KittiInference):
                  "lr": the validity map of the left-right check (`tau`; two passes per frame), invalid pixels are black and the
                  disparity is the UNFILLED one
     Pixels whose disparity is not finite or not > 0 are black.  Both maps come back in one copy and one synchronisation per
-    frame."""
+    frame.  `median=3 | 5` and `speckle=(max_size, max_diff)` (keywords, off by default) run the
+    post-filter of KittiInferenceFiltered first: `disp` is then the filtered disparity and a removed pixel is black."""
 
     def __init__(self, model, *args, cmap: str = "kitti", max_disp=None, mask=None, mask_min: float = 0.5, radius: int = 1,
-                 tau: float = 1.0, device_io: bool = True, **kwargs):
+                 tau: float = 1.0, device_io: bool = True, speckle=None, median: int = 0, **kwargs):
         if len(args) < 5:                # (KittiInference takes device_io as its fifth positional argument)
             kwargs["device_io"] = device_io
         super().__init__(model, *args, **kwargs)
+        self.median, self.speckle = _check_post(median, speckle)
         if not self.device_io:
             raise ValueError("KittiInferenceColor needs device_io=True: the map is coloured on the device, next to the disparity")
         if cmap not in ("kitti", "gray"):
@@ -696,11 +831,22 @@ class KittiInferenceColor(KittiInference):
         out_disp, out_rgb = _Color.views(self._color(s).dev, rows, cols)
         pred = maps[0].contiguous()
         mask = maps[1].contiguous().view_as(pred) if len(maps) > 1 else None
-        ops.disp_export(pred, dst_y0, rows, cols, out_f32=out_disp)
+        y0 = dst_y0
+        if self.median or self.speckle is not None:
+            # the post-filter: the disparity handed out is the filtered one (a removed pixel is +0.0: black), and from here on
+            # the maps are the window's own
+            pred, kept, mask = _post_filter(self, s, pred, mask, (dst_y0, rows, cols), self.mask_min, self.speckle, out_disp=out_disp)
+            if kept is None:
+                out_disp.copy_(pred)
+            elif self.mask_min > 0.0:
+                mask = kept if mask is None else mask * kept
+            y0 = 0
+        else:
+            ops.disp_export(pred, dst_y0, rows, cols, out_f32=out_disp)
         scale = {"max_disp": self.max_disp}
         if self.max_disp == "auto":
-            scale = {"range": ops.disp_range(pred, (dst_y0, rows, cols), mask, self.mask_min)}
-        ops.disp_colorize(pred, dst_y0, rows, cols, cmap=self.cmap, mask=mask, mask_min=self.mask_min, out=out_rgb, **scale)
+            scale = {"range": ops.disp_range(pred, (y0, rows, cols), mask, self.mask_min)}
+        ops.disp_colorize(pred, y0, rows, cols, cmap=self.cmap, mask=mask, mask_min=self.mask_min, out=out_rgb, **scale)
 
     def _readback(self, s, copy):
         """`copy` stream: the disparity and the picture -> pinned, one copy"""

@@ -2834,6 +2834,136 @@ def lidar_disparity(points, calib, n=None, occl=_geometry.LIDAR_OCCL, min_depth=
 
 
 # ------------------------------------------------------------------------------------------------
+# Disparity post-filter (csrc/postfilter.hip): speckle removal -- connected components of similar
+# disparity, the small ones dropped -- and a small masked median.  Inference only, no counterpart in the reference;
+# `postfilter.speckle_filter_host` / `median_filter_host` are the numpy restatements, equal bit for bit.  No launch
+# synchronises; with `out` and `workspace` passed in nothing is allocated either (hipGraph capture).
+# ------------------------------------------------------------------------------------------------
+SPECKLE_TILE = (_C["DCA_SPK_TILE_H"], _C["DCA_SPK_TILE_W"])
+SPECKLE_OUTPUTS = ("disp", "valid", "size")
+_SPECKLE_KINDS = {"disp": torch.float32, "valid": torch.float32, "size": torch.int32}
+POSTFILTER_MAX_BATCH = 65535
+
+
+def _pf_frame(name, disp, mask, mask_min, window):
+    """the maps (Hc,Wc) / (B,Hc,Wc) / (B,1,Hc,Wc), the optional mask of their shape and the window (y0, rows, cols), default
+    whole, as `_geo_frame` takes them for one frame -> (B, Hc, Wc, y0, rows, cols, mask_min, the outputs' shape)"""
+    _req_no_grad(name, disp, mask)
+    _req_dev(disp, name, "the disparity", torch.float32)
+    shape = tuple(disp.shape)
+    if len(shape) not in (2, 3, 4) or (len(shape) == 4 and shape[1] != 1) or disp.numel() == 0:
+        raise RuntimeError(f"{name}: expected (Hc,Wc), (B,Hc,Wc) or (B,1,Hc,Wc) disparity maps, got {shape}")
+    if mask is not None:
+        _req_f32_same(name, disp, mask, "the disparity and the mask")
+    mask_min = float(mask_min)
+    if mask is not None and math.isnan(mask_min):
+        raise RuntimeError(f"{name}: mask_min must not be NaN")
+    Hc, Wc = shape[-2:]
+    B = disp.numel() // (Hc * Wc)
+    try:
+        y0, rows, cols = (0, Hc, Wc) if window is None else (int(v) for v in window)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{name}: window is (y0, rows, cols), got {window!r}") from None
+    if y0 < 0 or rows <= 0 or cols <= 0 or y0 + rows > Hc or cols > Wc:
+        raise RuntimeError(f"{name}: the {rows} x {cols} window at row {y0} does not fit the {Hc} x {Wc} map")
+    if Hc * Wc >= 1 << 31 or rows * cols >= 1 << 31 or B > POSTFILTER_MAX_BATCH:
+        raise RuntimeError(f"{name}: a map must have fewer than 2^31 pixels (label offsets are 32-bit) and a batch at most "
+                           f"{POSTFILTER_MAX_BATCH} maps, got {B} x {Hc} x {Wc}")
+    return B, Hc, Wc, y0, rows, cols, mask_min, shape[:-2] + (rows, cols)
+
+
+def speckle_workspace(rows, cols, device, batch=1):
+    """(label, count): the two int32 buffers of batch * rows * cols words for `speckle_filter(..., workspace=)` on windows up
+    to rows x cols; a call writes every word it reads, nothing has to be cleared between calls"""
+    n = int(batch) * int(rows) * int(cols)
+    if n <= 0 or int(rows) * int(cols) >= 1 << 31:
+        raise RuntimeError(f"speckle_workspace: a {rows} x {cols} window, batch {batch}, is empty or has 2^31 pixels or more")
+    return torch.empty(n, device=device, dtype=torch.int32), torch.empty(n, device=device, dtype=torch.int32)
+
+
+def speckle_filter(disp, max_size, max_diff, mask=None, mask_min=0.5, window=None, fill=0.0, outputs=None, out=None,
+                   workspace=None):
+    """Speckle filter of disparity maps (Hc,Wc) / (B,Hc,Wc) / (B,1,Hc,Wc), images independent, over the window (y0, rows, cols)
+    of every map (definitions: include/dca_hip.h, dca_speckle_filter).  A window pixel is active iff it is finite and (mask is
+    None or mask >= mask_min); two 4-neighbours are joined iff both are active and |a - b| <= max_diff in float32 (equality
+    joins; chained, a ramp with small steps is one component).  max_size: an integer >= 0; components of at most max_size
+    pixels are removed (0: the identity on active pixels).  Returns a dict of (rows,cols) maps per image:
+      disp   float32  the input bit for bit where valid, `fill` elsewhere (+0.0: "no measurement")
+      valid  float32  1.0 where active and size > max_size, 0.0 elsewhere
+      size   int32    the pixel's component size, 0 for an inactive pixel
+    outputs: the names wanted (default all three; `valid` is always computed) -- the others are neither computed nor written.
+    out: a dict of buffers for some or all of them; workspace: `speckle_workspace(...)` of a window and batch at least this
+    large.  With both given nothing is allocated and the host never waits: the four launches can be captured into a
+    hipGraph.  Bitwise reproducible: tile-local union-find in LDS, a merge across tile edges with integer atomics."""
+    name = "speckle_filter"
+    B, Hc, Wc, y0, rows, cols, mask_min, shape = _pf_frame(name, disp, mask, mask_min, window)
+    try:
+        ok = int(max_size) == max_size and 0 <= int(max_size) < 1 << 31 and 0.0 <= float(max_diff) < math.inf
+        max_diff, fill = float(max_diff), float(fill)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise RuntimeError(f"{name}: max_size must be an integer >= 0, max_diff finite and >= 0 and fill a number, got "
+                           f"{max_size!r}, {max_diff!r} and {fill!r}")
+    names = SPECKLE_OUTPUTS if outputs is None else tuple(outputs)
+    if any(n not in SPECKLE_OUTPUTS for n in names):
+        raise RuntimeError(f"{name}: outputs are chosen from {SPECKLE_OUTPUTS}, got {names}")
+    out = {} if out is None else out
+    if not isinstance(out, dict) or set(out) - set(SPECKLE_OUTPUTS):
+        raise RuntimeError(f"{name}: out must be a dict with keys out of {SPECKLE_OUTPUTS}")
+    dev = disp.device
+    res = {}
+    for key in SPECKLE_OUTPUTS:
+        if key not in names and key != "valid":
+            continue
+        if key in out:
+            res[key] = _req_dev(out[key], name, f"out[{key!r}]", _SPECKLE_KINDS[key], shape)
+            if res[key].device != dev:
+                raise RuntimeError(f"{name}: out[{key!r}] must be on the disparity's device")
+        else:
+            res[key] = torch.empty(shape, device=dev, dtype=_SPECKLE_KINDS[key])
+    if workspace is None:
+        workspace = speckle_workspace(rows, cols, dev, B)
+    try:
+        label, count = workspace
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{name}: workspace is the (label, count) pair of `speckle_workspace`") from None
+    for t, what in ((label, "workspace[0] (label)"), (count, "workspace[1] (count)")):
+        _req_dev(t, name, what, torch.int32)
+        if t.numel() < B * rows * cols or t.device != dev:
+            raise RuntimeError(f"{name}: {what} must hold {B * rows * cols} int32 on the disparity's device, got {t.numel()}")
+    if label.data_ptr() == count.data_ptr():
+        raise RuntimeError(f"{name}: workspace[0] and workspace[1] must be two buffers")
+    with torch.cuda.device_of(disp):
+        _chk(_L().dca_speckle_filter(_ptr(disp), _ptr(mask), _ptr(res.get("disp")), _ptr(res["valid"]), _ptr(res.get("size")),
+                                     _ptr(label), _ptr(count), B, Hc, Wc, y0, rows, cols, int(max_size), max_diff, mask_min,
+                                     fill, _stream()), "dca_speckle_filter")
+    return res
+
+
+def median_filter(disp, ksize, mask=None, mask_min=0.5, window=None, out=None):
+    """Masked ksize x ksize median (ksize 3 or 5) of disparity maps (Hc,Wc) / (B,Hc,Wc) / (B,1,Hc,Wc) over the window
+    (y0, rows, cols), one launch (definitions: include/dca_hip.h, dca_median_filter).  For an active centre (finite, and
+    mask is None or mask >= mask_min) the candidates are the active pixels of the neighbourhood inside the window -- no
+    border replication -- and the result is the one of rank (n - 1) // 2, the lower median for even n, an input value bit
+    for bit (-0.0 < +0.0); an inactive centre is copied unchanged.  Returns float32 (rows,cols) per image; out: a buffer
+    of that shape to write into (not the input)."""
+    name = "median_filter"
+    B, Hc, Wc, y0, rows, cols, mask_min, shape = _pf_frame(name, disp, mask, mask_min, window)
+    if isinstance(ksize, bool) or ksize not in (3, 5):
+        raise RuntimeError(f"{name}: ksize is 3 or 5, got {ksize!r}")
+    if out is None:
+        out = torch.empty(shape, device=disp.device, dtype=torch.float32)
+    _req_dev(out, name, "out", torch.float32, shape)
+    if out.device != disp.device or out.untyped_storage().data_ptr() == disp.untyped_storage().data_ptr():
+        raise RuntimeError(f"{name}: out must be a buffer of its own on the disparity's device (the filter is not in place)")
+    with torch.cuda.device_of(disp):
+        _chk(_L().dca_median_filter(_ptr(disp), _ptr(mask), _ptr(out), B, Hc, Wc, y0, rows, cols, int(ksize), mask_min,
+                                    _stream()), "dca_median_filter")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # Pictures of a disparity map (csrc/visualize.hip; DESIGN.md section 6j): the KITTI error map of a prediction against the
 # ground truth (utils/visualization.py:31-55) and the colour-coded disparity map, uint8 RGB on the device.  No launch
 # synchronises; definitions: include/dca_hip.h.

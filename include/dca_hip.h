@@ -866,6 +866,47 @@ int dca_lidar_disparity(const float* points, long N, int S, long n, float m00, f
                         double rel, float* disp, float* depth, unsigned short* disp_u16, long long* count, unsigned* zbuf,
                         hipStream_t stream);
 
+/* ---- disparity post-filter (postfilter.hip); inference only, no backward, no counterpart in the reference
+ * d (B,Hc,Wc) fp32: B independent disparity maps; the window is rows x cols pixels starting at frame row y0, column 0 of every
+ * image, as in dca_disp_export; mask (B,Hc,Wc) fp32 or NULL, indexed like d.  Nothing outside the window is ever read as a
+ * neighbour.  A window pixel is ACTIVE iff d is finite (not NaN, |d| < inf) and (mask == NULL || mask >= mask_min); -0.0 is
+ * a finite value and active.  Outputs are (B,rows,cols).
+ *
+ * dca_speckle_filter (max_size >= 0; max_diff finite, >= 0): two 4-neighbours inside the window are joined iff both are
+ * active and fabsf(a - b) <= max_diff, the subtraction rounded to fp32; equality joins, the relation is symmetric and it
+ * is chained -- a ramp with small steps is ONE component.  Components are the connected components of that graph.
+ *   size  (int32)  the pixel's component size, 0 for an inactive pixel
+ *   valid (fp32)   1.0 where active and size > max_size, 0.0 elsewhere          (max_size = 0: the identity on active pixels)
+ *   disp  (fp32)   the input bit for bit where valid, `fill` elsewhere          (+0.0: the project's "no measurement")
+ * out_disp and out_size may be NULL; out_valid is always written.  label, count: rows cols B int32 words of workspace
+ * each, the caller's; every call writes all of them before it reads any (no clearing between calls).
+ * FOUR launches on the stream (three when the window is a single tile), kernel boundaries being the only global
+ * synchronisation: (1) one workgroup per DCA_SPK_TILE_H x DCA_SPK_TILE_W tile labels the tile in LDS: label = the window
+ * index r cols + c of the pixel's tile-local root, -1 for an inactive pixel, count = the local component's size at that
+ * root; (2) the pixel pairs across tile edges unite in global memory; (3) every tile-local root that is not the global
+ * root adds its count there, ONE integer atomic per (tile, local component); (4) every pixel reads its root's count.
+ * Label invariant: labels only ever decrease, label[x] <= x always, label[x] == x defines a root: every walk to a root
+ * strictly descends, every retry of a union strictly lowers one index, no loop waits for another workgroup.  In launch 2
+ * every label access is an agent-scope atomic (workgroups on different XCDs share the labels); there are no flags, no
+ * tickets, no spin-waits.  After the comparison everything is integer arithmetic or a copy of an input value: bitwise
+ * reproducible, whatever the execution order.
+ *
+ * dca_median_filter (ksize 3 or 5): ONE launch, tile and halo in LDS.  For an active centre the candidates are the active
+ * pixels of the ksize x ksize neighbourhood that lie inside the window (no border replication); with n of them the output
+ * is the candidate of rank (n - 1) / 2 (0-based, ascending: the lower median for even n) in the total order of the bit key
+ * b ^ ((b >> 31) | 0x80000000) (arithmetic shift; -0.0 < +0.0).  The output is an input value bit for bit; an inactive
+ * centre is copied unchanged.  out must not alias d.
+ * Refused: NULL d / out_valid / label / count / out, B outside [1, 65535], a window outside the frame, Hc Wc >= 2^31,
+ * rows cols >= 2^31 (label offsets are 32-bit), max_size < 0, max_diff negative or not finite, ksize outside {3, 5}, a NaN
+ * mask_min with a mask.  No launch synchronises or allocates. */
+#define DCA_SPK_TILE_H 16
+#define DCA_SPK_TILE_W 64
+int dca_speckle_filter(const float* d, const float* mask, float* out_disp, float* out_valid, int* out_size, int* label,
+                       int* count, int B, int Hc, int Wc, int y0, int rows, int cols, int max_size, float max_diff,
+                       float mask_min, float fill, hipStream_t stream);
+int dca_median_filter(const float* d, const float* mask, float* out, int B, int Hc, int Wc, int y0, int rows, int cols,
+                      int ksize, float mask_min, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
