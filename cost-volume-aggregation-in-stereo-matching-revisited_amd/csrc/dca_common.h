@@ -21,6 +21,12 @@ static inline int dca_launch_status() { return (int)hipGetLastError(); }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// the rows x cols window at row y0, column 0 lies inside an Hc x Wc map whose pixel offsets fit 32 bits
+static inline bool dca_window_ok(int Hc, int Wc, int y0, int rows, int cols) {
+  return Hc > 0 && Wc > 0 && (long)Hc * Wc < (1L << 31) && y0 >= 0 && rows > 0 && cols > 0 && (long)y0 + rows <= Hc &&
+         cols <= Wc;
+}
+
 // ---- launch geometry (host) ---------------------------------------------------------------------------------------------
 // A kernel whose launch sizes a caller-allocated buffer (statistics partials, y_cmax slots, weight-gradient slabs) has ONE
 // static function that fills a small geometry record from the problem dimensions; its extern "C" size query and its
@@ -72,6 +78,14 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 // Activation codes used by every epilogue / BN-apply kernel: slope 1 = identity, 0 = ReLU,
 // 0.1 = LeakyReLU(0.1).
 __device__ __forceinline__ float act_apply(float v, float slope) { return v > 0.f ? v : v * slope; }
+
+// uint16(v) as numpy's astype does it wherever that is defined (0 <= v < 65536: truncation toward zero); outside:
+// saturated to [0, 65535], NaN -> 0
+__device__ __forceinline__ unsigned short dca_sat_u16(float v) {
+  if (!(v > 0.f)) return 0;                // negative, zero, NaN
+  if (v >= 65535.f) return 65535;
+  return (unsigned short)(unsigned)v;      // v_cvt_u32_f32 truncates toward zero
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

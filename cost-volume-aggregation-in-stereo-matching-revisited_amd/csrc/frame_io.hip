@@ -188,15 +188,7 @@ extern "C" int dca_frame_apply(const unsigned char* left, const unsigned char* r
 }
 
 // ---- (d) disparity export -------------------------------------------------------------------------------------------------
-// uint16(pred * scale) as numpy's astype does it wherever that is defined (0 <= v < 65536: truncation); outside:
-// saturation, NaN -> 0.
-__device__ __forceinline__ unsigned short fio_u16(float p, float scale) {
-  const float v = p * scale;
-  if (!(v > 0.f)) return 0;                // negative, zero, NaN
-  if (v >= 65535.f) return 65535;
-  return (unsigned short)(unsigned)v;      // v_cvt_u32_f32 truncates toward zero
-}
-
+// uint16(pred * scale): dca_sat_u16 (dca_common.h)
 __global__ __launch_bounds__(FIO_THREADS) void disp_export_kernel(const unsigned* __restrict__ pred,
                                                                   unsigned* __restrict__ out_f32,
                                                                   unsigned short* __restrict__ out_u16, int Wc, int y0,
@@ -206,15 +198,14 @@ __global__ __launch_bounds__(FIO_THREADS) void disp_export_kernel(const unsigned
     const int r = (int)(i / w), c = (int)(i - (long)r * w);
     const unsigned bits = pred[(long)(y0 + r) * Wc + c];
     if (out_f32) out_f32[i] = bits;
-    if (out_u16) out_u16[i] = fio_u16(__uint_as_float(bits), scale);
+    if (out_u16) out_u16[i] = dca_sat_u16(__uint_as_float(bits) * scale);
   }
 }
 
 extern "C" int dca_disp_export(const float* pred, float* out_f32, unsigned short* out_u16, int Hc, int Wc, int y0, int h,
                                int w, float scale, hipStream_t stream) {
   DCA_REQUIRE(pred && (out_f32 || out_u16));
-  DCA_REQUIRE(Hc > 0 && Wc > 0 && (long)Hc * Wc < (1L << 31) && y0 >= 0 && h > 0 && w > 0);
-  DCA_REQUIRE((long)y0 + h <= Hc && w <= Wc);
+  DCA_REQUIRE(dca_window_ok(Hc, Wc, y0, h, w));
   const long n = (long)h * w;
   long nblk = (n + FIO_THREADS - 1) / FIO_THREADS;
   nblk = nblk > 2048 ? 2048 : nblk;

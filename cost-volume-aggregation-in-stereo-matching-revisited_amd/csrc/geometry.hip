@@ -51,13 +51,6 @@ __device__ __forceinline__ bool geo_keep(const GeoArgs& a, int i, int& r, int& c
   return keep && r % a.stride == 0 && c % a.stride == 0;
 }
 
-// uint16(v) as dca_disp_export: truncated toward zero, saturated to [0, 65535], NaN -> 0
-__device__ __forceinline__ unsigned short geo_u16(float v) {
-  if (!(v > 0.f)) return 0;
-  if (v >= 65535.f) return 65535;
-  return (unsigned short)(unsigned)v;
-}
-
 __global__ __launch_bounds__(PC_THREADS) void disp_to_depth_kernel(GeoArgs a, float* __restrict__ out_f32,
                                                                    unsigned short* __restrict__ out_u16, float scale) {
   const int n = a.rows * a.cols;
@@ -66,7 +59,7 @@ __global__ __launch_bounds__(PC_THREADS) void disp_to_depth_kernel(GeoArgs a, fl
     float Z;
     const float z = geo_keep(a, (int)i, r, c, Z) ? Z : 0.f;
     if (out_f32) out_f32[i] = z;
-    if (out_u16) out_u16[i] = geo_u16(z * scale);
+    if (out_u16) out_u16[i] = dca_sat_u16(z * scale);
   }
 }
 
@@ -178,8 +171,7 @@ __global__ __launch_bounds__(PC_THREADS) void pc_emit_kernel(GeoArgs a, const un
 // the scalars every kernel shares, checked once: false = refuse
 bool geo_args(GeoArgs& a, const float* pred, const float* mask, int Hc, int Wc, int y0, int rows, int cols, int stride,
               float fb, float doffs, float min_disp, float max_depth, float mask_min) {
-  if (!pred || Hc <= 0 || Wc <= 0 || (long)Hc * Wc >= (1L << 31) || y0 < 0 || rows <= 0 || cols <= 0) return false;
-  if ((long)y0 + rows > Hc || cols > Wc || stride < 1) return false;
+  if (!pred || !dca_window_ok(Hc, Wc, y0, rows, cols) || stride < 1) return false;
   if (!(fb > 0.f && fb < INFINITY) || !(fabsf(doffs) < INFINITY)) return false;
   if (!(min_disp >= 0.f && min_disp < INFINITY) || !(max_depth > 0.f && max_depth < INFINITY)) return false;
   if (mask && mask_min != mask_min) return false;

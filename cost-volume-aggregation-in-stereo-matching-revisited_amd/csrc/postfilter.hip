@@ -266,8 +266,8 @@ __global__ __launch_bounds__(PF_THREADS) void median_kernel(PfFrame f, int tiles
 }
 
 inline bool pf_frame_ok(const float* d, const float* mask, int B, int Hc, int Wc, int y0, int rows, int cols, float mask_min) {
-  return d && B > 0 && B <= 65535 && Hc > 0 && Wc > 0 && y0 >= 0 && rows > 0 && cols > 0 && (long)y0 + rows <= Hc &&
-         cols <= Wc && (long)Hc * Wc < (1L << 31) && (long)rows * cols < (1L << 31) && !(mask && mask_min != mask_min);
+  return d && B > 0 && B <= 65535 && dca_window_ok(Hc, Wc, y0, rows, cols) && (long)rows * cols < (1L << 31) &&
+         !(mask && mask_min != mask_min);
 }
 
 }  // namespace

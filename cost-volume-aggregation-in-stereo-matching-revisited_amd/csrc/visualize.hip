@@ -282,8 +282,7 @@ extern "C" long dca_disp_range_workspace(int B, int rows, int cols) {
 extern "C" int dca_disp_range(const float* disp, const float* mask, float* range, void* workspace, int B, int Hc, int Wc,
                               int y0, int rows, int cols, float mask_min, hipStream_t stream) {
   DCA_REQUIRE(disp && range && workspace && B > 0 && B <= 65535);
-  DCA_REQUIRE(Hc > 0 && Wc > 0 && (long)B * Hc * Wc < (1L << 31) && y0 >= 0 && rows > 0 && cols > 0);
-  DCA_REQUIRE((long)y0 + rows <= Hc && cols <= Wc && (!mask || mask_min == mask_min));
+  DCA_REQUIRE(dca_window_ok(Hc, Wc, y0, rows, cols) && (long)B * Hc * Wc < (1L << 31) && (!mask || mask_min == mask_min));
   const int nblk = vis_range_blocks((long)rows * ((cols + 3) / 4));
   const int vec = vis_vec(disp, Wc) && (!mask || vis_vec(mask, Wc));
   disp_range_partial_kernel<<<dim3(nblk, B), VIS_THREADS, 0, stream>>>(disp, mask, (float*)workspace, Hc, Wc, y0, rows, cols,
@@ -296,8 +295,7 @@ extern "C" int dca_disp_colorize(const float* disp, const float* mask, const flo
                                  int Wc, int y0, int rows, int cols, float max_disp, float mask_min, int cmap,
                                  hipStream_t stream) {
   DCA_REQUIRE(disp && out_u8 && (cmap == DCA_CMAP_GRAY || cmap == DCA_CMAP_KITTI));
-  DCA_REQUIRE(Hc > 0 && Wc > 0 && (long)Hc * Wc < (1L << 31) && y0 >= 0 && rows > 0 && cols > 0);
-  DCA_REQUIRE((long)y0 + rows <= Hc && cols <= Wc && (!mask || mask_min == mask_min));
+  DCA_REQUIRE(dca_window_ok(Hc, Wc, y0, rows, cols) && (!mask || mask_min == mask_min));
   DCA_REQUIRE(range || (max_disp > 0.f && max_disp < INFINITY));
   const int vec = vis_vec(disp, Wc) && (!mask || vis_vec(mask, Wc));
   const long cells = (long)rows * ((cols + 3) / 4);

@@ -638,7 +638,7 @@ class KittiInference3D(KittiInference):
     def __init__(self, model, calib=None, *args, mask=None, mask_min: float = 0.5, min_disp: float = 0.0,
                  max_depth: float = 80.0, stride: int = 1, radius: int = 1, tau: float = 1.0, speckle=None, median: int = 0,
                  **kwargs):
-        from . import ops
+        from . import frame_ops
         super().__init__(model, *args, **kwargs)
         self.median, self.speckle = _check_post(median, speckle)
         if calib is None:
@@ -656,7 +656,7 @@ class KittiInference3D(KittiInference):
             raise ValueError(f"mask is None, 'confidence' or 'lr', got {mask!r}")
         if int(stride) < 1 or int(radius) < 0:
             raise ValueError("stride >= 1 and radius >= 0")
-        ops._geo_scalars("KittiInference3D", calib, mask_min, min_disp, max_depth)       # the operators' ranges, up front
+        frame_ops._geo_scalars("KittiInference3D", calib, mask_min, min_disp, max_depth)       # the operators' ranges, up front
         self.calib, self.mask_mode = calib, mask
         self.filters = dict(mask_min=float(mask_min), min_disp=float(min_disp), max_depth=float(max_depth))
         self.stride, self.radius, self.tau = int(stride), int(radius), _check_tau(tau)

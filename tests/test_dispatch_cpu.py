@@ -1,8 +1,8 @@
 """Which entry point of libdca_hip.so serves each convolution and weight gradient, pinned without a GPU.
 
 Routing in ops.py reads only shapes, alignment, operand tags and the module flags, so it is observable on CPU tensors:
-`ops._L` is replaced by a recorder that notes every call as (entry-point name, per argument: the int / float value, or
-1 / 0 for a pointer given / null) and launches nothing.  Its answers to the size queries are fixed:
+`ops._L` is replaced by a recorder (tests/_recorder.py) that notes every call as (entry-point name, per argument: the
+int / float value, or 1 / 0 for a pointer given / null) and launches nothing.  Its answers to the size queries are fixed:
 
     *_bytes, *_workspace -> 4096        *_chunks, *_slots -> 4        everything else -> 0 (hipSuccess)
 
@@ -17,7 +17,6 @@ hot-path cases (some 800 launches each) keep the hash and, instead of the sequen
 The file is a record of behaviour, not a specification: re-record it only in a change that means to move a launch, and
 read the diff.  The GPU test at the end runs the `_conv_sliced` / `_wgrad` cases through the real library with the same
 recorder and compares the names (the real size queries answer other values than the fake's, so no hashes there)."""
-import ctypes
 import hashlib
 import json
 import os
@@ -32,9 +31,9 @@ if ROOT not in sys.path:
 
 import dcanet_amd  # noqa: E402,F401
 from dcanet_amd import ops  # noqa: E402
+from _recorder import Recorder  # noqa: E402
 
 GOLDEN_FILE = os.path.join(ROOT, "tests", "golden", "dispatch_trace.json")
-FAKE_SIZES = (("_bytes", 4096), ("_workspace", 4096), ("_chunks", 4), ("_slots", 4))
 
 ALL_ON = dict(CONV_X2=True, CONV_X3=True, CONV_S2_X2=True, WGRAD_S2_X2=True, DECONV_X3=True, C1_WGRAD_FUSED=True,
               BN_FUSE=True, PAIR_FUSE=True, PACK=True, AMAX_EMIT=True, _X3_MIN_WORKGROUPS=1)
@@ -43,32 +42,6 @@ SETTINGS = {"f16x2": {}, "bf16x3": {"CONV_X2": False}, "fp32": {"CONV_X2": False
 SETTINGS.update({"no_" + f: {f: False} for f in ("PACK", "BN_FUSE", "PAIR_FUSE", "CONV_S2_X2", "WGRAD_S2_X2", "DECONV_X3",
                                                  "C1_WGRAD_FUSED")})
 WIDTHS = (24, 22)         # quarter-res widths with W % 4 == 0 and 2; the volumes are (1, C, 6, 10, W)
-
-
-class Recorder:
-    """stands in for the ctypes library: records every call; forwards to `real` if given, else answers FAKE_SIZES"""
-
-    def __init__(self, real=None):
-        self.calls, self.real = [], real
-
-    def __getattr__(self, name):
-        if name.startswith("__"):
-            raise AttributeError(name)
-
-        def entry(*args):
-            self.calls.append([name, [_arg(a) for a in args]])
-            if self.real is not None:
-                return getattr(self.real, name)(*args)
-            return next((v for suffix, v in FAKE_SIZES if name.endswith(suffix)), 0)
-        return entry
-
-
-def _arg(a):
-    if a is None:
-        return 0
-    if isinstance(a, ctypes.c_void_p):
-        return 1 if a.value else 0
-    return float(a) if isinstance(a, float) else int(a)
 
 
 def _summary(calls, raised, counts=False):

@@ -140,7 +140,7 @@ def test_selfsup_launchers_refuse_bad_arguments_before_any_launch():
 
 
 def test_selfsup_operators_refuse_cpu_tensors_and_bad_shapes():
-    from dcanet_amd import ops
+    from dcanet_amd import frame_ops, ops
     from dcanet_amd.models.loss import PhotometricLoss
     from dcanet_amd.utils import loss_disp_smoothness
     I, R, d = torch.zeros(1, 3, 4, 8), torch.zeros(1, 3, 4, 8), torch.zeros(1, 4, 8)
@@ -155,7 +155,7 @@ def test_selfsup_operators_refuse_cpu_tensors_and_bad_shapes():
     # the argument check itself, on stand-ins that claim to be on the device: shapes, dtypes, layout, level count
     from unittest import mock
     with mock.patch.object(torch.Tensor, "is_cuda", new_callable=mock.PropertyMock, return_value=True):
-        chk = lambda *a, scalars=(0.85, 0.1, 1e-4, 9e-4): ops._selfsup_check(*a, scalars)
+        chk = lambda *a, scalars=(0.85, 0.1, 1e-4, 9e-4): frame_ops._selfsup_check(*a, scalars)
         assert chk(I, R, [d], (1.0,), None) == (1, 4, 8, [1.0], 0)
         assert chk(I, R, [d.unsqueeze(1)], (1.0,), torch.ones(1, 4, 8, dtype=torch.bool))[4] == 1
         bad = [
