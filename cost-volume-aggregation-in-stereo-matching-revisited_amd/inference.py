@@ -176,7 +176,7 @@ class _TakesRectify(type):
         obj.rectify = rectify
         obj.__init__(*args, **kwargs)
         if rectify is not None:
-            placement(*rectify.dst_hw, obj.crop_height, obj.crop_width)      # the rectified image must fit or cover the frame
+            placement(*obj._net_hw(*rectify.dst_hw), obj.crop_height, obj.crop_width)      # the rectified image must fit or cover the frame
         return obj
 
 
@@ -203,6 +203,7 @@ class KittiInference(metaclass=_TakesRectify):
     confidence = False           # True: a confidence map next to every disparity map (KittiInferenceWithConfidence)
     radius = 1                   # its window, in 1/4-res disparity bins either side of the peak
     CONF_U16_SCALE = 65535.0      # uint16 scale of the second map (a confidence in [0,1]; a 0 / 1 validity mask)
+    out_scale = 1                # the maps handed out are at most this many times the frame in each direction (HighResInference)
 
     @property
     def nmaps(self):
@@ -258,13 +259,21 @@ class KittiInference(metaclass=_TakesRectify):
         maps = self.forward_frame(left, right)
         return maps if self.confidence else (maps,)
 
+    def _net_hw(self, h, w):
+        """the size at which an h x w image (rectified, with rectify=) enters the network's frame (HighResInference: smaller)"""
+        return h, w
+
+    def _net_pair(self, s, left, right, h, w):
+        """current stream: the uint8 pair on the device as it enters the frame, with its size (HighResInference: downscaled)"""
+        return left, right, h, w
+
     # ---- device I/O: three stages per frame, each enqueued on the stream it is given --------------------------------
     def _slot(self, i):
         dev = next(self.net.parameters()).device
         if self._frames is None:
             self._frames = torch.empty((2, 3, self.crop_height, self.crop_width), device=dev, dtype=torch.float32)
         while len(self._slots) <= i:
-            self._slots.append(_Slot(dev, self.crop_height, self.crop_width))
+            self._slots.append(_Slot(dev, self.crop_height * self.out_scale, self.crop_width * self.out_scale))
         return self._slots[i]
 
     def _upload(self, s, left_rgb, right_rgb, copy):
@@ -278,7 +287,8 @@ class KittiInference(metaclass=_TakesRectify):
         if self.rectify is not None and (h, w) != tuple(self.rectify.src_hw):
             raise ValueError(f"rectify= was built for {self.rectify.src_hw[0]} x {self.rectify.src_hw[1]} raw images, got "
                              f"{h} x {w}")
-        place = placement(*((h, w) if self.rectify is None else self.rectify.dst_hw), self.crop_height, self.crop_width)
+        place = placement(*self._net_hw(*((h, w) if self.rectify is None else self.rectify.dst_hw)), self.crop_height,
+                          self.crop_width)
         n = h * w * c
         off = s.reserve_input(n)
         s.uploaded.synchronize()                     # the previous copy out of the pinned buffer
@@ -305,6 +315,7 @@ class KittiInference(metaclass=_TakesRectify):
                 h, w = self.rectify.dst_hw
                 left, right = ops.rectify_pair(left, right, self.rectify, out=s.rectified(h, w, c))
             s.left = left
+            left, right, h, w = self._net_pair(s, left, right, h, w)
             lut, _ = ops.frame_lut(ops.frame_histogram(left, right), h * w)
             fl, fr = ops.frame_apply(left, right, lut, (self.crop_height, self.crop_width), src_y0, dst_y0, rows, cols,
                                      out=self._frames)
@@ -576,6 +587,115 @@ class KittiInferenceFiltered(KittiInference):
         mask = maps[1].contiguous() if len(maps) > 1 else None
         # without a speckle filter, max_size 0 keeps every active pixel: valid = active, and only the others go
         _post_filter(self, s, pred, mask, (dst_y0, rows, cols), self.mask_min, self.speckle or (0, 0.0), out_disp, out_valid)
+
+    def stream(self, pairs, depth: int = 2):
+        """Generator of (disp, valid) tuples in input order, `depth` frames in flight, each equal byte for byte to the
+        one-at-a-time call."""
+        return super().stream(pairs, depth, False)
+
+    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray):
+        return self._call_device(left_rgb, right_rgb, False)
+
+
+class HighResInference(KittiInference):
+    """`disp, valid = HighResInference(model, scale=2, crop_height=..., crop_width=..., radius=2, sigma_s=1.0, sigma_r=24.0,
+    mask=None | "confidence" | "lr")(left_rgb, right_rgb)`: a pair that is LARGER than the network's frame (a Middlebury-F pair
+    is about 2000 x 2964, the frame 384 x 1248) goes through the network at 1 / scale of its size and comes back at its own
+    (DESIGN.md section 6m).  With device I/O (required: both resamplers read the uint8 pair where it lies), per frame: one
+    upload of the full-resolution pair, `ops.area_downscale_pair` (the reference's INTER_AREA halving for scale 2), the
+    unchanged histogram / table / `frame_apply` path on the small pair, the network, the mask of the chosen mode, ONE launch
+    of `ops.guided_upsample` straight from the padded frame through its window, guided by the full-resolution left image,
+    one read-back.  `crop_height`, `crop_width` are NETWORK-resolution sizes; the small image, ceil(H / scale) x
+    ceil(W / scale), must fit the frame.  `disp` is float32 (H,W) in FULL-resolution pixels (the network's values times
+    scale): the disparity range becomes scale * maxdisp.  `valid` is float32 1.0 / 0.0: 0 where no tap of the upsampler was
+    active (`disp` is +0.0 there).  The taps per mode, with `mask_min`:
+      None          every finite disparity > 0 of KittiInference's map
+      "confidence"  those whose window mass (`conf_radius`) reaches mask_min
+      "lr"          those of the UNFILLED left disparity that pass the cross-check (`tau`; two passes per frame)
+    `radius`, `sigma_s`, `sigma_r`, `floor`: `highres.jbu_tables`; the defaults were not tuned on real data.  The result is
+    `ops.guided_upsample` of the map(s) the existing class of that mode hands out for the downscaled pair, bit for bit.
+    `rectify=maps`: the raw pair is rectified at full resolution first.  With one fp32 sample below 2 GiB per tensor the
+    largest is the cost volume, channels x maxdisp / 4 x H / 4 x W / 4 floats at network resolution: at maxdisp 192 that is
+    fewer than 279,620 quarter-resolution pixels for the 40-channel volume of GwcNet-G and 174,762 for the 64 channels of
+    GwcNet-GC -- network frames up to 1024 x 4368 or 1632 x 2736 (G) and 1024 x 2720 or 1280 x 2176 (GC), so at scale 2
+    full-resolution pairs up to 2048 x 8736 (G) and 2048 x 5440 (GC); a Middlebury-F pair at scale 2 (1000 x 1482 ->
+    frame 1008 x 1488) fits both."""
+
+    nmaps = 2
+    MASKS = (None, "confidence", "lr")
+
+    def __init__(self, model, scale: int = 2, crop_height: int = 384, crop_width: int = 1248, graph: bool = True, dtype=None,
+                 device_io: bool = True, radius: int = 2, sigma_s: float = 1.0, sigma_r: float = 24.0, floor: float = 1e-4,
+                 mask=None, mask_min: float = 0.5, conf_radius: int = 1, tau: float = 1.0):
+        from . import highres
+        if isinstance(scale, bool) or not isinstance(scale, int) or not 2 <= scale <= highres.HR_MAX_SCALE:
+            raise ValueError(f"HighResInference: scale is an integer in 2..{highres.HR_MAX_SCALE}, got {scale!r}")
+        super().__init__(model, crop_height, crop_width, graph, dtype, device_io)
+        if not self.device_io:
+            raise ValueError("HighResInference needs device_io=True: the resamplers read the uint8 pair on the device")
+        if mask not in self.MASKS:
+            raise ValueError(f"mask is None, 'confidence' or 'lr', got {mask!r}")
+        if int(conf_radius) < 0 or float(mask_min) != float(mask_min):
+            raise ValueError("conf_radius >= 0 and mask_min must not be NaN")
+        self.scale = self.out_scale = scale
+        self.tables = highres.jbu_tables(scale, radius, sigma_s, sigma_r, floor)        # (refuses what it cannot do)
+        self._tables_dev = None
+        self.mask_mode, self.mask_min = mask, float(mask_min)
+        self.radius, self.tau = int(conf_radius), _check_tau(tau)       # (`radius` of the parent: the confidence window)
+        self.confidence = mask == "confidence"
+        self._mirrored = None
+
+    def _net_hw(self, h, w):
+        from .highres import small_hw
+        hs, ws = small_hw(h, w, self.scale)
+        if hs > self.crop_height or ws > self.crop_width:
+            raise ValueError(f"a {h} x {w} image is {hs} x {ws} at 1/{self.scale} and does not fit the {self.crop_height} x "
+                             f"{self.crop_width} frame")
+        return hs, ws
+
+    def _net_pair(self, s, left, right, h, w):
+        from . import ops
+        hs, ws = self._net_hw(h, w)
+        c = left.shape[2]
+        small = getattr(s, "small", None)
+        if small is None:            # room for the largest small pair the frame takes, allocated once per slot
+            small = s.small = torch.empty(2 * self.crop_height * self.crop_width * 4, device=s.device, dtype=torch.uint8)
+        s.hr = (h, w)
+        s.guide_lo = ops.area_downscale_pair(left, right, self.scale, out=small[:2 * hs * ws * c].view(2, hs, ws, c))
+        return s.guide_lo[0], s.guide_lo[1], hs, ws
+
+    def _frame_maps(self, left, right, cols):
+        if self.mask_mode == "lr":
+            disp, r = _lr_maps(self, left, right, cols, ("valid",))
+            return disp, r["valid"]
+        return super()._frame_maps(left, right, cols)
+
+    def _maps_out(self, buf, s):
+        h, w = s.hr
+        return tuple(buf[k * h * w:(k + 1) * h * w].view(h, w) for k in range(2))
+
+    def _export(self, s, maps, as_uint16):
+        from . import highres, ops
+        if self._tables_dev is None or self._tables_dev[0].device != s.device:
+            self._tables_dev = highres.device_tables(self.tables, s.device)
+        pred = maps[0].contiguous()
+        mask = maps[1].contiguous().view_as(pred) if len(maps) > 1 else None
+        out_disp, out_valid = self._maps_out(s.output(False, 2)[0], s)
+        ops.guided_upsample(pred, s.guide_lo[0], s.left, self.scale, self._tables_dev, s.meta[3][1:], mask, self.mask_min,
+                            out={"disp": out_disp, "valid": out_valid})
+
+    def _readback(self, s, copy):
+        """`copy` stream: both full-resolution maps -> pinned, one copy"""
+        dev, pin = s.output(False, 2)
+        n = 2 * s.hr[0] * s.hr[1]
+        with torch.cuda.stream(copy):
+            copy.wait_event(s.computed)
+            pin[:n].copy_(dev[:n], non_blocking=True)
+            s.done.record(copy)
+
+    def _result(self, s):
+        s.done.synchronize()
+        return tuple(m.numpy().copy() for m in self._maps_out(s.output(False, 2)[1], s))
 
     def stream(self, pairs, depth: int = 2):
         """Generator of (disp, valid) tuples in input order, `depth` frames in flight, each equal byte for byte to the

@@ -2039,3 +2039,7 @@ from .frame_ops import (  # noqa: E402,F401
     disp_to_depth, point_cloud_tiles, point_cloud_workspace, point_cloud, LIDAR_MAX_RADIUS, lidar_disparity,
     SPECKLE_TILE, SPECKLE_OUTPUTS, POSTFILTER_MAX_BATCH, speckle_workspace, speckle_filter, median_filter, CMAPS,
     disp_error_image, disp_range, disp_colorize)
+# ... and those for high-resolution pairs (highres.py)
+from .highres import (  # noqa: E402,F401
+    HR_MAX_SCALE, HR_MAX_RADIUS, HR_RANGE_LEN, HR_TILE, UPSAMPLE_OUTPUTS, area_downscale_pair, area_downscale_disp,
+    guided_upsample)

@@ -1,6 +1,7 @@
 """The training step's input side and bookkeeping without per-pixel host arithmetic and without a host round trip per
 step: the reference's loaders after the decode (dataloader/datasets.py:221-254 SceneFlow, :270-317 KITTI; the ETH3D
-and Middlebury classes repeat the KITTI body) and its `train()` (main_dca.py:122-141, train_kitti.py:92-120).
+and Middlebury classes repeat the KITTI body; the one used for Middlebury, datasets.py:547-673, halves the pair and the ground
+truth first: `downscale=2` here) and its `train()` (main_dca.py:122-141, train_kitti.py:92-120).
 
 The loaders run three full-image PIL enhancer passes per image (brightness, gamma, contrast), crop, paint an occlusion
 patch into one right crop in five, apply ToTensor + Normalize and hand two fp32 crops to the upload.  Each enhancer maps a
@@ -166,6 +167,18 @@ def draw_kitti(w, h, crop=(256, 512), np_random=np.random, py_random=_pyrandom) 
 
 
 # ---- the complete host path ----------------------------------------------------------------------------------------------
+def downscaled_inputs(left, right, disp, downscale, inf_to_zero=False, flip_rows=False):
+    """The decoded sample at 1 / downscale of its size (`highres.area_downscale_pair_host`, `area_downscale_disp_host`): the
+    uint8 pair block-averaged, the disparity block-averaged and divided by the factor (a uint16 payload is widened to
+    float32 first, which is exact), top-down whatever `flip_rows` says about the source."""
+    from .highres import area_downscale_disp_host, area_downscale_pair_host
+    small = area_downscale_pair_host(left, right, downscale)
+    disp = np.asarray(disp)
+    if disp.dtype == np.uint16:
+        disp = disp.astype(np.float32)
+    return small[0], small[1], area_downscale_disp_host(disp, downscale, inf_to_zero, flip_rows)
+
+
 def _check_pair(left, right):
     left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
     if left.dtype != np.uint8 or right.dtype != np.uint8 or left.ndim != 3 or left.shape[2] not in (3, 4) \
@@ -191,15 +204,21 @@ def photometric_tables(params: AugParams, gamma_fn=gamma_table) -> np.ndarray:
 
 
 def host_sample(left, right, disp, params: AugParams, crop=(256, 512), maxdisp=192, kind="kitti", norm=None,
-                gamma_fn=gamma_table, flip_rows=False, scale=None, inf_to_zero=False):
+                gamma_fn=gamma_table, flip_rows=False, scale=None, inf_to_zero=False, downscale=1):
     """One sample as the reference's loader produces it, from the decoded uint8 pair and the raw disparity:
     kind "kitti" (datasets.py:282-315): brightness, gamma, contrast on the whole image, crop, occlusion patch on the right
     crop, ToTensor + Normalize; kind "sceneflow" (datasets.py:235-245): crop, ToTensor + Normalize.  norm: (2,3,256)
     float32 table of the normalisation (default `inference.imagenet_lut()`); scale: of the disparity (default 1/256 for
-    "kitti", 1 for "sceneflow").  Returns numpy (imgL (3,th,tw) float32, imgR, gt (th,tw) float32, mask (th,tw) bool)."""
+    "kitti", 1 for "sceneflow").  downscale = s in 2..4: the pair and the disparity go through the area downscale of
+    `highres` first (`downscaled_inputs`), and everything else -- the crop parameters too -- refers to the small images;
+    downscale=2 with inf_to_zero=True is the reference's myImageFloder_middlebury_additional (datasets.py:547-673).
+    Returns numpy (imgL (3,th,tw) float32, imgR, gt (th,tw) float32, mask (th,tw) bool)."""
     if kind not in ("kitti", "sceneflow"):
         raise ValueError(f"kind {kind!r}")
     left, right = _check_pair(left, right)
+    if downscale != 1:
+        left, right, disp = downscaled_inputs(left, right, disp, downscale, inf_to_zero, flip_rows)
+        flip_rows = False
     h, w = left.shape[:2]
     th, tw = crop
     _check_params(params, h, w, th, tw)
@@ -235,7 +254,17 @@ class _Stage:
     def __init__(self, device):
         self.device = device
         self.pin = self.dev = None
+        self.small = self.small_d = None             # TrainInput(downscale=): the downscaled pair and disparity
         self.uploaded, self.computed = torch.cuda.Event(), torch.cuda.Event()
+
+    def reserve_small(self, nbytes, nfloats):
+        """views of nbytes uint8 and nfloats float32 on the device, in buffers that grow on demand (their readers run on the
+        one compute stream, in order, so a replaced buffer is freed behind them)"""
+        if self.small is None or self.small.numel() < nbytes:
+            self.small = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+        if self.small_d is None or self.small_d.numel() < nfloats:
+            self.small_d = torch.empty(nfloats, device=self.device, dtype=torch.float32)
+        return self.small[:nbytes], self.small_d[:nfloats]
 
     def reserve(self, nbytes):
         if self.pin is None or self.pin.numel() < nbytes:
@@ -249,7 +278,10 @@ class TrainInput:
 
     kind "kitti": photometric augmentation, crop, occlusion patch, normalisation; the disparity is the uint16 PNG payload
     (scale 1/256) or float32.  kind "sceneflow": crop and normalisation; the disparity is float32, `flip_rows=True` for a
-    PFM payload as stored.  Source sizes may differ from sample to sample.
+    PFM payload as stored.  Source sizes may differ from sample to sample.  downscale = s in 2..4: the uploaded pair and
+    the raw disparity go through `ops.area_downscale_pair` / `ops.area_downscale_disp` first (two more launches; a uint16
+    disparity is widened to float32 before the upload) and the crop refers to the small images, as in `host_sample`;
+    downscale=2 with `load(..., inf_to_zero=True)` is the reference's Middlebury training branch.
 
     device_io=False: `host_sample` into CPU tensors, as a DataLoader hands them over.
     device_io=True: `load` copies the uint8 pair, the raw disparity and 512 bytes of tables into pinned memory, uploads
@@ -260,9 +292,13 @@ class TrainInput:
     `GraphedTrainStep` reads them in place.  No queue setting is changed."""
 
     def __init__(self, batch, crop=(256, 512), maxdisp=192, kind="sceneflow", device_io=False, depth=2, device="cuda",
-                 norm=None, gamma_table=gamma_table, disp_scale=None):
+                 norm=None, gamma_table=gamma_table, disp_scale=None, downscale=1):
         if kind not in ("kitti", "sceneflow"):
             raise ValueError(f"kind {kind!r}")
+        if downscale != 1:
+            from .highres import _scale
+            downscale = _scale("TrainInput", downscale, ValueError)
+        self.downscale = downscale
         if batch < 1 or depth < 1:
             raise ValueError("batch >= 1 and depth >= 1")
         self.B, self.crop, self.maxdisp, self.kind = int(batch), (int(crop[0]), int(crop[1])), maxdisp, kind
@@ -298,7 +334,7 @@ class TrainInput:
             raise IndexError(f"slot {b} of a batch of {self.B}")
         if not self.device_io:
             l, r, g, m = host_sample(left_u8, right_u8, disp, params, self.crop, self.maxdisp, self.kind, self.norm.numpy(),
-                                     self.gamma_fn, flip_rows, self.scale, inf_to_zero)
+                                     self.gamma_fn, flip_rows, self.scale, inf_to_zero, self.downscale)
             self.imgL[b], self.imgR[b] = torch.from_numpy(l), torch.from_numpy(r)
             self.gt[b], self.mask[b] = torch.from_numpy(g), torch.from_numpy(m)
         else:
@@ -311,9 +347,13 @@ class TrainInput:
         disp = np.ascontiguousarray(disp)
         h, w, c = left.shape
         th, tw = self.crop
-        _check_params(p, h, w, th, tw)
+        ds = self.downscale
+        hs, ws = -(-h // ds), -(-w // ds)                 # the size the crop parameters refer to
+        _check_params(p, hs, ws, th, tw)
         if disp.dtype not in (np.float32, np.uint16) or disp.shape != (h, w):
             raise ValueError(f"expected a ({h},{w}) float32 or uint16 disparity, got {disp.dtype} {disp.shape}")
+        if ds > 1 and disp.dtype == np.uint16:
+            disp = disp.astype(np.float32)               # (exact; the downscale kernel takes float32)
         n, nd = h * w * c, disp.nbytes
         off_r = _up16(n)
         off_d = _up16(off_r + n)
@@ -336,6 +376,11 @@ class TrainInput:
         compute.wait_event(s.uploaded)
         L, R = s.dev[:n].view(h, w, c), s.dev[off_r:off_r + n].view(h, w, c)
         D = s.dev[off_d:off_d + nd].view(torch.uint16 if disp.dtype == np.uint16 else torch.float32).view(h, w)
+        if ds > 1:       # two more launches; from here on the sample is the small one, top-down
+            small, small_d = s.reserve_small(2 * hs * ws * c, hs * ws)
+            L, R = ops.area_downscale_pair(L, R, ds, out=small.view(2, hs, ws, c))
+            D = ops.area_downscale_disp(D, ds, inf_to_zero, flip_rows, out=small_d.view(hs, ws))
+            h, w, flip_rows = hs, ws, False
         if self.kind == "kitti":
             bg = s.dev[off_t:total].view(2, 256)
             U, T = ops.train_tables(ops.train_luma_sum(L, R, bg), h * w, bg, p.contrast, self.norm)

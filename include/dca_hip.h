@@ -907,6 +907,62 @@ int dca_speckle_filter(const float* d, const float* mask, float* out_disp, float
 int dca_median_filter(const float* d, const float* mask, float* out, int B, int Hc, int Wc, int y0, int rows, int cols,
                       int ksize, float mask_min, hipStream_t stream);
 
+/* ---- high-resolution pairs (highres.hip): integer-factor area downscale in front of the network,
+ * joint bilateral upsampling of its disparity behind it.  The downscales are the arithmetic of the reference's
+ * myImageFloder_middlebury_additional (dataloader/datasets.py:547-673); the upsampler has no counterpart there.  Everything
+ * in fp32 is evaluated one operation at a time (no fused multiply-adds), divisions are IEEE: the results are bitwise
+ * defined, dcanet_amd/highres.py holds the numpy restatements.  No atomics, no launch synchronises or allocates.
+ *
+ * With a factor s in 2..DCA_HR_MAX_SCALE an (H,W) image has h = ceil(H / s) rows and w = ceil(W / s) columns of blocks;
+ * block (j,i) holds the pixels (y,x) with y / s == j, x / s == i that exist: cnt = (min(H, (j+1) s) - j s) *
+ * (min(W, (i+1) s) - i s) of them, fewer than s s in the last partial row or column.
+ *
+ * dca_area_downscale_u8: ONE launch for both images of a pair.  left, right (H,W,C) uint8 interleaved, C = 3 or 4;
+ * out (2,h,w,C) uint8 (left, then right).  Per byte of every channel (a fourth channel is averaged like the others):
+ *   out = (sum + cnt / 2) / cnt        in integers, sum over the block's pixels
+ * For a full 2x2 block this is (a + b + c + d + 2) >> 2, what OpenCV's INTER_AREA gives for uint8 at fx = fy = 0.5.
+ *
+ * dca_area_downscale_f32: one map (H,W) fp32 -> (h,w) fp32:
+ *   sum = the block's pixels added in row-major order, starting from the first one;  out = (sum / float(cnt)) / float(s)
+ * (the mean of the disparities, then the change of unit to pixels of the small image: datasets.py:593-604 resizes, then
+ * multiplies by resize_scale).  inf_to_zero = 1: an out that is not finite (an infinity or a NaN anywhere in the block)
+ * becomes +0.0 -- the mean is taken with the infinities in it and zeroed afterwards, as the reference does.  flip_rows = 1:
+ * the source is a bottom-up PFM payload, row y of the image is stored row H - 1 - y.
+ *
+ * dca_guided_upsample: ONE frame, ONE launch: joint bilateral upsampling (Kopf et al. 2007) of the network's disparity
+ * under the full-resolution left image.  disp_lo (Hc,Wc) fp32, the padded network frame, of which the window of rows x cols
+ * pixels at frame row y0, column 0 is the image (as in dca_disp_export); mask_lo (Hc,Wc) fp32 or NULL, indexed like disp_lo;
+ * guide_lo (rows,cols,C) uint8, the downscaled left image; guide_hi (H,W,C) uint8 with ceil(H / s) == rows and
+ * ceil(W / s) == cols; ws (s, 2r+1) fp32 and wr (DCA_HR_RANGE_LEN) fp32, the spatial and range tables (the host computes
+ * them: no transcendental function is evaluated on the device); r in 1..DCA_HR_MAX_RADIUS.  For the output pixel (y,x):
+ *   j = y / s;  i = x / s;  py = y % s;  px = x % s;  num = den = 0
+ *   for a = -r..r (outer), b = -r..r (inner), in that order: the tap (j+a, i+b) is ACTIVE iff it lies inside the window,
+ *   its disparity d is finite and > 0 and (mask_lo == NULL || mask_lo >= mask_min).  For an active tap
+ *     k = |dR| + |dG| + |dB| between guide_hi[y,x] and guide_lo[j+a,i+b]          (an integer in 0..765; alpha is ignored)
+ *     wgt = (ws[py][a+r] * ws[px][b+r]) * wr[k];   num = num + wgt * d;   den = den + wgt
+ *   den > 0:  out = (num / den) * float(s), valid = 1.0;   otherwise out = +0.0, valid = 0.0
+ * Nothing outside the window is ever read as a tap.  out, valid: (H,W) fp32, either may be NULL, not both.
+ * One workgroup of DCA_HR_THREADS threads per tile of DCA_HR_TILE_H x DCA_HR_TILE_W output pixels; every thread owns
+ * DCA_HR_RUN consecutive columns of one row.
+ * Refused: NULL inputs or tables, s outside [2, DCA_HR_MAX_SCALE], r outside [1, DCA_HR_MAX_RADIUS], C outside {3, 4},
+ * non-positive sizes, H W >= 2^31 or Hc Wc >= 2^31 (pixel offsets are 32-bit), a window outside the frame, a guide_hi whose
+ * block counts are not (rows, cols), a NaN mask_min with a mask, two NULL outputs, an output that is an input. */
+#define DCA_HR_MAX_SCALE 4
+#define DCA_HR_MAX_RADIUS 3
+#define DCA_HR_RANGE_LEN 766
+#define DCA_HR_THREADS 256
+#define DCA_HR_TILE_H 16
+#define DCA_HR_TILE_W 64
+#define DCA_HR_RUN 4
+int dca_area_downscale_u8(const unsigned char* left, const unsigned char* right, unsigned char* out, int H, int W, int C,
+                          int s, hipStream_t stream);
+int dca_area_downscale_f32(const float* in, float* out, int H, int W, int s, int inf_to_zero, int flip_rows,
+                           hipStream_t stream);
+int dca_guided_upsample(const float* disp_lo, const float* mask_lo, const unsigned char* guide_lo,
+                        const unsigned char* guide_hi, const float* ws, const float* wr, float* out, float* valid, int Hc,
+                        int Wc, int y0, int rows, int cols, int H, int W, int C, int s, int r, float mask_min,
+                        hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
