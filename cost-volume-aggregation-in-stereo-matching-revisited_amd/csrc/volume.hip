@@ -410,6 +410,24 @@ static int gwc_fwd_launch(const float* L, const float* R, float* vol, int B, int
   hipLaunchKernelGGL(gwc_fwd_kernel<CPG>, dim3(H, G, B), dim3(256), lds, s, L, R, vol, B, C, H, W, D, G, vec);
   return dca_launch_status();
 }
+// LDS of gwc_bwd_blocked_kernel: padded rows (the partial sums reuse 6 CPG of the D gv rows)
+static size_t gwc_bwd_blocked_lds(int cpg, int W, int D) { return (size_t)(D + 2 * cpg) * (W + D + 4) * 4; }
+
+// The shape part of the choice between the two backward kernels and the blocked kernel's grid.x in one place (the launcher
+// and dca_gwc_volume_bwd_rows): 0 = gwc_bwd_kernel serves the shape; the launcher adds the 16-byte alignment of the five
+// tensors.
+static int gwc_bwd_blocked_rows(int cpg, int B, int H, int W, int D, int G) {
+  if (!(cpg <= 8 && cpg % 2 == 0 && W % 4 == 0 && W <= 256 && D % 4 == 0 && D >= 6 * cpg && D * (W / 4) <= 3072 &&
+        cpg * (W / 4) <= 512 && gwc_bwd_blocked_lds(cpg, W, D) <= 80 * 1024 && (long)D * H * W * 4 < 0x7ffffff0L &&
+        (long)cpg * H * W * 4 < 0x7ffffff0L))
+    return 0;
+  // persistent over the rows: ~1280 workgroups of 8 waves = five rounds of one per CU
+  int gx = (1280 + G * B - 1) / (G * B);
+  if (gx > H) gx = H;
+  if (gx < 1) gx = 1;
+  return gx;
+}
+
 template <int CPG>
 static int gwc_bwd_launch(const float* gvol, const float* L, const float* R, float* gL, float* gR, int B, int C,
                           int H, int W, int D, int G, hipStream_t s) {
@@ -417,15 +435,10 @@ static int gwc_bwd_launch(const float* gvol, const float* L, const float* R, flo
   if (lds > 64 * 1024)
     hipFuncSetAttribute((const void*)gwc_bwd_kernel<CPG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int vec = (W % 4 == 0) && ((((uintptr_t)gvol | (uintptr_t)L | (uintptr_t)R) & 15) == 0);
-  const size_t blds = (size_t)(D + 2 * CPG) * (W + D + 4) * 4;      // padded rows (the partial sums reuse 6 CPG of the D gv rows)
-  if (CPG <= 8 && CPG % 2 == 0 && vec && W <= 256 && D % 4 == 0 && D >= 6 * CPG && D * (W / 4) <= 3072 && CPG * (W / 4) <= 512 &&
-      ((((uintptr_t)gL | (uintptr_t)gR) & 15) == 0) && blds <= 80 * 1024 && (long)D * H * W * 4 < 0x7ffffff0L &&
-      (long)CPG * H * W * 4 < 0x7ffffff0L) {
+  const int gx = (vec && ((((uintptr_t)gL | (uintptr_t)gR) & 15) == 0)) ? gwc_bwd_blocked_rows(CPG, B, H, W, D, G) : 0;
+  if (gx > 0) {
+    const size_t blds = gwc_bwd_blocked_lds(CPG, W, D);
     hipFuncSetAttribute((const void*)gwc_bwd_blocked_kernel<CPG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);
-    // persistent over the rows: ~1280 workgroups of 8 waves = five rounds of one per CU
-    int gx = (1280 + G * B - 1) / (G * B);
-    if (gx > H) gx = H;
-    if (gx < 1) gx = 1;
     hipLaunchKernelGGL(gwc_bwd_blocked_kernel<CPG>, dim3(gx, G, B), dim3(512), blds, s, gvol, L, R, gL, gR, B, C, H, W, D, G);
     return dca_launch_status();
   }
@@ -448,11 +461,23 @@ extern "C" int dca_gwc_volume_fwd(const float* ref, const float* tgt, float* vol
   }
 }
 
-extern "C" int dca_gwc_volume_bwd(const float* gvol, const float* ref, const float* tgt, float* gref, float* gtgt,
+// what dca_gwc_volume_bwd accepts besides non-null pointers
+static bool gwc_bwd_shape_ok(int B, int C, int H, int W, int maxdisp, int num_groups) {
+  if (!(B > 0 && C > 0 && H > 0 && W > 0 && maxdisp > 0)) return false;
+  if (!(num_groups > 0 && C % num_groups == 0 && H <= 65535 && num_groups <= 65535 && B <= 65535)) return false;
+  if (!((size_t)(maxdisp + 2 * (C / num_groups)) * W * 4 <= 160 * 1024)) return false;
+  const int cpg = C / num_groups;
+  return cpg == 1 || cpg == 2 || cpg == 4 || cpg == 8 || cpg == 16;
+}
+
+extern "C" long dca_gwc_volume_bwd_rows(int B, int C, int H, int W, int maxdisp, int num_groups) {
+  if (!gwc_bwd_shape_ok(B, C, H, W, maxdisp, num_groups)) return -1;
+  return gwc_bwd_blocked_rows(C / num_groups, B, H, W, maxdisp, num_groups);
+}
+
+extern "C" int dca_gwc_volume_bwd(const float* gvol,const float* ref, const float* tgt, float* gref, float* gtgt,
                                   int B, int C, int H, int W, int maxdisp, int num_groups, hipStream_t stream) {
-  DCA_REQUIRE(gvol && ref && tgt && gref && gtgt && B > 0 && C > 0 && H > 0 && W > 0 && maxdisp > 0);
-  DCA_REQUIRE(num_groups > 0 && C % num_groups == 0 && H <= 65535 && num_groups <= 65535 && B <= 65535);
-  DCA_REQUIRE((size_t)(maxdisp + 2 * (C / num_groups)) * W * 4 <= 160 * 1024);
+  DCA_REQUIRE(gvol && ref && tgt && gref && gtgt && gwc_bwd_shape_ok(B, C, H, W, maxdisp, num_groups));
   switch (C / num_groups) {
     case 1: return gwc_bwd_launch<1>(gvol, ref, tgt, gref, gtgt, B, C, H, W, maxdisp, num_groups, stream);
     case 2: return gwc_bwd_launch<2>(gvol, ref, tgt, gref, gtgt, B, C, H, W, maxdisp, num_groups, stream);

@@ -25,9 +25,9 @@
 extern "C" {
 #endif
 
-/* Bumped whenever an argument list below changes; the ctypes loader (_lib.py) refuses a library built from another
+/* Bumped whenever an argument list below changes (21: dca_gwc_volume_bwd_rows joined the volume entries); the ctypes loader (_lib.py) refuses a library built from another
  * version of this header. */
-#define DCA_ABI_VERSION 20
+#define DCA_ABI_VERSION 21
 int dca_abi_version(void);
 
 /* storage types of the reduced-precision inference path (0 = fp32) */
@@ -42,6 +42,11 @@ int dca_gwc_volume_fwd(const float* ref, const float* tgt, float* vol, int B, in
 /* autograd of the above (the reference back-propagates through maxdisp slice-assign nodes). */
 int dca_gwc_volume_bwd(const float* gvol, const float* ref, const float* tgt, float* gref, float* gtgt, int B, int C,
                        int H, int W, int maxdisp, int num_groups, hipStream_t stream);
+/* Which kernel serves dca_gwc_volume_bwd at a shape (host arithmetic, no device call): > 0 = the row-persistent register-
+ * blocked kernel, and the value is its grid.x (a workgroup walks the rows y = blockIdx.x, + grid.x, ...), given 16-byte
+ * aligned gvol / ref / tgt / gref / gtgt; 0 = the plain kernel, one workgroup per row (also what misaligned tensors get at
+ * any shape); < 0 = dca_gwc_volume_bwd refuses these sizes. */
+long dca_gwc_volume_bwd_rows(int B, int C, int H, int W, int maxdisp, int num_groups);
 /* build_concat_volume(refimg_fea, targetimg_fea, maxdisp)  models/submodule.py:134-145; vol: (B,2C,maxdisp,H,W) */
 int dca_concat_volume_fwd(const float* ref, const float* tgt, float* vol, int B, int C, int H, int W, int maxdisp,
                           hipStream_t stream);

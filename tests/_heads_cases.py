@@ -75,7 +75,7 @@ def _sa(shape, mag, branch, arith):
 
 
 def _sa_threads(s):
-    return s[0] * s[2] * s[3]           # one thread per (b, pixel): volume.hip:343, :484
+    return s[0] * s[2] * s[3]           # one thread per (b, pixel): volume.hip:343, :509
 
 
 SOFTARGMIN = (

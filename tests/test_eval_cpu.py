@@ -118,7 +118,7 @@ def test_eval_ops_refuse_cpu_tensors():
 def test_state_length_and_abi():
     from dcanet_amd import _lib
     lib = _lib.load()
-    assert lib.dca_abi_version() == 20
+    assert lib.dca_abi_version() == 21
     assert lib.dca_eval_state_len(24) == 32 + 3 * 24 * 24 and lib.dca_eval_state_len(65) == 0
     assert lib.dca_disp_metrics_workspace(2, 540, 960) > 0 and lib.dca_disp_metrics_workspace(0, 1, 1) == 0
     # invalid arguments are refused before anything is launched (no GPU needed to see that)

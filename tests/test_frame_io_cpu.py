@@ -116,7 +116,7 @@ def test_library_refuses_bad_arguments_without_a_gpu():
     import ctypes
     from dcanet_amd import _lib
     lib = _lib.load()
-    assert lib.dca_abi_version() == 20
+    assert lib.dca_abi_version() == 21
     buf = (ctypes.c_char * 4096)()
     p = ctypes.cast(buf, ctypes.c_void_p)           # a non-null host pointer: refused calls never touch it
     # null pointers

@@ -29,7 +29,7 @@ def test_geometry_entry_points_are_bound_and_exported():
         assert _lib.SIGNATURES[name] == (res, args), name
         fn = getattr(lib, name)
         assert fn.restype is res and list(fn.argtypes) == args, name
-    assert lib.dca_abi_version() == 20 and _lib.ABI_VERSION == 20
+    assert lib.dca_abi_version() == 21 and _lib.ABI_VERSION == 21
     assert _lib.CONSTANTS["DCA_PC_TILE"] == ops.PC_TILE == TILE
     assert _lib.CONSTANTS["DCA_PC_RECORD_BYTES"] == ops.PC_RECORD_BYTES == VERTEX.itemsize == 16
 

@@ -7,6 +7,8 @@ tests/test_gpu_wgrad_fp64.py.  The forward / backward-data convolution kernels g
 20- and 27-tile shapes); two, three and more tiles per workgroup are gated in tests/test_gpu_conv_tiles_fp64.py.  The
 BatchNorm kernels get one chunk of a channel's voxels per launch here (two in the packed training chains); chunk boundaries,
 the finalize loops past 64 partials and the slot counts of the two chunkings are gated in tests/test_gpu_bn_chunks_fp64.py.
+The volume kernels get one image row per workgroup and one trip of every inner loop here; the row walk of the blocked backward
+kernel, its CPG 2 / 4 instantiations and the grid-stride sweeps are gated in tests/test_gpu_volume_fp64.py.
 
 Tolerances (fp32 path, north_star: 1e-3 abs on the disparity): kernel-level max-abs <= 2e-5 * scale for
 forward results (fp32 MFMA is an exact fma chain; only summation order differs), relative-L2 <= 1e-4

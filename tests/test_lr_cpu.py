@@ -17,7 +17,7 @@ def test_lr_entry_points_are_bound_and_exported():
     lib = _lib.load()
     for name in ("dca_mirror_pair", "dca_lr_consistency"):
         assert name in _lib.SIGNATURES and getattr(lib, name) is not None
-    assert lib.dca_abi_version() == 20 and _lib.ABI_VERSION == 20
+    assert lib.dca_abi_version() == 21 and _lib.ABI_VERSION == 21
 
 
 def test_lr_launchers_refuse_bad_arguments_before_any_launch():

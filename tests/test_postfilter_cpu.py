@@ -170,7 +170,7 @@ def test_postfilter_entry_points_are_bound_and_refuse_bad_arguments():
     from dcanet_amd import _lib, ops
     lib = _lib.load()
     assert ops.SPECKLE_TILE == (TH, TW) == (_lib.CONSTANTS["DCA_SPK_TILE_H"], _lib.CONSTANTS["DCA_SPK_TILE_W"])
-    assert _lib.ABI_VERSION == 20 and lib.dca_abi_version() == 20
+    assert _lib.ABI_VERSION == 21 and lib.dca_abi_version() == 21
     for name in ("dca_speckle_filter", "dca_median_filter"):
         assert name in _lib.SIGNATURES and getattr(lib, name) is not None
     p, q, r, s, t, u = (ctypes.c_void_p(16 * k) for k in range(1, 7))

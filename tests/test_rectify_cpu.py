@@ -278,13 +278,13 @@ def test_host_remap_refuses_a_wrong_pair():
 # ---- bindings -------------------------------------------------------------------------------------------------------------------
 def test_rectify_pair_is_bound_and_the_abi_version_stays():
     from dcanet_amd import _lib
-    assert _lib.ABI_VERSION == 20
+    assert _lib.ABI_VERSION == 21
     res, args = _lib.SIGNATURES["dca_rectify_pair"]
     assert res is ctypes.c_int and len(args) == 12
     assert args == [ctypes.c_void_p] * 3 + [ctypes.c_long] + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 5 + [ctypes.c_void_p]
     assert _lib.CONSTANTS["DCA_RECT_FRAC_BITS"] == 5 and _lib.CONSTANTS["DCA_RECT_MAX_SRC"] == 16384
     lib = _lib.load()
-    assert lib.dca_rectify_pair.argtypes == args and lib.dca_abi_version() == 20
+    assert lib.dca_rectify_pair.argtypes == args and lib.dca_abi_version() == 21
     # argument checks come before any launch: no device is touched
     assert lib.dca_rectify_pair(None, None, None, 0, None, None, 1, 1, 1, 1, 3, None) != 0
 

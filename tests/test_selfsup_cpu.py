@@ -98,7 +98,7 @@ def test_selfsup_entry_points_are_bound_and_exported():
     for name in ("dca_selfsup_loss_fwd", "dca_selfsup_loss_bwd"):
         assert name in _lib.SIGNATURES and getattr(lib, name) is not None
     assert len(_lib.SIGNATURES["dca_selfsup_loss_fwd"][1]) == 18 and len(_lib.SIGNATURES["dca_selfsup_loss_bwd"][1]) == 19
-    assert lib.dca_abi_version() == 20 and _lib.ABI_VERSION == 20
+    assert lib.dca_abi_version() == 21 and _lib.ABI_VERSION == 21
     assert ops.SELFSUP_MAX_LEVELS == _lib.CONSTANTS["DCA_SELFSUP_MAX_LEVELS"] == 8
     assert ops.SELFSUP_TILE == (16, 64) and ops.SELFSUP_SUMS == 4 and ops.SELFSUP_OUT == 5
 

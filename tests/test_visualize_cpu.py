@@ -114,7 +114,7 @@ def test_range_restatement():
 def test_launchers_are_bound_and_refuse_bad_arguments_without_a_device():
     from dcanet_amd import _lib
     i, f, p, lg = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_long
-    assert _lib.ABI_VERSION == 20
+    assert _lib.ABI_VERSION == 21
     assert _lib.SIGNATURES["dca_disp_error_image"] == (i, [p] * 4 + [i] * 5 + [f, f, i, p])
     assert _lib.SIGNATURES["dca_disp_range"] == (i, [p] * 4 + [i] * 6 + [f, p])
     assert _lib.SIGNATURES["dca_disp_range_workspace"] == (lg, [i] * 3)
@@ -129,7 +129,7 @@ def test_launchers_are_bound_and_refuse_bad_arguments_without_a_device():
     assert corners == REF.KITTI_CORNERS.astype(int).tolist()
     assert (C["DCA_CMAP_GRAY"], C["DCA_CMAP_KITTI"]) == (0, 1)
     lib = _lib.load()
-    assert lib.dca_abi_version() == 20
+    assert lib.dca_abi_version() == 21
     x = ctypes.c_void_p(4096)        # a non-NULL address that is never dereferenced: every call below is refused before a launch
     err, rng, col = lib.dca_disp_error_image, lib.dca_disp_range, lib.dca_disp_colorize
     assert err(x, x, None, None, 1, 4, 4, 0, 0, 3.0, 0.05, 1, None) != 0                  # no output
