@@ -29,6 +29,7 @@ launch (csrc/rectify.hip) in front of the unchanged chain
 from __future__ import annotations
 
 import collections
+import math
 
 import numpy as np
 import torch
@@ -122,19 +123,24 @@ def imagenet_lut() -> torch.Tensor:
 
 
 class _Slot:
-    """Buffers and events of one frame in flight (device I/O): pinned + device uint8 inputs that grow on demand, device +
-    pinned outputs of the frame's size, allocated when their format (float32 / uint16) is first asked for."""
+    """Buffers and events of one frame in flight (device I/O): pinned + device uint8 inputs that grow on demand, and ONE device +
+    ONE pinned byte buffer for what the frame hands out, sized once for the class's worst case.  The record of the frame in
+    the slot is a list of fields (name, dtype, shape) laid back to back from byte 0 (`set_fields`), so one copy of `out_bytes`
+    brings all of it to the host.  Whatever else a stage keeps per slot lives in `scratch`."""
 
-    def __init__(self, device, crop_height, crop_width):
+    def __init__(self, device, out_capacity):
         self.device = device
         self.in_pin = self.in_dev = None
-        self.out_len = crop_height * crop_width
-        self.out = {}                # (dtype, maps) -> (device, pinned)
+        self.out_dev = torch.empty(out_capacity, device=device, dtype=torch.uint8)
+        self.out_pin = torch.empty(out_capacity, dtype=torch.uint8).pin_memory()
+        self.dev, self.pin, self.out_bytes = {}, {}, 0
         self.uploaded, self.computed, self.done = (torch.cuda.Event() for _ in range(3))
         self.meta = None             # (h, w, c, placement, offset of the right image) of the frame in the slot
-        self.as_uint16 = False
+        self.out_hw = None           # the size of the maps the frame hands out (the window's; HighResInference: the image's)
+        self.copy = None             # the stream the record went out on
         self.rect = {}               # channels -> the rectified pair (rectify=), allocated once for the maps' dst_hw
         self.left = None             # the left image the frame in the slot was built from, as it lies in device memory
+        self._scratch = {}
 
     def reserve_input(self, nbytes):
         """room for two images of nbytes each, the second at the next multiple of 16 (vector loads); returns its offset"""
@@ -154,33 +160,36 @@ class _Slot:
             self.rect[c] = (buf[:n].view(hd, wd, c), buf[off:off + n].view(hd, wd, c))
         return self.rect[c]
 
-    def output(self, as_uint16, nmaps=1):
-        """(device, pinned) buffers with room for `nmaps` maps (disparity[, confidence]); the maps of a frame lie back to
-        back, map k of a rows x cols window at [k * rows * cols, (k + 1) * rows * cols)"""
-        dtype = torch.uint16 if as_uint16 else torch.float32
-        if (dtype, nmaps) not in self.out:
-            self.out[dtype, nmaps] = (torch.empty(nmaps * self.out_len, device=self.device, dtype=dtype),
-                                      torch.empty(nmaps * self.out_len, dtype=dtype).pin_memory())
-        return self.out[dtype, nmaps]
+    def scratch(self, key, build):
+        """a stage's own per-slot buffers, built by `build()` when first asked for"""
+        if key not in self._scratch:
+            self._scratch[key] = build()
+        return self._scratch[key]
+
+    def set_fields(self, fields):
+        """lays out the record of the frame in the slot: `dev` and `pin` become {name: view} of its fields in the device and in
+        the pinned output buffer, `out_bytes` the bytes in use"""
+        self.dev, self.pin, off = {}, {}, 0
+        for name, dtype, shape in fields:
+            end = off + _nbytes([(name, dtype, shape)])
+            self.dev[name] = self.out_dev[off:end].view(dtype).view(shape)
+            self.pin[name] = self.out_pin[off:end].view(dtype).view(shape)
+            off = end
+        self.out_bytes = off
 
 
-class _TakesRectify(type):
-    """The keyword `rectify=` of KittiInference and every subclass is taken HERE, when the class is called, and is in place as
-    `self.rectify` before `__init__` runs: the parameter list of `KittiInference.__init__` is kept as it is (callers and
-    subclasses forward it positionally and through *args / **kwargs)."""
-
-    def __call__(cls, *args, rectify=None, **kwargs):
-        if rectify is not None and not all(hasattr(rectify, k) for k in ("src_hw", "dst_hw", "X", "Y", "valid")):
-            raise TypeError(f"rectify= must be a geometry.RectifyMaps, got {type(rectify)}")
-        obj = cls.__new__(cls)
-        obj.rectify = rectify
-        obj.__init__(*args, **kwargs)
-        if rectify is not None:
-            placement(*obj._net_hw(*rectify.dst_hw), obj.crop_height, obj.crop_width)      # the rectified image must fit or cover the frame
-        return obj
+def _nbytes(fields):
+    return sum(math.prod(shape) * dtype.itemsize for _, dtype, shape in fields)
 
 
-class KittiInference(metaclass=_TakesRectify):
+def _check_tau(tau) -> float:
+    tau = float(tau)
+    if not (0.0 <= tau < float("inf")):
+        raise ValueError("tau must be finite and >= 0")
+    return tau
+
+
+class KittiInference:
     """`disp = KittiInference(model)(left_rgb, right_rgb)`: my_img.py:89-110 `my()` without the file I/O.
 
     `model` is a GwcNet (or the nn.DataParallel wrapper the reference builds, my_img.py:37) already on the GPU with its
@@ -188,42 +197,70 @@ class KittiInference(metaclass=_TakesRectify):
     3 x cva -> classif3 -> soft-argmin) is captured once for the fixed frame size and replayed (`graph=False`: eager).
 
     `device_io=True`: normalisation, padding, crop and the uint16 conversion run as HIP kernels; the host only copies the
-    uint8 pair into pinned memory and the result out of it.  `stream(pairs)` pipelines successive frames.
+    uint8 pair into pinned memory and the result out of it.  `stream(pairs)` pipelines successive frames.  `device_io=None`
+    (the default) is the class's own default: False here, True for the subclasses that work on the device only.
 
     `rectify=maps` (keyword, every subclass too; a geometry.RectifyMaps): the pairs handed in are RAW (maps.src_hw) and are
     rectified first -- `ops.rectify_pair` into a per-slot device buffer with device_io, `rectify_pair_host` without -- and
     everything behind (normalisation, placement, the maps handed out) is of the rectified images (maps.dst_hw): the result is
     what rectifying on the host and handing the rectified pair in gives.  None (the default) changes nothing.
 
-    The subclass `KittiInferenceWithConfidence` hands out `(disp, conf)` per frame (class attribute `confidence`), the
-    subclass `KittiInferenceLR` `(disp_filled, valid)`: a frame's maps come from `_frame_maps`, `nmaps` of them, and go
-    into the slot's output through `_export` (`KittiInference3D` adds its depth map and point cloud there)."""
+    What a subclass states: its mask mode, through `_take_mask` (which disparity and which mask `_frame_maps` yields); the
+    record a frame hands out, through `_fields`; and how the frame's maps get into that record, through `_export`.  The
+    buffers, the read-back, the result, `stream` and `__call__` are here, once."""
 
-    rectify = None               # a geometry.RectifyMaps: set by the `rectify=` keyword before __init__ runs
-    confidence = False           # True: a confidence map next to every disparity map (KittiInferenceWithConfidence)
+    confidence = False           # True: a confidence map next to every disparity map (mask mode "confidence")
     radius = 1                   # its window, in 1/4-res disparity bins either side of the peak
+    mask_mode = None             # None | "confidence" | "lr": what `_frame_maps` yields next to the disparity
     CONF_U16_SCALE = 65535.0      # uint16 scale of the second map (a confidence in [0,1]; a 0 / 1 validity mask)
     out_scale = 1                # the maps handed out are at most this many times the frame in each direction (HighResInference)
+    device_io = False            # what `device_io=None` means for the class
+    needs_device_io = None       # the reason why the class refuses device_io=False, if it does
+    has_uint16 = True            # False: the record has no uint16 form, `as_uint16=True` is refused
+    Frame = None                 # a namedtuple type to hand the fields out in, by name; None: a tuple (one field: itself)
+    _mirrored = None             # (2,1,3,Hc,Wc): the mirrored, swapped frames of `_lr_maps`, rewritten whole by every frame
 
     @property
     def nmaps(self):
-        """maps handed out per frame: the disparity[, a second map in [0,1]]"""
-        return 2 if self.confidence else 1
+        """the network's maps per frame: the disparity[, a second map in [0,1]]"""
+        return 1 if self.mask_mode is None else 2
 
     def __init__(self, model, crop_height: int = 384, crop_width: int = 1248, graph: bool = True, dtype=None,
-                 device_io: bool = False):
+                 device_io: bool = None, *, rectify=None):
         """dtype: None (fp32) or torch.float16 / torch.bfloat16 -- the reduced-precision path of BASELINE config 5
         ("fp16, hipGraph-captured 3D hourglass"): the captured hot path runs under ops.reduced_precision(dtype)."""
+        if rectify is not None and not all(hasattr(rectify, k) for k in ("src_hw", "dst_hw", "X", "Y", "valid")):
+            raise TypeError(f"rectify= must be a geometry.RectifyMaps, got {type(rectify)}")
         self.net = model.module if isinstance(model, torch.nn.DataParallel) else model
         self.crop_height, self.crop_width = crop_height, crop_width
         self.graph = graph
         self.dtype = dtype
         self._graphed = None
-        self.device_io = device_io
+        if device_io is not None:
+            self.device_io = device_io
+        if self.needs_device_io and not self.device_io:
+            raise ValueError(f"{type(self).__name__} needs device_io=True: {self.needs_device_io}")
+        self.rectify = rectify
+        if rectify is not None:
+            placement(*self._net_hw(*rectify.dst_hw), crop_height, crop_width)      # the rectified image must fit or cover the frame
         self._frames = None          # (2,3,Hc,Wc): the network's inputs, rewritten whole by every frame
         self._slots = []
         self._copy_stream = None
         self.net.eval()
+
+    def _take_mask(self, mask, mask_min=0.5, radius=1, tau=1.0):
+        """The mask mode of the instance, checked and stored: which disparity and which mask a frame yields (`_frame_maps`).
+          None          the disparity alone
+          "confidence"  the disparity and the window mass within `radius` bins of the peak
+          "lr"          the UNFILLED left disparity and the validity map of the cross-check under `tau` (two passes per frame)
+        `mask_min` is the threshold the stages behind apply to the mask."""
+        if mask not in (None, "confidence", "lr"):
+            raise ValueError(f"mask is None, 'confidence' or 'lr', got {mask!r}")
+        if int(radius) < 0 or float(mask_min) != float(mask_min):
+            raise ValueError("radius >= 0 and mask_min must not be NaN")
+        self.mask_mode, self.mask_min = mask, float(mask_min)
+        self.radius, self.tau = int(radius), _check_tau(tau)
+        self.confidence = mask == "confidence"
 
     @torch.no_grad()
     def forward_frame(self, left: torch.Tensor, right: torch.Tensor):
@@ -254,8 +291,22 @@ class KittiInference(metaclass=_TakesRectify):
         up = net.prop.forward_planes(guidance, r["stats4_q"][:, :ops.CONF_MASS + 1], (4.0, 4.0, 1.0))
         return up[:, ops.CONF_DISP:ops.CONF_DISP + 1], up[:, ops.CONF_MASS:ops.CONF_MASS + 1]
 
+    @torch.no_grad()
+    def _lr_maps(self, left, right, cols, outputs):
+        """the two passes of the left-right check under `self.tau`: the left disparity as the network gave it and the maps of
+        `ops.lr_consistency` named in `outputs`"""
+        from . import ops
+        disp = self.forward_frame(left, right)           # its own tensor: the second replay below does not touch it
+        if self._mirrored is None or self._mirrored.shape[1:] != left.shape or self._mirrored.device != left.device:
+            self._mirrored = torch.empty((2,) + tuple(left.shape), device=left.device, dtype=torch.float32)
+        disp_m = self.forward_frame(*ops.mirror_pair(left.contiguous(), right.contiguous(), out=self._mirrored))
+        return disp, ops.lr_consistency(disp.contiguous(), disp_m.contiguous(), self.tau, cols, outputs=outputs)
+
     def _frame_maps(self, left, right, cols):
-        """the `nmaps` maps of one frame as a tuple; cols: the image's width inside the frame"""
+        """the `nmaps` maps of one frame as a tuple, by the mask mode; cols: the image's width inside the frame"""
+        if self.mask_mode == "lr":
+            disp, r = self._lr_maps(left, right, cols, ("valid",))
+            return disp, r["valid"]
         maps = self.forward_frame(left, right)
         return maps if self.confidence else (maps,)
 
@@ -267,13 +318,19 @@ class KittiInference(metaclass=_TakesRectify):
         """current stream: the uint8 pair on the device as it enters the frame, with its size (HighResInference: downscaled)"""
         return left, right, h, w
 
+    def _fields(self, rows, cols, as_uint16):
+        """the record of a frame whose maps are rows x cols: (name, dtype, shape) in the order they lie in the slot's buffer"""
+        dtype = torch.uint16 if as_uint16 else torch.float32
+        return [(name, dtype, (rows, cols)) for name in ("disp", "mask")[:self.nmaps]]
+
     # ---- device I/O: three stages per frame, each enqueued on the stream it is given --------------------------------
     def _slot(self, i):
         dev = next(self.net.parameters()).device
         if self._frames is None:
             self._frames = torch.empty((2, 3, self.crop_height, self.crop_width), device=dev, dtype=torch.float32)
         while len(self._slots) <= i:
-            self._slots.append(_Slot(dev, self.crop_height * self.out_scale, self.crop_width * self.out_scale))
+            worst = self._fields(self.crop_height * self.out_scale, self.crop_width * self.out_scale, False)
+            self._slots.append(_Slot(dev, _nbytes(worst)))
         return self._slots[i]
 
     def _upload(self, s, left_rgb, right_rgb, copy):
@@ -314,46 +371,49 @@ class KittiInference(metaclass=_TakesRectify):
             if self.rectify is not None:
                 h, w = self.rectify.dst_hw
                 left, right = ops.rectify_pair(left, right, self.rectify, out=s.rectified(h, w, c))
-            s.left = left
+            s.left, s.out_hw = left, (rows, cols)
             left, right, h, w = self._net_pair(s, left, right, h, w)
             lut, _ = ops.frame_lut(ops.frame_histogram(left, right), h * w)
             fl, fr = ops.frame_apply(left, right, lut, (self.crop_height, self.crop_width), src_y0, dst_y0, rows, cols,
                                      out=self._frames)
-            self._export(s, self._frame_maps(fl, fr, cols), as_uint16)
+            s.set_fields(self._fields(*s.out_hw, as_uint16))
+            self._export(s, self._frame_maps(fl, fr, cols), s.dev)
             s.computed.record(compute)
-        s.as_uint16 = as_uint16
 
-    def _export(self, s, maps, as_uint16):
-        """current stream: the frame's maps, cropped to the image's window, into the slot's device output"""
+    def _export(self, s, maps, out):
+        """current stream: the frame's maps, cropped to the image's window, into `out`, the fields in the slot's device output"""
         from . import ops
         dst_y0, rows, cols = s.meta[3][1:]
-        dev = s.output(as_uint16, len(maps))[0]
-        for k, (m, scale) in enumerate(zip(maps, (256.0, self.CONF_U16_SCALE))):
-            out = dev[k * rows * cols:(k + 1) * rows * cols].view(rows, cols)
-            if as_uint16:
-                ops.disp_export(m.contiguous(), dst_y0, rows, cols, scale=scale, f32=False, u16=True, out_u16=out)
+        for m, o, scale in zip(maps, out.values(), (256.0, self.CONF_U16_SCALE)):
+            if o.dtype == torch.uint16:
+                ops.disp_export(m.contiguous(), dst_y0, rows, cols, scale=scale, f32=False, u16=True, out_u16=o)
             else:
-                ops.disp_export(m.contiguous(), dst_y0, rows, cols, out_f32=out)
+                ops.disp_export(m.contiguous(), dst_y0, rows, cols, out_f32=o)
 
     def _readback(self, s, copy):
-        """`copy` stream: device output -> pinned"""
-        rows, cols = s.meta[3][2:]
-        nmaps = self.nmaps
-        dev, pin = s.output(s.as_uint16, nmaps)
-        n = nmaps * rows * cols                          # one copy: the disparity, and the confidence behind it
+        """`copy` stream: the frame's record, device output -> pinned, in one copy of exactly its bytes"""
+        n = s.out_bytes
         with torch.cuda.stream(copy):
             copy.wait_event(s.computed)
-            pin[:n].copy_(dev[:n], non_blocking=True)
+            s.out_pin[:n].copy_(s.out_dev[:n], non_blocking=True)
             s.done.record(copy)
+        s.copy = copy
+
+    def _rest(self, s, head):
+        """host, after the frame's wait: sends for what the frame hands out beyond its record `head` (the fields in the pinned
+        buffer) and returns a function that waits for it and gives it as {name: array}.  Here: nothing, an empty dict.
+        KittiInference3D: the vertices."""
+        return dict
 
     def _result(self, s):
-        """host: the one synchronisation of a frame, then the result out of the pinned buffer"""
-        rows, cols = s.meta[3][2:]
+        """host: the one synchronisation of a frame, then a copy of every field out of the pinned buffer"""
         s.done.synchronize()
-        nmaps = self.nmaps
-        pin = s.output(s.as_uint16, nmaps)[1]
-        maps = tuple(pin[k * rows * cols:(k + 1) * rows * cols].numpy().reshape(rows, cols).copy() for k in range(nmaps))
-        return maps if nmaps > 1 else maps[0]
+        rest = self._rest(s, s.pin)                  # (in flight while the host copies the fields)
+        out = {name: v.numpy().copy() for name, v in s.pin.items()}
+        out.update(rest())
+        if self.Frame is not None:
+            return self.Frame(*(out.get(name) for name in self.Frame._fields))
+        return tuple(out.values()) if len(out) > 1 else out["disp"]
 
     def _call_device(self, left_rgb, right_rgb, as_uint16):
         dev = next(self.net.parameters()).device
@@ -364,15 +424,20 @@ class KittiInference(metaclass=_TakesRectify):
         self._readback(s, cur)
         return self._result(s)
 
+    def _check_format(self, as_uint16):
+        if as_uint16 and not self.has_uint16:
+            raise TypeError(f"{type(self).__name__} hands out no uint16 form of its frames: as_uint16=True is not for it")
+
     def stream(self, pairs, depth: int = 2, as_uint16: bool = False):
         """Generator over an iterable of (left_rgb, right_rgb) uint8 pairs (sizes may differ as long as each fits the
-        frame): yields the disparities -- with confidence, the (disp, conf) tuples -- in input order, `depth` frames in
-        flight.  A copy stream beside the compute stream carries the upload of frame i+1 and the read-back of frame i-1
-        while frame i computes."""
+        frame): yields what `__call__` gives for each pair, byte for byte, in input order, `depth` frames in flight.  A copy
+        stream beside the compute stream carries the upload of frame i+1 and the read-back of frame i-1 while frame i
+        computes."""
         if not self.device_io:
             raise RuntimeError("stream() needs KittiInference(..., device_io=True)")
         if depth < 1:
             raise ValueError("depth >= 1")
+        self._check_format(as_uint16)
         dev = next(self.net.parameters()).device
         compute = torch.cuda.current_stream(dev)
         if self._copy_stream is None:
@@ -404,7 +469,8 @@ class KittiInference(metaclass=_TakesRectify):
         finally:
             compute.wait_stream(copy)                # later work on the compute stream may reuse slot 0 (`__call__`)
 
-    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray, as_uint16: bool = False) -> np.ndarray:
+    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray, as_uint16: bool = False):
+        self._check_format(as_uint16)
         if self.device_io:
             return self._call_device(left_rgb, right_rgb, as_uint16)
         if self.rectify is not None:
@@ -430,32 +496,9 @@ class KittiInferenceWithConfidence(KittiInference):
     the captured hot path; with device I/O both maps come back in one copy and one synchronisation per frame.  The
     disparity is bitwise KittiInference's."""
 
-    confidence = True
-
     def __init__(self, model, *args, radius: int = 1, **kwargs):
         super().__init__(model, *args, **kwargs)
-        if int(radius) < 0:
-            raise ValueError("radius >= 0")
-        self.radius = int(radius)
-
-
-def _check_tau(tau) -> float:
-    tau = float(tau)
-    if not (0.0 <= tau < float("inf")):
-        raise ValueError("tau must be finite and >= 0")
-    return tau
-
-
-@torch.no_grad()
-def _lr_maps(infer, left, right, cols, outputs):
-    """the two passes of the left-right check for `infer` (its `tau`, its `_mirrored` buffer): the left disparity as the
-    network gave it and the maps of `ops.lr_consistency` named in `outputs`"""
-    from . import ops
-    disp = infer.forward_frame(left, right)          # its own tensor: the second replay below does not touch it
-    if infer._mirrored is None or infer._mirrored.shape[1:] != left.shape or infer._mirrored.device != left.device:
-        infer._mirrored = torch.empty((2,) + tuple(left.shape), device=left.device, dtype=torch.float32)
-    disp_m = infer.forward_frame(*ops.mirror_pair(left.contiguous(), right.contiguous(), out=infer._mirrored))
-    return disp, ops.lr_consistency(disp.contiguous(), disp_m.contiguous(), infer.tau, cols, outputs=outputs)
+        self._take_mask("confidence", radius=radius)
 
 
 class KittiInferenceLR(KittiInference):
@@ -471,16 +514,13 @@ class KittiInferenceLR(KittiInference):
     `valid` is float32 1.0 / 0.0, or uint16 65535 / 0 with as_uint16 (dca_disp_export with scale 65535).  With device I/O
     both maps come back in one copy and one synchronisation per frame.  A frame costs about two of KittiInference's."""
 
-    nmaps = 2
-
     def __init__(self, model, *args, tau: float = 1.0, **kwargs):
         super().__init__(model, *args, **kwargs)
-        self.tau = _check_tau(tau)
-        self._mirrored = None        # (2,1,3,Hc,Wc): the mirrored, swapped frames, rewritten whole by every frame
+        self._take_mask("lr", tau=tau)
 
-    @torch.no_grad()
     def _frame_maps(self, left, right, cols):
-        _, r = _lr_maps(self, left, right, cols, ("valid", "filled"))
+        """its own case: the FILLED disparity (the classes behind a mask mode take the unfilled one)"""
+        _, r = self._lr_maps(left, right, cols, ("valid", "filled"))
         return r["filled"], r["valid"]
 
 
@@ -512,17 +552,18 @@ class _Post:
         self.workspace = ops.speckle_workspace(crop_height, crop_width, device)
 
 
-def _post_filter(infer, s, pred, mask, window, mask_min, speckle, out_disp=None, out_valid=None):
-    """current stream: `infer.median`, then the speckle filter (max_size, max_diff) = `speckle`, over the window
-    (y0, rows, cols) of the frame's disparity `pred`; mask (of pred's shape, or None) with mask_min
-    decides which pixels are active.  Returns (disp, valid, mask), all (rows,cols): the filtered disparity, the speckle
-    filter's validity (None with `speckle` None) and the mask cropped to the window (None without a mask).  Nothing is
-    allocated after the slot's first frame."""
+def _post_filter(infer, s, pred, mask, window, out_disp, speckle, fold, out_valid=None):
+    """current stream: `infer.median`, then the speckle filter (max_size, max_diff) = `speckle` (None: none), over the window
+    (y0, rows, cols) of the frame's disparity `pred`; mask (of pred's shape, or None) with
+    `infer.mask_min` decides which pixels are active.  The filtered disparity goes to `out_disp`, the speckle filter's validity
+    to `out_valid` if given.  Returns the (pred, mask, window) the following stage reads: the filtered disparity and the
+    mask, both the window's own (rows,cols) from here on.  `fold`: the speckle filter's validity multiplies the mask (a
+    removed pixel is no measurement), which is sound only where the stage behind applies a mask_min > 0.  Nothing is allocated
+    after the slot's first frame, but the product of a fold."""
     from . import ops
-    if getattr(s, "post", None) is None:
-        s.post = _Post(s.device, infer.crop_height, infer.crop_width)
+    post = s.scratch("post", lambda: _Post(s.device, infer.crop_height, infer.crop_width))
     y0, rows, cols = window
-    med, cropped, disp, valid = (s.post.maps[k, :rows * cols].view(rows, cols) for k in range(4))
+    med, cropped, disp, valid = (post.maps[k, :rows * cols].view(rows, cols) for k in range(4))
     pred = pred.view(pred.shape[-2:])
     if mask is not None:
         mask = mask.view(pred.shape)
@@ -530,14 +571,16 @@ def _post_filter(infer, s, pred, mask, window, mask_min, speckle, out_disp=None,
     else:
         cropped = None
     if infer.median:
-        pred = ops.median_filter(pred, infer.median, mask, mask_min, window, out=med)
+        pred = ops.median_filter(pred, infer.median, mask, infer.mask_min, window, out=med)
         mask, window = cropped, None
-    if speckle is None:                              # (the callers have a median then)
-        return med, None, cropped
-    out = {"disp": disp if out_disp is None else out_disp, "valid": valid if out_valid is None else out_valid}
-    r = ops.speckle_filter(pred, speckle[0], speckle[1], mask, mask_min, window, outputs=("disp",), out=out,
-                           workspace=s.post.workspace)
-    return r["disp"], r["valid"], cropped
+    if speckle is None:                              # the median alone (the callers have one then)
+        out_disp.copy_(med)
+        return med, cropped, (0, rows, cols)
+    r = ops.speckle_filter(pred, speckle[0], speckle[1], mask, infer.mask_min, window, outputs=("disp",),
+                           out={"disp": out_disp, "valid": valid if out_valid is None else out_valid}, workspace=post.workspace)
+    if fold:
+        cropped = r["valid"] if cropped is None else cropped * r["valid"]
+    return r["disp"], cropped, (0, rows, cols)
 
 
 class KittiInferenceFiltered(KittiInference):
@@ -555,46 +598,25 @@ class KittiInferenceFiltered(KittiInference):
     Buffers are allocated once per slot; both maps come back in one copy and one synchronisation per frame."""
 
     nmaps = 2
+    device_io = True
+    needs_device_io = "the filters run on the device, next to the disparity"
+    has_uint16 = False
 
     def __init__(self, model, *args, median: int = 0, speckle=(200, 2.0), mask=None, mask_min: float = 0.5, radius: int = 1,
-                 tau: float = 1.0, device_io: bool = True, **kwargs):
-        if len(args) < 5:                # (KittiInference takes device_io as its fifth positional argument)
-            kwargs["device_io"] = device_io
+                 tau: float = 1.0, **kwargs):
         super().__init__(model, *args, **kwargs)
-        if not self.device_io:
-            raise ValueError("KittiInferenceFiltered needs device_io=True: the filters run on the device, next to the disparity")
-        if mask not in (None, "confidence", "lr"):
-            raise ValueError(f"mask is None, 'confidence' or 'lr', got {mask!r}")
-        if int(radius) < 0 or float(mask_min) != float(mask_min):
-            raise ValueError("radius >= 0 and mask_min must not be NaN")
+        self._take_mask(mask, mask_min, radius, tau)
         self.median, self.speckle = _check_post(median, speckle)
-        self.mask_mode, self.mask_min = mask, float(mask_min)
-        self.radius, self.tau = int(radius), _check_tau(tau)
-        self.confidence = mask == "confidence"
-        self._mirrored = None
 
-    def _frame_maps(self, left, right, cols):
-        if self.mask_mode == "lr":
-            disp, r = _lr_maps(self, left, right, cols, ("valid",))
-            return disp, r["valid"]
-        return super()._frame_maps(left, right, cols)
+    def _fields(self, rows, cols, as_uint16):
+        return [("disp", torch.float32, (rows, cols)), ("valid", torch.float32, (rows, cols))]
 
-    def _export(self, s, maps, as_uint16):
-        dst_y0, rows, cols = s.meta[3][1:]
-        dev = s.output(False, 2)[0]
-        out_disp, out_valid = (dev[k * rows * cols:(k + 1) * rows * cols].view(rows, cols) for k in range(2))
+    def _export(self, s, maps, out):
         pred = maps[0].contiguous()
         mask = maps[1].contiguous() if len(maps) > 1 else None
-        # without a speckle filter, max_size 0 keeps every active pixel: valid = active, and only the others go
-        _post_filter(self, s, pred, mask, (dst_y0, rows, cols), self.mask_min, self.speckle or (0, 0.0), out_disp, out_valid)
-
-    def stream(self, pairs, depth: int = 2):
-        """Generator of (disp, valid) tuples in input order, `depth` frames in flight, each equal byte for byte to the
-        one-at-a-time call."""
-        return super().stream(pairs, depth, False)
-
-    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray):
-        return self._call_device(left_rgb, right_rgb, False)
+        # without a speckle filter, max_size 0 keeps every active pixel: valid = active, and only the others go.  `valid` is
+        # handed out itself: nothing behind reads the mask, so nothing is folded into it
+        _post_filter(self, s, pred, mask, s.meta[3][1:], out["disp"], self.speckle or (0, 0.0), False, out["valid"])
 
 
 class HighResInference(KittiInference):
@@ -622,28 +644,21 @@ class HighResInference(KittiInference):
     frame 1008 x 1488) fits both."""
 
     nmaps = 2
+    needs_device_io = "the resamplers read the uint8 pair on the device"
+    has_uint16 = False
     MASKS = (None, "confidence", "lr")
 
     def __init__(self, model, scale: int = 2, crop_height: int = 384, crop_width: int = 1248, graph: bool = True, dtype=None,
                  device_io: bool = True, radius: int = 2, sigma_s: float = 1.0, sigma_r: float = 24.0, floor: float = 1e-4,
-                 mask=None, mask_min: float = 0.5, conf_radius: int = 1, tau: float = 1.0):
+                 mask=None, mask_min: float = 0.5, conf_radius: int = 1, tau: float = 1.0, *, rectify=None):
         from . import highres
         if isinstance(scale, bool) or not isinstance(scale, int) or not 2 <= scale <= highres.HR_MAX_SCALE:
             raise ValueError(f"HighResInference: scale is an integer in 2..{highres.HR_MAX_SCALE}, got {scale!r}")
-        super().__init__(model, crop_height, crop_width, graph, dtype, device_io)
-        if not self.device_io:
-            raise ValueError("HighResInference needs device_io=True: the resamplers read the uint8 pair on the device")
-        if mask not in self.MASKS:
-            raise ValueError(f"mask is None, 'confidence' or 'lr', got {mask!r}")
-        if int(conf_radius) < 0 or float(mask_min) != float(mask_min):
-            raise ValueError("conf_radius >= 0 and mask_min must not be NaN")
-        self.scale = self.out_scale = scale
+        self.scale = self.out_scale = scale             # (`_net_hw` reads it when the parent fits rectify= into the frame)
+        super().__init__(model, crop_height, crop_width, graph, dtype, device_io, rectify=rectify)
+        self._take_mask(mask, mask_min, conf_radius, tau)       # (`radius` of the parent: the confidence window)
         self.tables = highres.jbu_tables(scale, radius, sigma_s, sigma_r, floor)        # (refuses what it cannot do)
         self._tables_dev = None
-        self.mask_mode, self.mask_min = mask, float(mask_min)
-        self.radius, self.tau = int(conf_radius), _check_tau(tau)       # (`radius` of the parent: the confidence window)
-        self.confidence = mask == "confidence"
-        self._mirrored = None
 
     def _net_hw(self, h, w):
         from .highres import small_hw
@@ -657,80 +672,41 @@ class HighResInference(KittiInference):
         from . import ops
         hs, ws = self._net_hw(h, w)
         c = left.shape[2]
-        small = getattr(s, "small", None)
-        if small is None:            # room for the largest small pair the frame takes, allocated once per slot
-            small = s.small = torch.empty(2 * self.crop_height * self.crop_width * 4, device=s.device, dtype=torch.uint8)
-        s.hr = (h, w)
-        s.guide_lo = ops.area_downscale_pair(left, right, self.scale, out=small[:2 * hs * ws * c].view(2, hs, ws, c))
-        return s.guide_lo[0], s.guide_lo[1], hs, ws
+        s.out_hw = (h, w)                                # the maps come back at the image's own size
+        small = ops.area_downscale_pair(left, right, self.scale, out=self._small(s, hs, ws, c))
+        return small[0], small[1], hs, ws
 
-    def _frame_maps(self, left, right, cols):
-        if self.mask_mode == "lr":
-            disp, r = _lr_maps(self, left, right, cols, ("valid",))
-            return disp, r["valid"]
-        return super()._frame_maps(left, right, cols)
+    def _small(self, s, hs, ws, c):
+        """the slot's downscaled pair, (2,hs,ws,c) uint8, in a buffer with room for the largest the frame takes"""
+        buf = s.scratch("small", lambda: torch.empty(2 * self.crop_height * self.crop_width * 4, device=s.device, dtype=torch.uint8))
+        return buf[:2 * hs * ws * c].view(2, hs, ws, c)
 
-    def _maps_out(self, buf, s):
-        h, w = s.hr
-        return tuple(buf[k * h * w:(k + 1) * h * w].view(h, w) for k in range(2))
+    def _fields(self, h, w, as_uint16):
+        return [("disp", torch.float32, (h, w)), ("valid", torch.float32, (h, w))]
 
-    def _export(self, s, maps, as_uint16):
+    def _export(self, s, maps, out):
         from . import highres, ops
         if self._tables_dev is None or self._tables_dev[0].device != s.device:
             self._tables_dev = highres.device_tables(self.tables, s.device)
         pred = maps[0].contiguous()
         mask = maps[1].contiguous().view_as(pred) if len(maps) > 1 else None
-        out_disp, out_valid = self._maps_out(s.output(False, 2)[0], s)
-        ops.guided_upsample(pred, s.guide_lo[0], s.left, self.scale, self._tables_dev, s.meta[3][1:], mask, self.mask_min,
-                            out={"disp": out_disp, "valid": out_valid})
-
-    def _readback(self, s, copy):
-        """`copy` stream: both full-resolution maps -> pinned, one copy"""
-        dev, pin = s.output(False, 2)
-        n = 2 * s.hr[0] * s.hr[1]
-        with torch.cuda.stream(copy):
-            copy.wait_event(s.computed)
-            pin[:n].copy_(dev[:n], non_blocking=True)
-            s.done.record(copy)
-
-    def _result(self, s):
-        s.done.synchronize()
-        return tuple(m.numpy().copy() for m in self._maps_out(s.output(False, 2)[1], s))
-
-    def stream(self, pairs, depth: int = 2):
-        """Generator of (disp, valid) tuples in input order, `depth` frames in flight, each equal byte for byte to the
-        one-at-a-time call."""
-        return super().stream(pairs, depth, False)
-
-    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray):
-        return self._call_device(left_rgb, right_rgb, False)
+        guide_lo = self._small(s, *s.meta[3][2:], s.left.shape[2])[0]        # (the small image fits the frame: the window is its size)
+        ops.guided_upsample(pred, guide_lo, s.left, self.scale, self._tables_dev, s.meta[3][1:], mask, self.mask_min, out=out)
 
 
 Frame3D = collections.namedtuple("Frame3D", "disp mask depth vertices")
 
 
 class _Geo:
-    """Per-slot buffers of KittiInference3D, allocated once for the frame size.  `head`: 16 bytes of `count` (2 int64), then
-    the frame's maps back to back (disparity[, mask], depth; float32) -- one copy brings the maps AND the count to the host.
-    `vert`: the vertex records, room for the worst case of the frame."""
+    """Per-slot buffers of KittiInference3D beyond the frame's record, allocated once for the frame size: `vert`, the vertex
+    records with room for the worst case of the frame, on the device and pinned, and the offsets workspace of `ops.point_cloud`."""
 
     def __init__(self, device, crop_height, crop_width, stride):
         from . import ops
-        nbytes = 16 + 3 * crop_height * crop_width * 4
         cap = -(-crop_height // stride) * -(-crop_width // stride)
-        self.head_dev = torch.empty(nbytes, device=device, dtype=torch.uint8)
-        self.head_pin = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
         self.vert_dev = torch.empty((cap, 4), device=device, dtype=torch.float32)
         self.vert_pin = torch.empty((cap, 4), dtype=torch.float32).pin_memory()
         self.offsets = ops.point_cloud_workspace(crop_height, crop_width, device)[0]
-        self.count = self.head_dev[:16].view(torch.int64)
-        self.head_done = torch.cuda.Event()
-        self.copy = None             # the stream the head went out on: the vertices follow it there
-
-    def maps(self, buf, nmaps, rows, cols):
-        """the views of `nmaps` rows x cols float32 maps in a head buffer"""
-        fl = buf[16:].view(torch.float32)
-        return [fl[k * rows * cols:(k + 1) * rows * cols].view(rows, cols) for k in range(nmaps)]
 
 
 class KittiInference3D(KittiInference):
@@ -749,11 +725,17 @@ class KittiInference3D(KittiInference):
     row-major order, in the left camera's frame (`geometry.write_ply` stores it as it is).  All buffers of a frame in
     flight are allocated once per slot.  The read-back is one copy of the maps with the count in front, then -- once that
     count is on the host -- one copy of exactly count * 16 bytes of vertices: ONE more host wait per frame than the other
-    classes have, on that frame's own copy only; in `stream()` the later frames keep computing meanwhile.
+    classes have, on that frame's own copy only; in `stream()` the later frames keep computing meanwhile, and the vertex copy
+    of frame i goes onto the copy stream directly behind that frame's maps.
     `median=3 | 5` and `speckle=(max_size, max_diff)` (keywords, off by default) put the post-filter of
     KittiInferenceFiltered in front of the geometry stage: `disp` is then the filtered disparity, and the speckle filter's
     validity multiplies the mask exactly where `rectify`'s does -- a removed pixel gets depth 0 and no vertex (mask_min
     must be > 0).  With the defaults every result is byte for byte what it is without the keywords."""
+
+    # (`device_io` stays False here: this class has always asked for device_io=True to be written out)
+    needs_device_io = "the point colours are read from the uint8 image on the device"
+    has_uint16 = False
+    Frame = Frame3D
 
     def __init__(self, model, calib=None, *args, mask=None, mask_min: float = 0.5, min_disp: float = 0.0,
                  max_depth: float = 80.0, stride: int = 1, radius: int = 1, tau: float = 1.0, speckle=None, median: int = 0,
@@ -770,63 +752,45 @@ class KittiInference3D(KittiInference):
         if self.speckle is not None and not float(mask_min) > 0.0:
             raise ValueError("with speckle= the filter's validity (0 / 1) enters the mask: mask_min must be > 0")
         self._valid_frame = None     # rectify=: valid[0] placed in the frame, float32 (Hc,Wc), built once
-        if not self.device_io:
-            raise ValueError("KittiInference3D needs device_io=True: the point colours are read from the uint8 image on the device")
-        if mask not in (None, "confidence", "lr"):
-            raise ValueError(f"mask is None, 'confidence' or 'lr', got {mask!r}")
-        if int(stride) < 1 or int(radius) < 0:
-            raise ValueError("stride >= 1 and radius >= 0")
+        if int(stride) < 1:
+            raise ValueError("stride >= 1")
         frame_ops._geo_scalars("KittiInference3D", calib, mask_min, min_disp, max_depth)       # the operators' ranges, up front
-        self.calib, self.mask_mode = calib, mask
-        self.filters = dict(mask_min=float(mask_min), min_disp=float(min_disp), max_depth=float(max_depth))
-        self.stride, self.radius, self.tau = int(stride), int(radius), _check_tau(tau)
-        self.confidence = mask == "confidence"
-        self._mirrored = None
+        self._take_mask(mask, mask_min, radius, tau)
+        self.calib, self.stride = calib, int(stride)
+        self.filters = dict(mask_min=self.mask_min, min_disp=float(min_disp), max_depth=float(max_depth))
 
-    @property
-    def nmaps(self):
-        """the network's maps per frame: the disparity[, the mask]; the depth map follows them in the slot's buffer"""
-        return 1 if self.mask_mode is None else 2
-
-    def _frame_maps(self, left, right, cols):
-        if self.mask_mode == "lr":
-            disp, r = _lr_maps(self, left, right, cols, ("valid",))
-            return disp, r["valid"]
-        return super()._frame_maps(left, right, cols)
+    def _fields(self, rows, cols, as_uint16):
+        """16 bytes of `count` (2 int64), then the maps (disparity[, mask], depth): one copy brings the maps AND the count"""
+        maps = ("disp", "mask", "depth") if self.nmaps == 2 else ("disp", "depth")
+        return [("count", torch.int64, (2,))] + [(name, torch.float32, (rows, cols)) for name in maps]
 
     def _geo(self, s):
-        if getattr(s, "geo", None) is None:
-            s.geo = _Geo(s.device, self.crop_height, self.crop_width, self.stride)
-        return s.geo
+        return s.scratch("geo", lambda: _Geo(s.device, self.crop_height, self.crop_width, self.stride))
 
-    def _export(self, s, maps, as_uint16):
+    def _export(self, s, maps, out):
         from . import ops
         h, w, c, (src_y0, dst_y0, rows, cols), _ = s.meta
         g = self._geo(s)
         pred = maps[0].contiguous()
         mask = maps[1].contiguous() if len(maps) > 1 else None
-        views = g.maps(g.head_dev, len(maps) + 1, rows, cols)
-        for m, out in zip((pred, mask) if mask is not None else (pred,), views):
-            ops.disp_export(m, dst_y0, rows, cols, out_f32=out)
+        ops.disp_export(pred, dst_y0, rows, cols, out_f32=out["disp"])
+        if mask is not None:
+            ops.disp_export(mask, dst_y0, rows, cols, out_f32=out["mask"])
         window = (dst_y0, rows, cols)
         valid = None
         if self.rectify is not None:     # a pixel without a full source footprint is no measurement (the maps handed out stay as they are)
             valid = self._valid(pred.device, src_y0, dst_y0, rows, cols)
         if self.median or self.speckle is not None:
-            # the post-filter: the disparity handed out is the filtered one, and from here on the maps are the window's own
-            pred, kept, mask = _post_filter(self, s, pred, mask, window, self.filters["mask_min"], self.speckle, out_disp=views[0])
-            if kept is None:
-                views[0].copy_(pred)
-            else:                                    # a removed pixel is no measurement either: depth 0, no vertex
-                mask = kept if mask is None else mask * kept
-            window = (0, rows, cols)
+            # the disparity handed out is the filtered one; a removed pixel is no measurement either: depth 0, no vertex
+            # (mask_min > 0 is enforced with speckle=, so the fold always holds)
+            pred, mask, window = _post_filter(self, s, pred, mask, window, out["disp"], self.speckle, True)
             if valid is not None:
                 valid = valid[dst_y0:dst_y0 + rows, :cols].contiguous()
         if valid is not None:
             mask = valid.view_as(pred) if mask is None else mask * valid.view_as(pred)
-        ops.disp_to_depth(pred, self.calib, window, mask, out_f32=views[-1], **self.filters)
+        ops.disp_to_depth(pred, self.calib, window, mask, out_f32=out["depth"], **self.filters)
         ops.point_cloud(pred, self.calib, s.left, mask, window, v0=src_y0, stride=self.stride,
-                        out=g.vert_dev, workspace=(g.offsets, g.count), **self.filters)
+                        out=g.vert_dev, workspace=(g.offsets, out["count"]), **self.filters)
 
     def _valid(self, device, src_y0, dst_y0, rows, cols):
         """rectify.valid[0] as a float32 mask placed in the frame like the image; built once (the frame size is fixed)"""
@@ -836,55 +800,21 @@ class KittiInference3D(KittiInference):
             self._valid_frame = torch.from_numpy(frame).to(device)
         return self._valid_frame
 
-    def _readback(self, s, copy):
-        """`copy` stream: the count and the maps -> pinned, one copy"""
-        rows, cols = s.meta[3][2:]
-        g = self._geo(s)
-        n = 16 + (self.nmaps + 1) * rows * cols * 4
-        with torch.cuda.stream(copy):
-            copy.wait_event(s.computed)
-            g.head_pin[:n].copy_(g.head_dev[:n], non_blocking=True)
-            g.head_done.record(copy)
-        g.copy = copy
-
-    def _result(self, s):
-        """host: wait for the maps and the count, send exactly the written records after them, wait for those"""
+    def _rest(self, s, head):
+        """the vertex step: the count is on the host, so exactly the written records follow the maps on their copy stream;
+        the frame's second host wait is for them"""
         from .geometry import PLY_VERTEX
-        rows, cols = s.meta[3][2:]
         g = self._geo(s)
-        g.head_done.synchronize()
-        written = int(g.head_pin[:16].view(torch.int64)[1])
-        with torch.cuda.stream(g.copy):
+        written = int(head["count"][1])
+        with torch.cuda.stream(s.copy):
             if written:
                 g.vert_pin[:written].copy_(g.vert_dev[:written], non_blocking=True)
-            s.done.record(g.copy)
-        maps = [m.numpy().copy() for m in g.maps(g.head_pin, self.nmaps + 1, rows, cols)]
-        s.done.synchronize()
-        vertices = g.vert_pin[:written].numpy().view(PLY_VERTEX).reshape(-1).copy()
-        return Frame3D(maps[0], maps[1] if self.nmaps == 2 else None, maps[-1], vertices)
+            s.done.record(s.copy)
 
-    def stream(self, pairs, depth: int = 2):
-        """Generator of Frame3D tuples in input order, `depth` frames in flight, each equal byte for byte to the one-at-a-time
-        call.  The vertex copy of frame i goes onto the copy stream directly behind that frame's maps."""
-        return super().stream(pairs, depth, False)
-
-    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray) -> Frame3D:
-        return self._call_device(left_rgb, right_rgb, False)
-
-
-class _Color:
-    """Per-slot buffers of KittiInferenceColor, allocated once for the frame size: the float32 disparity of a rows x cols
-    window at byte 0, its uint8 RGB image behind it at byte 4 rows cols -- one copy brings both to the host."""
-
-    def __init__(self, device, crop_height, crop_width):
-        nbytes = 7 * crop_height * crop_width
-        self.dev = torch.empty(nbytes, device=device, dtype=torch.uint8)
-        self.pin = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
-
-    @staticmethod
-    def views(buf, rows, cols):
-        n = rows * cols
-        return buf[:4 * n].view(torch.float32).view(rows, cols), buf[4 * n:7 * n].view(rows, cols, 3)
+        def vertices():
+            s.done.synchronize()
+            return {"vertices": g.vert_pin[:written].numpy().view(PLY_VERTEX).reshape(-1).copy()}
+        return vertices
 
 
 class KittiInferenceColor(KittiInference):
@@ -902,18 +832,17 @@ class KittiInferenceColor(KittiInference):
     frame.  `median=3 | 5` and `speckle=(max_size, max_diff)` (keywords, off by default) run the
     post-filter of KittiInferenceFiltered first: `disp` is then the filtered disparity and a removed pixel is black."""
 
+    device_io = True
+    needs_device_io = "the map is coloured on the device, next to the disparity"
+    has_uint16 = False
+
     def __init__(self, model, *args, cmap: str = "kitti", max_disp=None, mask=None, mask_min: float = 0.5, radius: int = 1,
-                 tau: float = 1.0, device_io: bool = True, speckle=None, median: int = 0, **kwargs):
-        if len(args) < 5:                # (KittiInference takes device_io as its fifth positional argument)
-            kwargs["device_io"] = device_io
+                 tau: float = 1.0, speckle=None, median: int = 0, **kwargs):
         super().__init__(model, *args, **kwargs)
         self.median, self.speckle = _check_post(median, speckle)
-        if not self.device_io:
-            raise ValueError("KittiInferenceColor needs device_io=True: the map is coloured on the device, next to the disparity")
         if cmap not in ("kitti", "gray"):
             raise ValueError(f"cmap is 'kitti' or 'gray', got {cmap!r}")
-        if mask not in (None, "confidence", "lr"):
-            raise ValueError(f"mask is None, 'confidence' or 'lr', got {mask!r}")
+        self._take_mask(mask, mask_min, radius, tau)
         if max_disp is None:
             max_disp = getattr(self.net, "maxdisp", None)
             if max_disp is None:
@@ -922,75 +851,28 @@ class KittiInferenceColor(KittiInference):
             max_disp = float(max_disp)
             if not 0.0 < max_disp < float("inf"):
                 raise ValueError(f"max_disp is 'auto' or a positive, finite number, got {max_disp}")
-        if int(radius) < 0 or float(mask_min) != float(mask_min):
-            raise ValueError("radius >= 0 and mask_min must not be NaN")
-        self.cmap, self.max_disp, self.mask_mode, self.mask_min = cmap, max_disp, mask, float(mask_min)
-        self.radius, self.tau = int(radius), _check_tau(tau)
-        self.confidence = mask == "confidence"
-        self._mirrored = None
+        self.cmap, self.max_disp = cmap, max_disp
 
-    @property
-    def nmaps(self):
-        """the network's maps per frame: the disparity[, the mask]"""
-        return 1 if self.mask_mode is None else 2
+    def _fields(self, rows, cols, as_uint16):
+        """the float32 disparity, its uint8 RGB picture behind it at byte 4 rows cols: one copy brings both"""
+        return [("disp", torch.float32, (rows, cols)), ("rgb", torch.uint8, (rows, cols, 3))]
 
-    def _frame_maps(self, left, right, cols):
-        if self.mask_mode == "lr":
-            disp, r = _lr_maps(self, left, right, cols, ("valid",))
-            return disp, r["valid"]
-        return super()._frame_maps(left, right, cols)
-
-    def _color(self, s):
-        if getattr(s, "color", None) is None:
-            s.color = _Color(s.device, self.crop_height, self.crop_width)
-        return s.color
-
-    def _export(self, s, maps, as_uint16):
+    def _export(self, s, maps, out):
         from . import ops
-        dst_y0, rows, cols = s.meta[3][1:]
-        out_disp, out_rgb = _Color.views(self._color(s).dev, rows, cols)
+        y0, rows, cols = s.meta[3][1:]
         pred = maps[0].contiguous()
         mask = maps[1].contiguous().view_as(pred) if len(maps) > 1 else None
-        y0 = dst_y0
         if self.median or self.speckle is not None:
-            # the post-filter: the disparity handed out is the filtered one (a removed pixel is +0.0: black), and from here on
-            # the maps are the window's own
-            pred, kept, mask = _post_filter(self, s, pred, mask, (dst_y0, rows, cols), self.mask_min, self.speckle, out_disp=out_disp)
-            if kept is None:
-                out_disp.copy_(pred)
-            elif self.mask_min > 0.0:
-                mask = kept if mask is None else mask * kept
-            y0 = 0
+            # the disparity handed out is the filtered one (a removed pixel is +0.0: black).  With mask_min <= 0 the mask switches
+            # nothing off, so the filter's validity (0 / 1) must not enter it either
+            pred, mask, (y0, rows, cols) = _post_filter(self, s, pred, mask, (y0, rows, cols), out["disp"], self.speckle,
+                                                        self.mask_min > 0.0)
         else:
-            ops.disp_export(pred, dst_y0, rows, cols, out_f32=out_disp)
+            ops.disp_export(pred, y0, rows, cols, out_f32=out["disp"])
         scale = {"max_disp": self.max_disp}
         if self.max_disp == "auto":
             scale = {"range": ops.disp_range(pred, (y0, rows, cols), mask, self.mask_min)}
-        ops.disp_colorize(pred, y0, rows, cols, cmap=self.cmap, mask=mask, mask_min=self.mask_min, out=out_rgb, **scale)
-
-    def _readback(self, s, copy):
-        """`copy` stream: the disparity and the picture -> pinned, one copy"""
-        rows, cols = s.meta[3][2:]
-        c = self._color(s)
-        n = 7 * rows * cols
-        with torch.cuda.stream(copy):
-            copy.wait_event(s.computed)
-            c.pin[:n].copy_(c.dev[:n], non_blocking=True)
-            s.done.record(copy)
-
-    def _result(self, s):
-        rows, cols = s.meta[3][2:]
-        s.done.synchronize()
-        disp, rgb = _Color.views(self._color(s).pin, rows, cols)
-        return disp.numpy().copy(), rgb.numpy().copy()
-
-    def stream(self, pairs, depth: int = 2):
-        """Generator of (disp, rgb) tuples in input order, `depth` frames in flight, each equal byte for byte to the
-        one-at-a-time call."""
-        return super().stream(pairs, depth, False)
-
-    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray):
-        return self._call_device(left_rgb, right_rgb, False)
+        ops.disp_colorize(pred, y0, rows, cols, cmap=self.cmap, mask=mask, mask_min=self.mask_min, out=out["rgb"], **scale)
 
 
 def color_png(path: str, rgb: np.ndarray) -> None:

@@ -159,8 +159,13 @@ def test_host_path_is_the_default_and_keeps_its_signature():
     import inspect
     from dcanet_amd.inference import KittiInference
     sig = inspect.signature(KittiInference.__init__)
-    assert list(sig.parameters)[1:] == ["model", "crop_height", "crop_width", "graph", "dtype", "device_io"]
-    assert sig.parameters["device_io"].default is False
+    positional = [k for k, p in sig.parameters.items() if p.kind is p.POSITIONAL_OR_KEYWORD]
+    assert positional[1:] == ["model", "crop_height", "crop_width", "graph", "dtype", "device_io"]
+    assert [k for k in sig.parameters if k not in positional] == ["rectify"]       # keyword-only, None: no rectification
+    assert sig.parameters["rectify"].kind is inspect.Parameter.KEYWORD_ONLY and sig.parameters["rectify"].default is None
+    # device_io=None stands for the class's own default, which is the host path here
+    assert sig.parameters["device_io"].default is None and KittiInference.device_io is False
     infer = KittiInference(torch.nn.Linear(1, 1))
+    assert infer.device_io is False and KittiInference(torch.nn.Linear(1, 1), 384, 1248, True, None, True).device_io is True
     with pytest.raises(RuntimeError, match="device_io=True"):
         next(infer.stream([]))

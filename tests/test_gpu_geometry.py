@@ -11,7 +11,7 @@ import torch
 
 from _geometry_reference import (CALIB, MASK_MIN, MAX_DEPTH, MIN_DISP, SHAPES, TILE, V0, VERTEX, Y0, Calib,
                                  geometry_reference, scene)
-from oracle import dcanet_oracle as O
+from _inference_cases import lr_tau as _lr_tau, model as _model, pairs as _pairs
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -277,43 +277,8 @@ def test_geometry_replays_from_a_hipgraph():
 
 
 # ---- through the wrapper ---------------------------------------------------------------------------------------------------
-_MODEL = []
 WRAP_CALIB = Calib(40.0, float(np.float32(40.0 * 0.5)), 31.5, 15.5, 0.0)
 WRAP = dict(crop_height=32, crop_width=64, graph=True, device_io=True)
-
-
-def _model():
-    """one seeded GwcNet(32) for the whole module, never modified (eval mode, no grad)"""
-    if not _MODEL:
-        from dcanet_amd.models.gwcnet_dca_g import GwcNet
-        m = GwcNet(32, use_concat_volume=False)
-        m.load_state_dict(O.seeded_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}), strict=True)
-        _MODEL.append(m.to(DEV).eval())
-    return _MODEL[0]
-
-
-def _pairs(rng, sizes):
-    return [(rng.integers(0, 256, (h, w, 3), dtype=np.uint8), rng.integers(0, 256, (h, w, 3), dtype=np.uint8))
-            for h, w in sizes]
-
-
-def _lr_tau(plain, left_rgb, right_rgb):
-    """a threshold under which most in-view pixels of this pair pass the cross-check: the 60th percentile of the
-    differences of the whole window (out-of-view pixels are +inf), so that the MEDIAN of the validity map is 1"""
-    from dcanet_amd import ops
-    from dcanet_amd.inference import placement
-    h, w = left_rgb.shape[:2]
-    l8, r8 = dev(left_rgb), dev(right_rgb)
-    with torch.no_grad():
-        lut, _ = ops.frame_lut(ops.frame_histogram(l8, r8), h * w)
-        fl, fr = ops.frame_apply(l8, r8, lut, (32, 64), *placement(h, w, 32, 64))
-        disp = plain.forward_frame(fl, fr).clone()
-        disp_m = plain.forward_frame(*ops.mirror_pair(fl.contiguous(), fr.contiguous())).clone()
-        diff = ops.lr_consistency(disp, disp_m, 0.0, w, outputs=("diff",))["diff"]
-    diff = np.sort(diff[0, 0, 32 - h:, :w].cpu().numpy().reshape(-1))
-    tau = float(diff[int(0.6 * diff.size)])
-    assert np.isfinite(tau), f"only {int(np.isfinite(diff).sum())} of {diff.size} pixels are in view"
-    return tau
 
 
 @pytest.mark.parametrize("mode", [None, "confidence", "lr"])

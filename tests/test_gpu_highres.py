@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 import torch
 
+from _inference_cases import model as _model
 from dcanet_amd.highres import (area_downscale_disp_host, area_downscale_pair_host, device_tables, guided_upsample_host,
                                 jbu_tables)
-from oracle import dcanet_oracle as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -331,18 +331,7 @@ def test_wrappers_refuse_by_name_before_the_library(op, what, change, monkeypatc
 
 
 # ---- through the wrappers ---------------------------------------------------------------------------------------------------
-_MODEL = []
 WRAP = dict(crop_height=32, crop_width=64, graph=True, device_io=True)
-
-
-def _model():
-    """one seeded GwcNet(32) for the whole module, never modified (eval mode, no grad)"""
-    if not _MODEL:
-        from dcanet_amd.models.gwcnet_dca_g import GwcNet
-        m = GwcNet(32, use_concat_volume=False)
-        m.load_state_dict(O.seeded_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}), strict=True)
-        _MODEL.append(m.to(DEV).eval())
-    return _MODEL[0]
 
 
 @pytest.mark.parametrize("mode", [None, "confidence", "lr"])

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from _inference_cases import pairs as _pairs
 from _lr_reference import SHAPES, lr_reference, scene
 from oracle import dcanet_oracle as O
 from oracle.seeded import seeded_tensor
@@ -227,11 +228,6 @@ def test_predict_lr(concat, monkeypatch):
 
 
 # ---- through the wrapper ---------------------------------------------------------------------------------------------------
-def _pairs(rng, sizes):
-    return [(rng.integers(0, 256, (h, w, 3), dtype=np.uint8), rng.integers(0, 256, (h, w, 3), dtype=np.uint8))
-            for h, w in sizes]
-
-
 def _frames(plain, left_rgb, right_rgb):
     """the float32 frames KittiInference hands its network, built the way it builds them"""
     from dcanet_amd import ops

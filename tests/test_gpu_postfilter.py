@@ -9,9 +9,9 @@ import numpy as np
 import pytest
 import torch
 
+from _inference_cases import lr_tau as _lr_tau, model as _model, pairs as _pairs
 from _postfilter_cases import flipped, median_cases, speckle_cases
 from dcanet_amd.postfilter import median_filter_host, speckle_filter_host
-from oracle import dcanet_oracle as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -157,42 +157,7 @@ def test_postfilter_operators_refuse_what_they_cannot_do():
 
 
 # ---- through the wrappers ---------------------------------------------------------------------------------------------------
-_MODEL = []
 WRAP = dict(crop_height=32, crop_width=64, graph=True, device_io=True)
-
-
-def _model():
-    """one seeded GwcNet(32) for the whole module, never modified (eval mode, no grad)"""
-    if not _MODEL:
-        from dcanet_amd.models.gwcnet_dca_g import GwcNet
-        m = GwcNet(32, use_concat_volume=False)
-        m.load_state_dict(O.seeded_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}), strict=True)
-        _MODEL.append(m.to(DEV).eval())
-    return _MODEL[0]
-
-
-def _pairs(rng, sizes):
-    return [(rng.integers(0, 256, (h, w, 3), dtype=np.uint8), rng.integers(0, 256, (h, w, 3), dtype=np.uint8))
-            for h, w in sizes]
-
-
-def _lr_tau(plain, left_rgb, right_rgb):
-    """a threshold under which most in-view pixels of this pair pass the cross-check: the 60th percentile of the
-    differences of the whole window (out-of-view pixels are +inf)"""
-    from dcanet_amd import ops
-    from dcanet_amd.inference import placement
-    h, w = left_rgb.shape[:2]
-    l8, r8 = dev(left_rgb), dev(right_rgb)
-    with torch.no_grad():
-        lut, _ = ops.frame_lut(ops.frame_histogram(l8, r8), h * w)
-        fl, fr = ops.frame_apply(l8, r8, lut, (32, 64), *placement(h, w, 32, 64))
-        disp = plain.forward_frame(fl, fr).clone()
-        disp_m = plain.forward_frame(*ops.mirror_pair(fl.contiguous(), fr.contiguous())).clone()
-        diff = ops.lr_consistency(disp, disp_m, 0.0, w, outputs=("diff",))["diff"]
-    diff = np.sort(diff[0, 0, 32 - h:, :w].cpu().numpy().reshape(-1))
-    tau = float(diff[int(0.6 * diff.size)])
-    assert np.isfinite(tau), f"only {int(np.isfinite(diff).sum())} of {diff.size} pixels are in view"
-    return tau
 
 
 def _split(disp, mask, mask_min, median):
