@@ -8,7 +8,7 @@
 //
 // All tensors are NC[D]HW fp32: channel c owns contiguous runs of S = D*H*W floats per sample, so
 // every kernel streams 16 B per lane along S.
-#include "dca_frag.h"
+#include "bn_math.h"
 #include "../../include/dca_hip.h"
 
 // ------------------------------------------------------------------------------------ BN statistics
@@ -165,20 +165,11 @@ __global__ __launch_bounds__(64) void bn_finalize_centered_kernel(const double* 
 // the way: block (chunk ch, channel c) stores its maximum into slot [c][ch] (nchunk <= DCA_AMAX_CSLOTS), or they write the
 // operand in the packed px2 format directly (the *_pack kernels), scaled by exponents the finalize kernels derive from bounds.
 
-// scale*y + shift of every apply and backward kernel below: ONE rounding, written as an explicit fma so that no two kernels (and
-// no two forms of one kernel) can contract it differently.
-__device__ __forceinline__ float bn_affine(float y, float sc, float sh) { return __fmaf_rn(y, sc, sh); }
+// (bn_affine, bn_bwd_acc, px2_split: bn_math.h)
 // What bn_apply_kernel writes for a slope-1 BatchNorm without residuals: the value of the folded skip branch, which the
 // *_pack and backward kernels form in registers from (y_r, stats_r) instead of reading it as res_pre -- same bits, so the
 // output and the ReLU mask of the backward pass are those of the route that stores it.
 __device__ __forceinline__ float bn_skip(float y, float sc, float sh) { return act_apply(bn_affine(y, sc, sh), 1.f); }
-// One element's terms of the backward sums (sum g, sum g*xhat).  Not contracted: every reduction over the same (g, y, stats)
-// -- bn_bwd_reduce_kernel's own pair and the second pair it forms for a folded skip BatchNorm -- rounds alike.
-__device__ __forceinline__ void bn_bwd_acc(float g, float y, float mean, float invstd, float& a0, float& a1) {
-#pragma clang fp contract(off)
-  a0 += g;
-  a1 += g * (y - mean) * invstd;
-}
 
 // z = act(scale[c]*y + shift[c] + res_pre) + res_post.  Block (ch, c): chunk ch of channel c, all samples.
 // zmax / ymax (may be null): per-channel slots that receive max |z| and max |y - mean| (the latter bounds |xhat| for the
@@ -221,15 +212,6 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
   if (zmax) dca_cmax_put(am, zmax + (long)c * DCA_AMAX_CSLOTS + ch);
   if (ymax) dca_cmax_put(ym, ymax + (long)c * DCA_AMAX_CSLOTS + ch);
 }
-
-// the two f16 terms of the f16x2 kernels (x2_split) as 16-bit patterns
-__device__ __forceinline__ void px2_split(float v, int e, unsigned short& h, unsigned short& l) {
-  _Float16 hh, ll;
-  x2_split(v, e, hh, ll);
-  h = __builtin_bit_cast(unsigned short, hh);
-  l = __builtin_bit_cast(unsigned short, ll);
-}
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
 // The same BatchNorm apply (no residuals) writing z in the packed px2 operand format (dca_common.h) for the f16x2
 // convolution that consumes it: block (ch, cg) = chunk ch of the 8-channel group cg, all samples; a lane takes ONE voxel and
@@ -1245,6 +1227,18 @@ extern "C" int dca_bn_backward_reduce(const float* dz, const float* y, const flo
                      (double*)nullptr);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, stream, part, nchunk, (double)N * (double)S, dgb, C,
                      stats, training, (const unsigned*)nullptr, (const unsigned*)nullptr, 0, (int*)nullptr);
+  return dca_launch_status();
+}
+
+// the chunking of bn_bwd_reduce_kernel and the finalize launch for a reduce pass that lives in another file and keeps that
+// kernel's summation order (bn_math.h; conv3d_c1.hip: dca_bn_backward_pack_c1)
+void dca_internal_bn_chunking(long S, int C, int* nchunk, long* chunk_len) { chunking(S, C, nchunk, chunk_len); }
+
+int dca_internal_bn_bwd_finalize(const double* part, int nchunk, double count, float* dgb, int C, const float* stats,
+                                 int training, const unsigned* gmax, const unsigned* ymax, int ymax_slots, int* dyexps,
+                                 hipStream_t stream) {
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, stream, part, nchunk, count, dgb, C, stats, training, gmax,
+                     ymax, ymax_slots, dyexps);
   return dca_launch_status();
 }
 

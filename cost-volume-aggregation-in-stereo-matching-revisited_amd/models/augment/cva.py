@@ -65,13 +65,14 @@ class _Classify(nn.Sequential):
 
     def forward(self, x, alias=False):
         """alias=True: returns (logits, x') with x' = x for the other consumers of x (ops._Conv3d.forward, `alias`)"""
+        # (h is read by the head alone: in training its gradient is formed inside the BatchNorm's backward, ops.conv3d)
         if alias:
             h, xa = self[0](x, slope=0.0, alias=True)
-            return conv3d_plain(h, self[2]), xa
+            return conv3d_plain(h, self[2], sole_reader=True), xa
         h = self[0](x, slope=0.0)
         if h.dtype != torch.float32:            # reduced-precision inference: 2-byte features, fp32 logits
             return ops.conv3d_c1_lp(h, self[2].weight)
-        return conv3d_plain(h, self[2])
+        return conv3d_plain(h, self[2], sole_reader=True)
 
 
 class cva(nn.Module):

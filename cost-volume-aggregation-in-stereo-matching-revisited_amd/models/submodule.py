@@ -72,9 +72,9 @@ class ConvBnReLU3d(nn.Sequential):
         return self[0](x, slope=0.0)
 
 
-def conv3d_plain(x, conv):
-    """nn.Conv3d(32, 1, 3, padding=1, bias=False) heads (classifiers)."""
-    return ops.conv3d(x, conv.weight, conv.stride[0], False)
+def conv3d_plain(x, conv, sole_reader=False):
+    """nn.Conv3d(32, 1, 3, padding=1, bias=False) heads (classifiers).  sole_reader: nothing else reads x (ops.conv3d)."""
+    return ops.conv3d(x, conv.weight, conv.stride[0], False, sole_reader=sole_reader)
 
 
 # ------------------------------------------------------------------ 2D neighbours of the path (PyTorch)

@@ -285,6 +285,7 @@ CONV_S2_X2 = os.environ.get("DCA_CONV_S2", "x2") != "fp32"     # the stride-2 co
 BN_FUSE = os.environ.get("DCA_BN_FUSE", "1") != "0"        # BatchNorm batch statistics from the conv epilogue (training)   # the transposed-convolution member of the family alone (A/B timing)
 C1_BWD_FUSE = os.environ.get("DCA_C1_BWD", "fused") != "split"      # 1x1x1 conv + BatchNorm backward as one launch (A/B)
 SKIP_FOLD = os.environ.get("DCA_SKIP_FOLD", "1") != "0"    # cva skip BatchNorm folded into the block's output BatchNorm (A/B)
+C1_HEAD_BWD = os.environ.get("DCA_C1_HEAD_BWD", "fused") != "split"  # logit heads: backward-data inside the BatchNorm backward (A/B)
 _X3_MIN_WORKGROUPS = 1
 
 
@@ -517,6 +518,31 @@ def _c1_bwd_fused(dz, x, x2, weight):
                                  _ptr(weight), _ptr(part), _ptr(gx), _ptr(gx2), _ptr(gw), C1 + C2, 1, N, C1, C2,
                                  weight.shape[0], S, _stream()), "dca_conv1_bwd_fused")
     return gx, gx2, gw
+
+
+def _c1_head_bwd_route(h, weight, sole_reader):
+    """how the backward of a logit head Conv3d(32, 1, 3) over h = relu(BN(y)) runs -- "fused" (conv3d_c1.hip,
+    dca_bn_backward_pack_c1: the head's backward does its weight gradient only and hands (dlogit, weight) on in place of the
+    gradient of h, the BatchNorm's two backward passes form that gradient in registers; it is never a tensor) or "split" (the head
+    writes the gradient of h with dca_conv3d_c1_bwd_data, the BatchNorm reads it twice).  Asked once, in the forward, by `conv3d`
+    when h exists: h.grad_fn is the BatchNorm's node, which is told the answer there.  sole_reader: the caller's promise that
+    nothing but this head reads h -- any other reader's gradient would have to be added to a tensor that does not exist (a
+    broken promise raises in the BatchNorm's backward, where the hand-off arrives without its tag)."""
+    if not (C1_HEAD_BWD and sole_reader and torch.is_grad_enabled()):
+        return "split"
+    node = h.grad_fn
+    if not isinstance(node, _BnAct._backward_cls) or getattr(node, "meta", None) is None:
+        return "split"
+    training, slope, has_pre, has_post, pack_dy, _ = node.meta
+    if not (training and pack_dy and float(slope) == 0.0) or has_pre or has_post:
+        return "split"
+    if tuple(weight.shape) != (1, 32, 3, 3, 3) or h.dim() != 5 or h.shape[1] != 32 or h.shape[-1] % 4:
+        return "split"
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.requires_grad for t in (h, weight)):
+        return "split"
+    if _is_packed(h) or h.data_ptr() % 16 or not h.is_contiguous() or h[0].numel() * 4 >= 0x7ffffff0:
+        return "split"      # (y has h's layout and comes from the same allocator: _BnAct.forward, torch.empty_like)
+    return "fused"
 
 
 class _SkipBn:
@@ -799,8 +825,11 @@ class _Conv3dC1(torch.autograd.Function):
     weight gradient run on the 1x1x1 matrix-core kernels (see include/dca_hip.h); C must be 32 or 64."""
 
     @staticmethod
-    def forward(ctx, x, weight):
+    def forward(ctx, x, weight, head_fused=False):
+        """head_fused: _c1_head_bwd_route answered "fused" (conv3d): backward hands (dy, weight) to the BatchNorm that produced
+        x instead of writing the gradient of x"""
         x, weight = _req(x, "conv3d"), _req(weight, "conv3d.weight")
+        ctx.head_fused = bool(head_fused)
         N, C, D, H, W = x.shape
         with torch.cuda.device_of(x):
             T = _conv_sliced(x, None, weight, C, 27, 1, 1, 0, 1, 1, False)      # wt[ci][tap] = w[0, ci, tap]; (N,27,D,H,W)
@@ -817,7 +846,12 @@ class _Conv3dC1(torch.autograd.Function):
         gx = gw = None
         lib = _L()
         with torch.cuda.device_of(x):
-            if ctx.needs_input_grad[0]:
+            if ctx.head_fused:
+                # no tensor for the gradient of x: a view of dy with x's shape (no memory of its own) carries what the
+                # BatchNorm's backward needs to form it (_BnAct.backward, dca_bn_backward_pack_c1)
+                gx = dy.expand(N, C, D, H, W)
+                gx._dca_head = (dy, weight)
+            elif ctx.needs_input_grad[0]:
                 gx = torch.empty_like(x)
                 _chk(lib.dca_conv3d_c1_bwd_data(_ptr(dy), _ptr(weight), _ptr(gx), N, C, D, H, W, _stream()),
                      "dca_conv3d_c1_bwd_data")
@@ -834,7 +868,7 @@ class _Conv3dC1(torch.autograd.Function):
                     G = torch.empty((N, 27, D, H, W), device=x.device, dtype=torch.float32)
                     _chk(lib.dca_conv3d_c1_expand(_ptr(dy), _ptr(G), N, D, H, W, _stream()), "dca_conv3d_c1_expand")
                     _wgrad(x, G, gw, 0, C, 27, 1, 1, 1, 27)                      # dw[ci*27 + tap]
-        return gx, gw
+        return gx, gw, None
 
 
 class _Conv3d(torch.autograd.Function):
@@ -1028,8 +1062,13 @@ def convbn3d_pair(x, conv_a, bn_a, slope_a, conv_b, bn_b, slope_b, pack_a=False,
     return za, zb
 
 
-def conv3d(x, weight, stride=1, transposed=False, x2=None):
+def conv3d(x, weight, stride=1, transposed=False, x2=None, sole_reader=False):
+    """sole_reader (logit heads): the caller promises that x, the output of a `convbn3d`, is read by nothing but this
+    convolution (_c1_head_bwd_route)"""
     if _k3s1(weight, stride, transposed, x2, head=True) and weight.shape[1] in (32, 64):
+        if _c1_head_bwd_route(x, weight, sole_reader) == "fused":
+            x.grad_fn.head_fused = True          # the BatchNorm's node: its backward takes the head's hand-off
+            return _Conv3dC1.apply(x, weight, True)
         return _Conv3dC1.apply(x, weight)
     return _Conv3d.apply(x, x2, weight, int(stride), bool(transposed))
 
@@ -1141,6 +1180,8 @@ class _BnAct(torch.autograd.Function):
     def backward(ctx, dz):
         y, stats, res_pre, ymax = ctx.saved_tensors
         training, slope, has_pre, has_post, pack_dy, ymax_slots = ctx.meta
+        if getattr(ctx, "head_fused", False):
+            return _BnAct._backward_head(ctx, dz)
         dz = _req(dz, "batch_norm.backward")
         N, C = y.shape[0], y.shape[1]
         S = y[0, 0].numel()
@@ -1179,6 +1220,35 @@ class _BnAct(torch.autograd.Function):
             g_pre = g_out if g_out is not None else dz
         g_post = dz if (has_post and ctx.needs_input_grad[10]) else None
         return dy, dgb[:C], dgb[C:2 * C], None, None, None, None, None, None, g_pre, g_post, None, None, None, None, None
+
+    @staticmethod
+    def _backward_head(ctx, dz):
+        """backward of the BatchNorm in front of a logit head on the fused route (_c1_head_bwd_route; training, pack_dy, ReLU,
+        no residuals): dz is not data but the head's hand-off (dlogit, weight), and the two passes form the gradient from it"""
+        y, stats, _, ymax = ctx.saved_tensors
+        training, slope, _, _, _, ymax_slots = ctx.meta
+        tag = getattr(dz, "_dca_head", None)
+        if tag is None:
+            raise RuntimeError("batch_norm.backward: expected the hand-off of the logit head behind this BatchNorm (its output "
+                               "has another reader besides the head, or the tag was lost on the way through autograd)")
+        dlogit, w_head = tag
+        N, C, D, H, W = y.shape
+        if dlogit.shape != (N, 1, D, H, W) or dz.shape != y.shape:
+            raise RuntimeError("batch_norm.backward: the head's hand-off does not belong to this BatchNorm")
+        lib = _L()
+        with torch.cuda.device_of(y):
+            nchunk = lib.dca_bn_backward_pack_c1_chunks(N, D, H, W)
+            part = torch.empty((C * nchunk * 2,), device=y.device, dtype=torch.float64)
+            dgb = torch.empty((4 * C,), device=y.device, dtype=torch.float32)
+            dyexps = torch.empty((C,), device=y.device, dtype=torch.int32)
+            gmax = torch.empty((C * CSLOTS,), device=y.device, dtype=torch.int32)
+            dy = torch.empty_like(y)
+            _chk(lib.dca_bn_backward_pack_c1(_ptr(dlogit), _ptr(w_head), _ptr(y), _ptr(stats), _ptr(part), _ptr(dgb), _ptr(dy),
+                                             _ptr(dyexps), _ptr(gmax), _ptr(ymax), ymax_slots if ymax is not None else 0,
+                                             N, C, D, H, W, float(slope), int(training), _stream()),
+                 "dca_bn_backward_pack_c1")
+            _tag_px2(dy, dyexps)
+        return dy, dgb[:C], dgb[C:2 * C], None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 class _BnSkipAct(torch.autograd.Function):

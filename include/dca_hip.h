@@ -343,6 +343,20 @@ int dca_bn_backward_reduce(const float* dz, const float* y, const float* stats, 
 int dca_bn_backward_pack(const float* dz, const float* y, const float* stats, double* part, float* dgb, void* dyp,
                          int* dyexps, unsigned* gmax, const unsigned* ymax, int ymax_slots, int N, int C, long S,
                          float slope, int training, hipStream_t stream);
+/* dca_bn_backward_pack for the BatchNorm in front of a logit head (ConvBn3d -> ReLU -> Conv3d(C, 1, 3)), with the head's
+ * backward-data folded in: dz = the gradient of the head's input is never a tensor, both passes form it from the head's
+ * 1-channel output gradient dlogit (N,1,D,H,W) and weight w_head (1,C,3,3,3) -- the 27-tap stencil of
+ * dca_conv3d_c1_bwd_data, same rounding -- while they stream y.  No dca_conv3d_c1_bwd_data launch, no write and no
+ * two reads of a (N,C,D,H,W) tensor.  Every output is, bit for bit, what dca_conv3d_c1_bwd_data + dca_bn_backward_pack give:
+ * the reduce pass keeps that entry's chunks and per-lane summation order.  C == 32, W % 4 == 0, 16-byte aligned dlogit / y /
+ * dyp, C*D*H*W*4 < 2^31 (hipErrorInvalidValue otherwise: use the two entries).  part = C * dca_bn_backward_pack_c1_chunks(N, D,
+ * H, W) * 2 doubles (= dca_bn_num_chunks(32, D*H*W) chunks); dca_bn_backward_pack_c1_grid: the persistent workgroups of the
+ * apply pass (4 x 8 x 32 tiles; for tests); the other arguments as dca_bn_backward_pack. */
+int dca_bn_backward_pack_c1_chunks(int N, int D, int H, int W);
+int dca_bn_backward_pack_c1_grid(int N, int D, int H, int W);
+int dca_bn_backward_pack_c1(const float* dlogit, const float* w_head, const float* y, const float* stats, double* part,
+                            float* dgb, void* dyp, int* dyexps, unsigned* gmax, const unsigned* ymax, int ymax_slots, int N,
+                            int C, int D, int H, int W, float slope, int training, hipStream_t stream);
 /* The output BatchNorm of a block whose pre-activation residual is ITSELF a slope-1 BatchNorm without residuals over batch
  * statistics (models/augment/cva.py:26-31: relu(BN_d(deconv) + BN_r(redir))), with that skip BatchNorm folded in: the
  * residual is never stored, every kernel forms res_pre = fma(y_r, scale_r, shift_r) in registers from the skip's input y_r
