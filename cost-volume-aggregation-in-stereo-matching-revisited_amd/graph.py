@@ -15,13 +15,17 @@ class GraphedHotPath:
     the same shapes to replay.  Returns the dict of outputs (static buffers: clone them if they must outlive the
     next call)."""
 
-    def __init__(self, model, *example_inputs, warmup: int = 2, **hot_path_kwargs):
+    def __init__(self, model, *example_inputs, warmup: int = 2, hints4=None, **hot_path_kwargs):
         """example_inputs: the arguments of `model.hot_path` -- tensors, or tuples of tensors (the extractor's l2 / l3 /
         l4 segments), or None.  hot_path_kwargs: keywords handed to every `model.hot_path` call as they are (e.g.
-        confidence=1); they are part of what is captured."""
+        confidence=1); they are part of what is captured.  hints4: a tensor makes the guided hot path the captured one and
+        the hint map one more static input: every call then takes `hints4=` and copies it in."""
         assert not model.training, "graph capture is for the eval path (training BN updates buffers)"
         self.model = model
         self.static_in = [_tree(t, lambda u: u.detach().clone()) for t in example_inputs]
+        self.static_hints4 = None if hints4 is None else hints4.detach().clone()
+        if hints4 is not None:
+            hot_path_kwargs = dict(hot_path_kwargs, hints4=self.static_hints4)
         stream = torch.cuda.Stream()
         stream.wait_stream(torch.cuda.current_stream())
         with torch.no_grad(), torch.cuda.stream(stream):
@@ -32,9 +36,12 @@ class GraphedHotPath:
         with torch.no_grad(), torch.cuda.graph(self.graph):
             self.static_out = model.hot_path(*self.static_in, **hot_path_kwargs)
 
-    def __call__(self, *inputs):
+    def __call__(self, *inputs, hints4=None):
+        assert (hints4 is None) == (self.static_hints4 is None), "hints4 is given iff the graph was captured with one"
         for s, t in zip(self.static_in, inputs):
             _tree2(s, t, _copy_checked)
+        if hints4 is not None:
+            _copy_checked(self.static_hints4, hints4)
         self.graph.replay()
         return self.static_out
 

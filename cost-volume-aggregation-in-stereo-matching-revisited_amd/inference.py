@@ -35,6 +35,7 @@ import numpy as np
 import torch
 
 from .geometry import depth_png, rectify_pair_host  # noqa: F401  (depth_png: the depth exporter, next to disparity_png)
+from .geometry import LidarCalib, LidarProjector
 from .graph import GraphedHotPath
 
 
@@ -275,14 +276,16 @@ class KittiInference:
         import contextlib
         from . import ops
         kwargs = {"confidence": self.radius} if self.confidence else {}      # the statistics launch is part of the graph
+        kwargs.update(self._hot_kwargs())
+        live = self._hot_inputs()
         ctx = ops.reduced_precision(self.dtype) if self.dtype is not None else contextlib.nullcontext()
         with ctx:      # (a replay needs no context: the captured launches are already the reduced-precision kernels)
             if self.graph:
                 if self._graphed is None:
-                    self._graphed = GraphedHotPath(net, *args, **kwargs)
-                r = self._graphed(*args)
+                    self._graphed = GraphedHotPath(net, *args, **kwargs, **live)
+                r = self._graphed(*args, **live)
             else:
-                r = net.hot_path(*args, **kwargs)
+                r = net.hot_path(*args, **kwargs, **live)
         if not self.confidence:
             return net.prop(guidance, r["pred4_q"])
         # the leading planes of the statistics as they lie in memory (disparity, unimodal disparity, window mass): one
@@ -309,6 +312,14 @@ class KittiInference:
             return disp, r["valid"]
         maps = self.forward_frame(left, right)
         return maps if self.confidence else (maps,)
+
+    def _hot_kwargs(self):
+        """further keywords of `hot_path` that are settings: part of what a graph captures"""
+        return {}
+
+    def _hot_inputs(self):
+        """further keywords of `hot_path` that are tensors of the frame: static inputs of the graph, copied in at every call"""
+        return {}
 
     def _net_hw(self, h, w):
         """the size at which an h x w image (rectified, with rectify=) enters the network's frame (HighResInference: smaller)"""
@@ -415,11 +426,11 @@ class KittiInference:
             return self.Frame(*(out.get(name) for name in self.Frame._fields))
         return tuple(out.values()) if len(out) > 1 else out["disp"]
 
-    def _call_device(self, left_rgb, right_rgb, as_uint16):
+    def _call_device(self, left_rgb, right_rgb, as_uint16, *more):
         dev = next(self.net.parameters()).device
         cur = torch.cuda.current_stream(dev)
         s = self._slot(0)
-        self._upload(s, left_rgb, right_rgb, cur)
+        self._upload(s, left_rgb, right_rgb, cur, *more)
         self._compute(s, cur, as_uint16)
         self._readback(s, cur)
         return self._result(s)
@@ -446,14 +457,14 @@ class KittiInference:
         copy.wait_stream(compute)
         inflight = collections.deque()               # slots in input order; [slot, read-back enqueued]
         try:
-            for i, (left_rgb, right_rgb) in enumerate(pairs):
+            for i, (left_rgb, right_rgb, *more) in enumerate(pairs):      # (more: what a subclass's `_upload` takes per frame)
                 if len(inflight) == depth:               # slot i % depth is the oldest frame's: hand that frame out first
                     old = inflight.popleft()
                     if not old[1]:
                         self._readback(old[0], copy)
                     yield self._result(old[0])
                 s = self._slot(i % depth)
-                self._upload(s, left_rgb, right_rgb, copy)
+                self._upload(s, left_rgb, right_rgb, copy, *more)
                 self._compute(s, compute, as_uint16)
                 # the read-back of the frame before goes behind this upload on the copy stream: it waits for that frame's
                 # compute, and an upload queued behind it would wait too
@@ -522,6 +533,99 @@ class KittiInferenceLR(KittiInference):
         """its own case: the FILLED disparity (the classes behind a mask mode take the unfilled one)"""
         _, r = self._lr_maps(left, right, cols, ("valid", "filled"))
         return r["filled"], r["valid"]
+
+
+class KittiInferenceGuided(KittiInference):
+    """`disp = KittiInferenceGuided(model, ...)(left_rgb, right_rgb, hints)`: KittiInference (device I/O; eager or graph, fp32
+    or reduced precision, rectify=) whose network is guided by sparse disparity hints: `__call__` and
+    `stream(triples)` take a third item per frame.
+      lidar=None               the (h,w) float32 hint map of the image (the rectified image, with rectify=): a disparity in
+                               pixels, +0.0 where nothing was measured; a numpy array (uploaded beside the pair) or a tensor
+                               on the device (read on the current stream)
+      lidar=geometry.LidarCalib   the (N,4) float32 scan: staged through a `geometry.LidarProjector` and projected with
+                               `ops.lidar_disparity` (hw of the calibration = the image's size)
+    `ops.hints_to_quarter` writes the frame's hints through the frame's placement into ONE buffer the instance owns, and
+    `forward_frame` hands it to the (graphed) hot path: no allocation per frame.  guide = (k, c) of `ops.cost_volume`.  The
+    record handed out is KittiInference's.  Not combined with the other subclasses."""
+
+    device_io = True
+    needs_device_io = "the hints are brought to the network's frame on the device"
+
+    def __init__(self, model, *args, lidar=None, guide=(10.0, 1.0), **kwargs):
+        super().__init__(model, *args, **kwargs)
+        from .guided import guide_params
+        guide_params("KittiInferenceGuided", guide)
+        if lidar is not None and not isinstance(lidar, LidarCalib):
+            raise TypeError(f"lidar= must be a geometry.LidarCalib, got {type(lidar)}")
+        if self.crop_height % 4 or self.crop_width % 4:
+            raise ValueError("KittiInferenceGuided: the frame must be a multiple of 4 in both directions")
+        self.lidar, self.guide = lidar, (float(guide[0]), float(guide[1]))
+        self._proj = None            # the LidarProjector, built with the first scan
+        self.hints4 = None           # (1,Hc/4,Wc/4): the frame's hints, rewritten whole by every frame
+
+    def _hot_kwargs(self):
+        return {"guide": self.guide}
+
+    def _hot_inputs(self):
+        return {"hints4": self.hints4}
+
+    @torch.no_grad()
+    def forward_frame(self, left, right, hints=None):
+        """`hints` (1,Hc,Wc) or (Hc,Wc) float32 on the device: the hint map of the frame (a direct call); None: the hints
+        `_net_pair` has put into `self.hints4`"""
+        if hints is not None:
+            from . import ops
+            self._hints4_buffer(left.device)
+            ops.hints_to_quarter(hints.reshape(1, self.crop_height, self.crop_width).contiguous(),
+                                 (self.crop_height, self.crop_width), maxdisp=self.net.maxdisp, out=self.hints4)
+        if self.hints4 is None:
+            raise RuntimeError("KittiInferenceGuided.forward_frame: no hints yet (hand them in, or go through __call__)")
+        return super().forward_frame(left, right)
+
+    def __call__(self, left_rgb, right_rgb, hints, as_uint16: bool = False):
+        self._check_format(as_uint16)
+        return self._call_device(left_rgb, right_rgb, as_uint16, hints)
+
+    def _hints4_buffer(self, dev):
+        if self.hints4 is None:
+            self.hints4 = torch.zeros((1, self.crop_height // 4, self.crop_width // 4), device=dev, dtype=torch.float32)
+        return self.hints4
+
+    def _upload(self, s, left_rgb, right_rgb, copy, hints):
+        super()._upload(s, left_rgb, right_rgb, copy)
+        hw = tuple(s.meta[:2]) if self.rectify is None else tuple(self.rectify.dst_hw)
+        if self.lidar is not None:
+            if tuple(self.lidar.hw) != hw:
+                raise ValueError(f"lidar= projects into {self.lidar.hw[0]} x {self.lidar.hw[1]} images, got {hw[0]} x {hw[1]}")
+            s.hints = ("scan", hints)
+            return
+        if isinstance(hints, torch.Tensor):
+            if not hints.is_cuda or hints.dtype != torch.float32 or tuple(hints.shape) != hw or not hints.is_contiguous():
+                raise ValueError(f"hints must be a contiguous float32 {hw} map, got {hints.dtype} {tuple(hints.shape)}")
+            s.hints = ("map", hints)
+            return
+        hints = np.ascontiguousarray(hints)
+        if hints.dtype != np.float32 or hints.shape != hw:
+            raise ValueError(f"hints must be a float32 {hw} map of the image, got {hints.dtype} {hints.shape}")
+        pin, dev = s.scratch(("hints",) + hw, lambda: (torch.empty(hw, dtype=torch.float32).pin_memory(),
+                                                       torch.empty(hw, device=s.device, dtype=torch.float32)))
+        pin.numpy()[:] = hints       # (the copy that last left this buffer is behind the `uploaded` the parent waited for)
+        with torch.cuda.stream(copy):
+            dev.copy_(pin, non_blocking=True)
+            s.uploaded.record(copy)  # again: the pair and the hints
+        s.hints = ("map", dev)
+
+    def _net_pair(self, s, left, right, h, w):
+        """current stream: also the frame's `hints4`, from the slot's map (or scan) through the slot's placement"""
+        from . import ops
+        kind, item = s.hints
+        if kind == "scan":
+            if self._proj is None:
+                self._proj = LidarProjector(self.lidar, s.device, capacity=max(1 << 18, int(np.asarray(item).shape[0])))
+            item = self._proj(item)["disp"]
+        ops.hints_to_quarter(item, (self.crop_height, self.crop_width), s.meta[3], maxdisp=self.net.maxdisp,
+                             out=self._hints4_buffer(s.device)[0])
+        return left, right, h, w
 
 
 def _check_post(median, speckle):

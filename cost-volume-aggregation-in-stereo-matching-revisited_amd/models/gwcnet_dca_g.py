@@ -135,17 +135,21 @@ class GwcNet(nn.Module):
                 m.bias.data.zero_()
 
     # ---- the hot path proper: 1/4-res features -> 1/4-res disparity (+ training heads)
-    def hot_path(self, gwc_left, gwc_right, concat_left=None, concat_right=None, aux_volumes=False, confidence=None):
+    def hot_path(self, gwc_left, gwc_right, concat_left=None, concat_right=None, aux_volumes=False, confidence=None,
+                 hints4=None, guide=ops.GUIDE):
         with ops.batched_bn_counters():   # one multi-tensor add for all BatchNorm step counters
-            return self._hot_path(gwc_left, gwc_right, concat_left, concat_right, aux_volumes, confidence)
+            return self._hot_path(gwc_left, gwc_right, concat_left, concat_right, aux_volumes, confidence, hints4, guide)
 
-    def _hot_path(self, gwc_left, gwc_right, concat_left=None, concat_right=None, aux_volumes=False, confidence=None):
+    def _hot_path(self, gwc_left, gwc_right, concat_left=None, concat_right=None, aux_volumes=False, confidence=None,
+                  hints4=None, guide=ops.GUIDE):
         """reference gwcnet_dca_g.py:216-239 (+ :244-275 when training).  Returns a dict with `pred4_q`
         (B,1,H/4,W/4) in 1/4-res pixels, `prob_volume2` and, in training mode, the auxiliary heads.  `aux_volumes`
         adds `prob_volume1` and `prob_volume3` (fp32, also under ops.reduced_precision): the three region heads the
         reference's evaluation step scores (main_dca.py:211-213).  `confidence` = a window radius (int; inference only)
         adds `stats4_q` (B,5,H/4,W/4), the statistics of the final disparity distribution (ops.softargmin_stats), whose
-        plane 0 then IS `pred4_q` (a view; bitwise the soft-argmin): one launch in place of the soft-argmin's."""
+        plane 0 then IS `pred4_q` (a view; bitwise the soft-argmin): one launch in place of the soft-argmin's.
+        `hints4` (B,H/4,W/4), sparse disparity hints in 1/4-res bins (`ops.hints_to_quarter`), with guide = (k, c): guided
+        stereo, `ops.cost_volume(hints4=, guide=)`; None changes nothing."""
         d = self.maxdisp // 4
         lp = ops._lp_dtype()
         if confidence is not None and (self.training or torch.is_grad_enabled()):
@@ -158,7 +162,7 @@ class GwcNet(nn.Module):
         volume = ops.cost_volume(gwc_left, gwc_right, d, self.num_groups,
                                  concat_left if self.use_concat_volume else None,
                                  concat_right if self.use_concat_volume else None,
-                                 out_dtype=torch.float32 if lp is None else lp)
+                                 out_dtype=torch.float32 if lp is None else lp, hints4=hints4, guide=guide)
         cost0 = self.dres0(volume)
         cost0 = self.dres1(cost0)                               # dres1(cost0) + cost0
         heads = self.training and lp is None
@@ -191,12 +195,27 @@ class GwcNet(nn.Module):
             res["pred2"] = ops.softmax_dim1(logits2.squeeze(1))
         return res
 
-    def forward(self, left, right, disp_true=None):
+    def _hints4(self, left, hints):
+        """the full-resolution hint map (B,H,W) / (B,1,H,W) of the (padded) input -> `hints4` of the hot path, or None"""
+        if hints is None:
+            return None
+        if isinstance(hints, torch.Tensor) and hints.dim() == 4 and hints.shape[1] == 1:
+            hints = hints[:, 0]
+        if not isinstance(hints, torch.Tensor) or hints.dim() != 3 or tuple(hints.shape) != (left.shape[0],) + tuple(left.shape[2:]):
+            raise RuntimeError(f"GwcNet: hints must be a (B,H,W) map of the input images {tuple(left.shape)}, got "
+                               f"{tuple(hints.shape) if isinstance(hints, torch.Tensor) else type(hints)}")
+        return ops.hints_to_quarter(hints.detach().contiguous(), left.shape[2:], maxdisp=self.maxdisp)
+
+    def forward(self, left, right, disp_true=None, *, hints=None, guide=ops.GUIDE):
+        """`hints`: a sparse disparity map of the (padded) left image, (B,H,W) float32 in pixels, +0.0 where nothing was
+        measured (what `ops.lidar_disparity` writes): guided stereo, in training mode too -- the
+        hints get no gradient, the features do."""
         features_left = self.feature_extraction(left)
         features_right = self.feature_extraction(right)
         guidance = self.guidance(left)
         r = self.hot_path(features_left["gwc_segments"], features_right["gwc_segments"],
-                          features_left.get("concat_feature"), features_right.get("concat_feature"))
+                          features_left.get("concat_feature"), features_right.get("concat_feature"),
+                          hints4=self._hints4(left, hints), guide=guide)
         pred4 = self.prop(guidance["g"], r["pred4_q"])
         if self.training:
             return [r["pred0"], r["pred_dca1"], r["pred_dca2"], r["pred1"], r["pred2"]], [r["pred_dca3"], pred4]
@@ -208,13 +227,14 @@ class GwcNet(nn.Module):
                       ("entropy", ops.CONF_ENT, 1.0), ("std", ops.CONF_STD, 4.0))
 
     @torch.no_grad()
-    def predict(self, left, right, radius=1):
+    def predict(self, left, right, radius=1, *, hints=None, guide=ops.GUIDE):
         """Inference with per-pixel confidence (no counterpart in the reference): eval mode, no grad.  Returns full-
         resolution (B,1,H,W) maps: `disp` (bitwise `forward(left, right)[0]`), `disp_unimodal` (the soft-argmin over the
         bins within `radius` of the most likely one: no averaging over two peaks at a depth edge), `confidence` (the
         probability mass of that window, in [0,1]), `entropy` (of the whole distribution, normalised to [0,1]) and `std`
         (its standard deviation in pixels).  All five go through the convex up-sampler in one launch; like the disparity,
-        every map falls towards 0 in the 4-pixel cells along the frame border (zero padding of the 3x3 neighbourhood)."""
+        every map falls towards 0 in the 4-pixel cells along the frame border (zero padding of the 3x3 neighbourhood).
+        `hints`, `guide`: as in `forward`."""
         was_training = self.training
         self.eval()
         try:
@@ -223,7 +243,7 @@ class GwcNet(nn.Module):
             guidance = self.guidance(left)
             r = self.hot_path(features_left["gwc_segments"], features_right["gwc_segments"],
                               features_left.get("concat_feature"), features_right.get("concat_feature"),
-                              confidence=int(radius))
+                              confidence=int(radius), hints4=self._hints4(left, hints), guide=guide)
             names, planes, scales = zip(*self.PREDICT_PLANES)
             assert planes == tuple(range(ops.CONF_PLANES))         # stats4_q as it is: no gather
             up = self.prop.forward_planes(guidance["g"], r["stats4_q"], scales)
@@ -240,7 +260,9 @@ class GwcNet(nn.Module):
         resolution (B,1,H,W) maps: `disp` (bitwise `forward(left, right)[0]`), `disp_filled` (`disp` where the two views
         agree within `tau` pixels; elsewhere the smaller of the nearest agreeing neighbours in the row), `valid` (1.0 /
         0.0), `lr_diff` (|d_left - d_right| at the matched position, +inf where that lies outside the image) and
-        `disp_right` (the right view's disparity in its own coordinates)."""
+        `disp_right` (the right view's disparity in its own coordinates).  Takes no hints: there is
+        no scan in the right camera's mirrored frame, and a guided left pass checked against an unguided right pass needs a
+        study of its own."""
         ops._req_no_grad("predict_lr", left, right)
         was_training = self.training
         self.eval()

@@ -13,6 +13,7 @@ import threading
 import torch
 
 from ._call import _C, _L, _chk, _ptr, _raw_device, _raw_stream, _req, _req_no_grad, _stream, _vp  # noqa: F401
+from .guided import GUIDE, guide_params, hints_to_quarter  # noqa: F401
 
 
 def _opt(t, name):
@@ -76,12 +77,79 @@ def gwc_volume(ref, tgt, maxdisp, num_groups):
     return _GwcVolume.apply(ref, tgt, int(maxdisp), int(num_groups))
 
 
-class _CostVolume(torch.autograd.Function):
-    """Fused builder (csrc/volume_fused.hip): gwc volume from 1-3 channel segments per side + optional concat volume,
-    one output tensor, fp32 or the reduced-precision storage type."""
+def _guide_args(name, hints4, vol_shape, device, guide):
+    """the ONE check of a guided call: hints4 as it is (no copy) -- float32, contiguous, 16-byte aligned, (B,H,W) of the
+    (B,C,D,H,W) volume and on its device, never differentiated -- and guide = (k, c) -> (hints4, k, 1 / (2 c^2))"""
+    k, i2c2 = guide_params(name, guide)
+    want = (vol_shape[0],) + tuple(vol_shape[3:])
+    if not isinstance(hints4, torch.Tensor) or not hints4.is_cuda:
+        raise RuntimeError(f"{name}: hints4 must be on the ROCm device; there is no CPU fallback")
+    if hints4.dtype != torch.float32 or not hints4.is_contiguous() or hints4.data_ptr() % 16:
+        raise RuntimeError(f"{name}: hints4 must be a contiguous, 16-byte aligned float32 tensor, got {hints4.dtype}")
+    if tuple(hints4.shape) != want or hints4.device != device:
+        raise RuntimeError(f"{name}: hints4 must be {want} on {device}, got {tuple(hints4.shape)} on {hints4.device}")
+    if hints4.requires_grad:
+        raise RuntimeError(f"{name}: hints4 gets no gradient: detach it")
+    return hints4, k, i2c2
+
+
+def _modulate(vol, hints4, k, i2c2, out):
+    B, C, D, H, W = vol.shape
+    with torch.cuda.device_of(vol):
+        _chk(_L().dca_volume_modulate(_ptr(vol), _ptr(hints4), _ptr(out), B, C, D, H, W, k, i2c2, _stream()),
+             "dca_volume_modulate")
+    return out
+
+
+class _VolumeModulate(torch.autograd.Function):
+    """volume * m(d, hints4) (csrc/guided.hip); m does not depend on the volume, so the backward is the same kernel on the
+    incoming gradient"""
 
     @staticmethod
-    def forward(ctx, maxdisp, num_groups, out_dtype, nseg, has_concat, *tensors):
+    def forward(ctx, volume, hints4, k, i2c2):
+        volume = _req(volume, "volume_modulate")
+        ctx.save_for_backward(hints4)
+        ctx.meta = (k, i2c2)
+        return _modulate(volume, hints4, k, i2c2, torch.empty_like(volume))
+
+    @staticmethod
+    def backward(ctx, g):
+        (hints4,), (k, i2c2) = ctx.saved_tensors, ctx.meta
+        g = _req(g, "volume_modulate.backward")
+        return _modulate(g, hints4, k, i2c2, torch.empty_like(g)), None, None, None
+
+
+def volume_modulate(volume, hints4, k=GUIDE[0], c=GUIDE[1], out=None):
+    """Guided stereo as a pass of its own: the fp32 volume (B,C,D,H,W) times, along the disparity
+    axis, k exp(-(d - h4)^2 / (2 c^2)) wherever hints4 (B,H,W) holds a hint h4 > 0 (in disparity bins; +0.0 = none, factor
+    exactly 1).  out (inference only: no autograd node is made): `volume` itself (in place) or a buffer of its own of the
+    volume's shape, which is what comes back.  The gradient with respect to the volume is the same kernel on the incoming
+    gradient; hints4 gets none."""
+    name = "volume_modulate"
+    if not isinstance(volume, torch.Tensor) or volume.dim() != 5:
+        raise RuntimeError(f"{name}: expected a (B,C,D,H,W) volume")
+    hints4, k, i2c2 = _guide_args(name, hints4, volume.shape, volume.device, (k, c))
+    if out is None:
+        return _VolumeModulate.apply(volume, hints4, k, i2c2)
+    _req_no_grad(f"{name}(out=)", volume)
+    if volume.dtype != torch.float32 or not volume.is_cuda or not volume.is_contiguous() or volume.data_ptr() % 4:
+        raise RuntimeError(f"{name}: out= needs a contiguous float32 volume on the ROCm device")
+    if out is not volume:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() \
+                or out.shape != volume.shape or out.device != volume.device:
+            raise RuntimeError(f"{name}: out must be a contiguous float32 tensor of the volume's shape on its device")
+        if out.untyped_storage().data_ptr() == volume.untyped_storage().data_ptr():
+            raise RuntimeError(f"{name}: out is the volume itself (in place) or a buffer of its own")
+    return _modulate(volume, hints4, k, i2c2, out)
+
+
+class _CostVolume(torch.autograd.Function):
+    """Fused builder (csrc/volume_fused.hip): gwc volume from 1-3 channel segments per side + optional concat volume,
+    one output tensor, fp32 or the reduced-precision storage type.  guide = None, or (hints4, k, 1 / (2 c^2)): the guided
+    instantiations, which multiply every channel by the hint's factor before the store."""
+
+    @staticmethod
+    def forward(ctx, maxdisp, num_groups, out_dtype, nseg, has_concat, guide, *tensors):
         refs = [_req(t, "cost_volume.ref") for t in tensors[:nseg]]
         tgts = [_req(t, "cost_volume.tgt") for t in tensors[nseg:2 * nseg]]
         cref = _req(tensors[2 * nseg], "cost_volume.cref") if has_concat else None
@@ -99,9 +167,15 @@ class _CostVolume(torch.autograd.Function):
         # fp32 volume without concat part: the builder emits the per-channel maxima the first f16x2 convolution scales by
         vmax = _cslots(num_groups, vol.device) if (CONV_X2 and AMAX_EMIT and code == 0 and Cc == 0 and B * H <= CSLOTS) else None
         with torch.cuda.device_of(vol):
-            _chk(_L().dca_cost_volume_fwd(rp, tp, sc, nseg, _ptr(cref), _ptr(ctgt), Cc, _ptr(vol), B, H, W, maxdisp,
-                                          num_groups, code, _ptr(vmax), _stream()), "dca_cost_volume_fwd")
+            if guide is None:
+                _chk(_L().dca_cost_volume_fwd(rp, tp, sc, nseg, _ptr(cref), _ptr(ctgt), Cc, _ptr(vol), B, H, W, maxdisp,
+                                              num_groups, code, _ptr(vmax), _stream()), "dca_cost_volume_fwd")
+            else:
+                _chk(_L().dca_cost_volume_guided_fwd(rp, tp, sc, nseg, _ptr(cref), _ptr(ctgt), Cc, _ptr(vol), B, H, W, maxdisp,
+                                                     num_groups, code, _ptr(vmax), _ptr(guide[0]), guide[1], guide[2],
+                                                     _stream()), "dca_cost_volume_guided_fwd")
         ctx.save_for_backward(*refs, *tgts)
+        ctx.guide = guide
         ctx.meta = (maxdisp, num_groups, nseg, segC, Cc, (B, H, W))
         return _tag_cmax(vol, vmax, B * H)   # no read pass in front of dres0's first convolution
 
@@ -110,6 +184,8 @@ class _CostVolume(torch.autograd.Function):
         maxdisp, G, nseg, segC, Cc, (B, H, W) = ctx.meta
         refs, tgts = ctx.saved_tensors[:nseg], ctx.saved_tensors[nseg:]
         gvol = _req(gvol, "cost_volume.backward")
+        if ctx.guide is not None:      # the factor does not depend on the features: d/dvolume -> m * d/dvolume, then as unguided
+            gvol = _modulate(gvol, *ctx.guide, torch.empty_like(gvol))
         ref = refs[0] if nseg == 1 else torch.cat(refs, 1)
         tgt = tgts[0] if nseg == 1 else torch.cat(tgts, 1)
         gg = gvol if Cc == 0 else gvol[:, :G].contiguous()
@@ -126,14 +202,17 @@ class _CostVolume(torch.autograd.Function):
                 _chk(lib.dca_concat_volume_bwd(_ptr(gc), _ptr(gcr), _ptr(gct), B, Cc, H, W, maxdisp, _stream()),
                      "dca_concat_volume_bwd")
                 grads += [gcr, gct]
-        return (None, None, None, None, None) + tuple(grads)
+        return (None, None, None, None, None, None) + tuple(grads)
 
 
-def cost_volume(ref, tgt, maxdisp, num_groups, cref=None, ctgt=None, out_dtype=torch.float32):
+def cost_volume(ref, tgt, maxdisp, num_groups, cref=None, ctgt=None, out_dtype=torch.float32, hints4=None, guide=GUIDE):
     """build_gwc_volume(ref, tgt) [cat build_concat_volume(cref, ctgt)] as ONE (B, G + 2*Cc, D, H, W) tensor.  `ref` /
     `tgt` may be tuples of channel segments (the extractor's l2 / l3 / l4 maps) that are read in place.  Falls back to
     the separate builders + torch.cat when W % 4 != 0, and for the fp32 volume also when D % 4 != 0 (the fused kernel takes
-    any D; the fp32 routing is left as it was).  The reduced-precision volume has the fused builder only: any D, W % 4 == 0."""
+    any D; the fp32 routing is left as it was).  The reduced-precision volume has the fused builder only: any D, W % 4 == 0.
+    hints4 (B,H,W) float32, a hint in disparity bins per cell, +0.0 = none (`hints_to_quarter`), with guide = (k, c): guided
+    stereo -- every channel is multiplied along the disparity axis by k exp(-(d - h4)^2 / (2 c^2)) where a hint is, inside
+    the fused builder, and by `volume_modulate` behind the fallback; None changes nothing."""
     refs = tuple(ref) if isinstance(ref, (tuple, list)) else (ref,)
     tgts = tuple(tgt) if isinstance(tgt, (tuple, list)) else (tgt,)
     W = refs[0].shape[-1]
@@ -141,15 +220,20 @@ def cost_volume(ref, tgt, maxdisp, num_groups, cref=None, ctgt=None, out_dtype=t
     cpg = C // num_groups if num_groups else 0
     ok = (W % 4 == 0 and (maxdisp % 4 == 0 or out_dtype != torch.float32) and len(refs) <= 3 and cpg in (1, 2, 4, 8, 16)
           and C % num_groups == 0 and all(t.shape[1] % cpg == 0 for t in refs))
+    g = None
+    if hints4 is not None:
+        B, _, H, _ = refs[0].shape
+        g = _guide_args("cost_volume", hints4, (B, 0, int(maxdisp), H, W), refs[0].device, guide)
     if not ok:
         if out_dtype != torch.float32:
             raise RuntimeError("cost_volume: the reduced-precision volume needs W % 4 == 0")
         r1 = refs[0] if len(refs) == 1 else torch.cat(refs, 1)
         t1 = tgts[0] if len(tgts) == 1 else torch.cat(tgts, 1)
         vol = gwc_volume(r1, t1, maxdisp, num_groups)
-        return vol if cref is None else torch.cat((vol, concat_volume(cref, ctgt, maxdisp)), 1)
+        vol = vol if cref is None else torch.cat((vol, concat_volume(cref, ctgt, maxdisp)), 1)
+        return vol if g is None else _VolumeModulate.apply(vol, *g)
     extra = () if cref is None else (cref, ctgt)
-    return _CostVolume.apply(int(maxdisp), int(num_groups), out_dtype, len(refs), cref is not None, *refs, *tgts, *extra)
+    return _CostVolume.apply(int(maxdisp), int(num_groups), out_dtype, len(refs), cref is not None, g, *refs, *tgts, *extra)
 
 
 def concat_volume(ref, tgt, maxdisp):

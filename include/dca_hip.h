@@ -982,6 +982,39 @@ int dca_guided_upsample(const float* disp_lo, const float* mask_lo, const unsign
                         int Wc, int y0, int rows, int cols, int H, int W, int C, int s, int r, float mask_min,
                         hipStream_t stream);
 
+/* ---- guided stereo (guided.hip, volume_fused.hip): sparse disparity hints (a LiDAR scan projected by
+ * dca_lidar_disparity) modulate the cost volume along the disparity axis (Poggi et al., CVPR 2019).  Nothing in the
+ * reference corresponds to it.  No atomics, no launch synchronises or allocates.
+ *
+ * A full-resolution hint h is VALID iff 0 < h < maxdisp (a NaN or an infinity is not).
+ *
+ * dca_hints_to_quarter: hints (B,h,w) fp32 -> hints4 (B, Hc/4, Wc/4) fp32 over the network's Hc x Wc frame, Hc % 4 == 0,
+ * Wc % 4 == 0.  The image window is rows x cols pixels from source row src_y0, column 0, at frame row dst_y0, column 0 (as
+ * in dca_frame_apply).  Cell (Y,X) looks at the frame pixels 4Y..4Y+3 x 4X..4X+3 that lie inside the window:
+ *   hints4 = 0.25f * max(valid h in the block),   +0.0 if the block holds none
+ * (the largest disparity is the nearest surface).  Every cell is written.  count (int64, may be NULL) receives the number of
+ * cells > 0, by a second launch of one workgroup that sums integers in a fixed order.
+ *
+ * The factor of disparity bin d (an integer) at a cell with the hint h4, for k > 0 and i2c2 = 1 / (2 c^2) > 0:
+ *   m(d, h4) = h4 > 0 ?  k * expf(-((d - h4) * (d - h4)) * i2c2)  :  1.0f         every product rounded on its own
+ * (csrc/guided_math.h, the one definition both routes below call).
+ *
+ * dca_volume_modulate: out[b,c,d,y,x] = in[b,c,d,y,x] * m(d, hints4[b,y,x]) on an fp32 (B,C,D,H,W) tensor; out == in is
+ * allowed (in place), any other overlap is not.  16-byte accesses when W % 4 == 0 and all three pointers are 16-byte
+ * aligned, single floats otherwise; a thread owns (b, d, y, x quad) and walks the C channels with its factors in registers.
+ *
+ * dca_cost_volume_guided_fwd: dca_cost_volume_fwd with every channel of the volume multiplied by m in the builders' inner
+ * loops, before the store's rounding and before the per-row maxima of vmax are taken.  Same arguments and requirements;
+ * hints4 (B,H,W) fp32, 16-byte aligned.  The fp32 result is bitwise dca_cost_volume_fwd followed by dca_volume_modulate. */
+int dca_hints_to_quarter(const float* hints, float* hints4, long* count, int B, int h, int w, int Hc, int Wc, int src_y0,
+                         int dst_y0, int rows, int cols, float maxdisp, hipStream_t stream);
+int dca_volume_modulate(const float* in, const float* hints4, float* out, int B, int C, int D, int H, int W, float k,
+                        float i2c2, hipStream_t stream);
+int dca_cost_volume_guided_fwd(const float* const* refs, const float* const* tgts, const int* seg_channels, int nseg,
+                               const float* cref, const float* ctgt, int Cc, void* vol, int B, int H, int W, int maxdisp,
+                               int num_groups, int dtype, unsigned* vmax, const float* hints4, float k, float i2c2,
+                               hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
