@@ -921,6 +921,118 @@ class KittiInference3D(KittiInference):
         return vertices
 
 
+FrameGround = collections.namedtuple("FrameGround", "disp label free_row free_disp bev plane")
+
+
+class _Ground:
+    """Per-slot buffers of KittiInferenceGround beyond the frame's record, allocated once for the frame size: the v-disparity
+    histogram and the workspace of `ops.ground_plane`."""
+
+    def __init__(self, device, crop_height, crop_width, max_disp):
+        from . import ops
+        self.vdisp = torch.empty((crop_height, max_disp), device=device, dtype=torch.int32)
+        self.workspace = ops.ground_workspace(crop_height, crop_width, max_disp, device)
+
+
+class KittiInferenceGround(KittiInference):
+    """`disp, label, free_row, free_disp, bev, plane = KittiInferenceGround(model, calib, mask=None | "confidence" | "lr", ...)(
+    left_rgb, right_rgb)`: KittiInference with device I/O (required: the stage runs where the disparity lies) followed by the
+    ground stage on the same stream: `ops.ground_plane` -- v-disparity, Hough line, least squares with
+    roll -- and `ops.ground_segment` under `calib` (a geometry.StereoCalib of the images as they are handed in; with `rectify=`
+    of the rectified pair, by default the maps' own `calib`, and pixels whose source footprint leaves the raw image are no
+    measurement: the maps' validity is the mask, or multiplies it; mask_min must be > 0 then).  The disparity and the mask per
+    mode are KittiInference3D's: None, "confidence" (`radius`) or "lr" (`tau`; the UNFILLED left disparity, two passes per frame).
+    `median=3 | 5` and `speckle=(max_size, max_diff)` (off by default) run the post-filter of
+    KittiInferenceFiltered BEFORE the fit: `disp` is then the filtered disparity, a removed pixel is no measurement.
+      disp       float32 (h,w)        the disparity the stage read
+      label      uint8   (h,w)        0 no data, 1 ground, 2 obstacle, 3 overhang, 4 below ground
+      free_row   int32   (w,)         the base row of the lowest obstacle of every column, -1: none; free_disp float32 (w,): its disparity
+      bev        int32   (2,NZ,NX)    ground / obstacle pixels per cell of `grid` = (cell, x_half, z_max) in metres
+      plane      float64 (16,)        the plane record (`ground.PLANE_FIELDS`; `ground.plane_pose(plane, calib, v0)` gives the camera's
+                                      height, pitch and roll; v0 = the image row of the window's first row, 0 for an image
+                                      that fits the frame)
+    `max_disp`: the histogram's bins, default the model's `maxdisp`; `min_disp`: the smallest valid disparity; `plane`, `segment`:
+    dicts of further keywords of `ops.ground_plane` (fit_rows, refine, tol, min_rise, min_votes, min_inliers) and
+    `ops.ground_segment` (tol_d, h_ground, h_max, min_run).  All buffers are allocated once per slot; the whole record comes
+    back in one copy and one synchronisation per frame."""
+
+    device_io = True
+    needs_device_io = "the ground stage runs on the device, next to the disparity"
+    has_uint16 = False
+    Frame = FrameGround
+    PLANE_KEYS = ("fit_rows", "refine", "tol", "min_rise", "min_votes", "min_inliers")
+    SEGMENT_KEYS = ("tol_d", "h_ground", "h_max", "min_run")
+    _valid = KittiInference3D._valid
+    _valid_frame = None
+
+    def __init__(self, model, calib=None, *args, mask=None, mask_min: float = 0.5, radius: int = 1, tau: float = 1.0, speckle=None,
+                 median: int = 0, max_disp=None, min_disp=None, grid=None, plane=None, segment=None, **kwargs):
+        from . import ground as G
+        super().__init__(model, *args, **kwargs)
+        name = type(self).__name__
+        self.median, self.speckle = _check_post(median, speckle)
+        if calib is None:
+            calib = getattr(self.rectify, "calib", None)
+            if calib is None:
+                raise ValueError(f"{name} needs calib=, or rectify= maps that carry the rectified pair's calibration")
+        if self.rectify is not None and not float(mask_min) > 0.0:
+            raise ValueError("with rectify= the maps' validity (0 / 1) enters the mask: mask_min must be > 0")
+        self._take_mask(mask, mask_min, radius, tau)
+        if max_disp is None:
+            max_disp = getattr(self.net, "maxdisp", None)
+            if max_disp is None:
+                raise ValueError(f"{name} needs max_disp=: the model has no `maxdisp`")
+        plane, segment = dict(plane or {}), dict(segment or {})
+        if set(plane) - set(self.PLANE_KEYS) or set(segment) - set(self.SEGMENT_KEYS):
+            raise ValueError(f"{name}: plane= takes {self.PLANE_KEYS} and segment= takes {self.SEGMENT_KEYS}, got {sorted(plane)} and "
+                             f"{sorted(segment)}")
+        self.min_disp = G.GROUND_MIN_DISP if min_disp is None else float(min_disp)
+        self.grid = G.GROUND_GRID if grid is None else tuple(float(v) for v in grid)
+        # the operators' ranges, up front (fit_rows is checked against the frame; an image may be smaller)
+        p = dict(rows_range=plane.get("fit_rows"), min_rise=G.GROUND_MIN_RISE, min_votes=None, refine=G.GROUND_REFINE,
+                 min_inliers=G.GROUND_MIN_INLIERS, tol=G.GROUND_TOL)
+        p.update({k: v for k, v in plane.items() if k != "fit_rows"})
+        G.plane_scalars(name, ValueError, self.crop_height, self.crop_width, max_disp, min_disp=self.min_disp, **p)
+        G.calib_scalars(name, ValueError, calib)
+        g = dict(tol_d=G.GROUND_TOL_D, h_ground=G.GROUND_H_GROUND, h_max=G.GROUND_H_MAX, min_run=G.GROUND_MIN_RUN)
+        g.update(segment)
+        self._cells = G.segment_scalars(name, ValueError, max_disp, self.min_disp, grid=self.grid, **g)[-1][3:]       # (NX, NZ)
+        self.calib, self.max_disp, self.plane_kw, self.segment_kw = calib, int(max_disp), plane, segment
+
+    def _fields(self, rows, cols, as_uint16):
+        """the doubles first, the bytes last: every field lies at a multiple of its element size"""
+        NX, NZ = self._cells
+        return [("plane", torch.float64, (16,)), ("disp", torch.float32, (rows, cols)), ("free_row", torch.int32, (cols,)),
+                ("free_disp", torch.float32, (cols,)), ("bev", torch.int32, (2, NZ, NX)), ("label", torch.uint8, (rows, cols))]
+
+    def _export(self, s, maps, out):
+        from . import ops
+        h, w, c, (src_y0, dst_y0, rows, cols), _ = s.meta
+        g = s.scratch("ground", lambda: _Ground(s.device, self.crop_height, self.crop_width, self.max_disp))
+        pred = maps[0].contiguous()
+        pred = pred.view(pred.shape[-2:])
+        mask = maps[1].contiguous().view_as(pred) if len(maps) > 1 else None
+        window = (dst_y0, rows, cols)
+        valid = None
+        if self.rectify is not None:     # a pixel without a full source footprint is no measurement
+            valid = self._valid(pred.device, src_y0, dst_y0, rows, cols)
+        if self.median or self.speckle is not None:
+            # the filters run before the fit; a removed pixel is +0.0, below every min_disp > 0, and leaves the mask where it has one
+            pred, mask, window = _post_filter(self, s, pred, mask, window, out["disp"], self.speckle, self.mask_min > 0.0)
+            if valid is not None:
+                valid = valid[dst_y0:dst_y0 + rows, :cols].contiguous()
+        else:
+            ops.disp_export(pred, dst_y0, rows, cols, out_f32=out["disp"])
+        if valid is not None:
+            mask = valid if mask is None else mask * valid
+        frame = dict(max_disp=self.max_disp, mask=mask, mask_min=self.mask_min, window=window, min_disp=self.min_disp)
+        ops.ground_plane(pred, calib=self.calib, v0=src_y0, workspace=g.workspace,
+                         out={"plane": out["plane"], "vdisp": g.vdisp[:rows]}, **frame, **self.plane_kw)
+        names = ("label", "free_row", "free_disp", "bev")
+        ops.ground_segment(pred, out["plane"], self.calib, grid=self.grid, outputs=names, out={k: out[k] for k in names}, **frame,
+                           **self.segment_kw)
+
+
 class KittiInferenceColor(KittiInference):
     """`disp, rgb = KittiInferenceColor(model, cmap="kitti", max_disp=None, mask=None | "confidence" | "lr", ...)(left_rgb,
     right_rgb)`: KittiInference with device I/O (required: the picture is made where the disparity lies) followed by one

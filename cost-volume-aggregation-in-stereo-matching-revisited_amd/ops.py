@@ -2197,3 +2197,6 @@ from .frame_ops import (  # noqa: E402,F401
 from .highres import (  # noqa: E402,F401
     HR_MAX_SCALE, HR_MAX_RADIUS, HR_RANGE_LEN, HR_TILE, UPSAMPLE_OUTPUTS, area_downscale_pair, area_downscale_disp,
     guided_upsample)
+# ... and those for the ground plane (ground.py)
+from .ground import (  # noqa: E402,F401
+    GROUND_PLANE_LEN, GROUND_WS_LEN, GROUND_SUMS_AT, GROUND_OUTPUTS, ground_workspace, ground_plane, ground_segment)

@@ -1015,6 +1015,113 @@ int dca_cost_volume_guided_fwd(const float* const* refs, const float* const* tgt
                                int num_groups, int dtype, unsigned* vmax, const float* hints4, float k, float i2c2,
                                hipStream_t stream);
 
+/* ---- ground plane, obstacles and free space from disparity (ground.hip, ground_math.h); inference
+ * only, no backward, no counterpart in the reference.  dcanet_amd/ground.py holds the numpy restatements.
+ * d (B,Hc,Wc) fp32: B independent disparity maps; the window is rows x cols pixels starting at frame row y0, column 0 of every
+ * image, as in dca_speckle_filter; mask (B,Hc,Wc) fp32 or NULL, indexed like d.  NB = max_disp, R = rows.  Every fp32 and
+ * fp64 formula below is evaluated one operation at a time (no fused multiply-adds), IEEE division and square root; every
+ * accumulation is an integer count or an integer sum (LDS and agent-scope integer atomics, whose result does not depend
+ * on the order); there is no floating-point atomic: every output is bitwise defined.
+ *
+ * A window pixel (r, c) with the disparity d is VALID iff, in this order,
+ *   d >= min_disp                           (false for a NaN and for -inf; min_disp >= 0)
+ *   t = d * 16.0f + 0.5f;  t < float(16 NB)  (false for +inf);   q = (int)t, the disparity in sixteenths;  bin = q >> 4 < NB
+ *   mask == NULL || mask >= mask_min
+ *
+ * dca_ground_plane.
+ * (a) v-disparity (Labayrade et al. 2002): vdisp[b, r, bin] (int32, rows x NB per image) = the number of valid pixels of
+ *     window row r in that bin.  One wave per row, the row's histogram in LDS; every word of vdisp is written.
+ * (b) line by Hough vote.  Candidates are the integer pairs (d_top, d_bot), the line's disparity at window row 0 and at row
+ *     R-1:  d_top in [-NB, NB), d_bot in [1, NB), d_bot - d_top >= min_rise (a wall draws a vertical line: no rise).  So
+ *     the horizon lies above the window (d_top >= 0) or in it at or above the row where a line from -NB at the top reaches
+ *     0 -- in the upper half whenever d_bot <= NB; a horizon further down is not found.
+ *       bin(r) = floor_div(2 (d_top (R-1-r) + d_bot r) + (R-1), 2 (R-1))       floor division: negative above the horizon
+ *       vote   = sum of vdisp[r, bin(r)] over the fit rows r in [r_lo, r_hi) with 0 <= bin(r) < NB
+ *     The best candidate has the largest vote; ties go to the smallest d_bot, then the smallest d_top: the unsigned
+ *     maximum of  vote << 32 | ~(d_bot 2 NB + d_top + NB)  (32 bits).  best vote < min_votes: status 1, nothing is refined.
+ * (c) `refine` rounds of least squares with roll for  d = a u' + b v' + c,  u' = c - cols / 2, v' = r - rows / 2 (integer
+ *     divisions).  The inliers of a round are the valid pixels of the fit rows with fabsf(d - p) <= tol in fp32, where
+ *       round 0:  p = (float(d_top) * float(R-1-r) + float(d_bot) * float(r)) / float(R-1)
+ *       later:    p = (a32 * float(u') + b32 * float(v')) + c32,   a32 = (float)a etc.: the record's doubles rounded once
+ *     Over them the ten int64 sums  S = { n, Su, Sv, Sq, Suu, Suv, Svv, Suq, Svq, Sqq }  (u = u', v = v', q as above) are
+ *     formed exactly, and one thread solves in fp64, with the sums converted to double, in exactly this order:
+ *       c00 = Svv n - Sv Sv;   c01 = Suv n - Sv Su;   c02 = Suv Sv - Svv Su
+ *       c11 = Suu n - Su Su;   c12 = Suu Sv - Suv Su; c22 = Suu Svv - Suv Suv
+ *       det = (Suu c00 - Suv c01) + Su c02
+ *       A = ((Suq c00 - Svq c01) + Sq c02) / det;  B = ((Svq c11 - Suq c01) - Sq c12) / det
+ *       C = ((Suq c02 - Svq c12) + Sq c22) / det
+ *       rss = Sqq - ((A Suq + B Svq) + C Sq);   ms = rss / n;   rms = sqrt(ms > 0 ? ms : 0) / 16
+ *       a = A / 16;  b = B / 16;  c = C / 16
+ *     n < min_inliers or not det > 0 (the Gram determinant is never negative in exact arithmetic): status 2, the record
+ *     keeps the last good plane and the remaining rounds do nothing.  The plane before round 0 is the Hough line:
+ *       a = 0;  b = double(d_bot - d_top) / double(R-1);  c = double(d_top) + b * double(rows / 2)
+ * Plane record, DCA_GROUND_PLANE_LEN doubles per image:
+ *   [0] a  [1] b  [2] c  [3] inliers of the record's plane (0: the Hough line)  [4] their rms residual, pixels
+ *   [5] status: 0 fitted, 1 no line (best vote < min_votes), 2 a refinement round failed  [6] d_top  [7] d_bot
+ *   [8] best vote  [9] hs  [10..12] the unit normal  [13] cols / 2  [14] rows / 2  [15] refinement rounds that succeeded
+ * With calibrated = 1, f, baseline, cx, cy, doffs and v0 (the image row of window row 0) as doubles: in the image
+ * coordinates u = col, v = v0 + row the plane is  den = d + doffs = a u + b v + c_img, in the camera frame
+ * a X + b Y + nz Z = baseline:
+ *   c_img = ((c - a * [13]) - b * (v0 + [14])) + doffs;   nz = ((a * cx + b * cy) + c_img) / f
+ *   norm = sqrt((a * a + b * b) + nz * nz);   hs = baseline / norm (the camera's height above the plane, metres);
+ *   normal = (a / norm, b / norm, nz / norm);   not norm > 0, or calibrated = 0:  hs = 0 and normal = 0
+ * ws: DCA_GROUND_WS_LEN int64 per image of workspace, the caller's, cleared by the first launch of every call:
+ *   [0] the Hough key   [8 + 10 k + j] sum j of round k   (the rounds that did nothing leave zeros)
+ * Launches: v-disparity, vote, then (sums, solve) per round: 2 + 2 refine; refine = 0 takes 3, the solve kernel writing the
+ * record of the Hough line alone.  Kernel boundaries are the only global synchronisation; nothing is allocated, nothing
+ * waits, every scalar is passed by value.
+ * Exactness: with rows, cols <= DCA_GROUND_MAX_DIM and NB <= DCA_GROUND_MAX_DISP every vote and every count is below 2^31
+ * (at most rows cols), every line numerator below 2^27, every int64 sum below 2^59 (rows cols * 2^14 * 2^14); a sum below 2^53
+ * converts to double exactly, a larger one is rounded once, to nearest, on the device and in the restatement alike.
+ * Refused: NULL d / plane / vdisp / ws, B outside [1, 65535], a window outside the frame, Hc Wc >= 2^31, rows < 2, rows or
+ * cols > DCA_GROUND_MAX_DIM, max_disp outside [8, DCA_GROUND_MAX_DISP], fit rows outside 0 <= r_lo < r_hi <= rows,
+ * min_rise outside [1, NB], min_votes < 1, refine outside [0, DCA_GROUND_MAX_REFINE], min_inliers < 3, min_disp or tol negative
+ * or not finite, a NaN mask_min with a mask, calibrated outside {0, 1}; with calibrated = 1: f or baseline not positive and
+ * finite, cx, cy, doffs or v0 not finite.
+ *
+ * dca_ground_segment: labels, height above the road, free space per column and a bird's-eye occupancy grid from d, the
+ * record `plane` of dca_ground_plane (read from device memory; it must have been computed with calibrated = 1 under this
+ * calibration) and the fp32 calibration of dca_point_cloud (fb = float(f * baseline), rounded once by the host).
+ * Per window pixel, with a32, b32, c32, hs32 the record's doubles rounded once to fp32:
+ *   p = (a32 * float(u') + b32 * float(v')) + c32;   den = d + doffs;   pden = p + doffs;   h = (hs32 * (den - pden)) / den
+ * h is the height above the road in metres, positive for a surface nearer than the road along the ray.  Labels (uint8),
+ * the first rule that matches:
+ *   0  no data        the pixel is not valid, or not den > 0, or the record's status is 1, or not hs32 > 0
+ *   1  ground         fabsf(d - p) <= tol_d  ||  fabsf(h) <= h_ground
+ *   4  below ground   h < 0
+ *   3  overhang       h > h_max
+ *   2  obstacle       everything else
+ * Outputs, any may be NULL (free_row and free_disp together), not all:
+ *   label (B,rows,cols) uint8;   height (B,rows,cols) fp32: h, +0.0 where the label is 0
+ *   free_row (B,cols) int32, free_disp (B,cols) fp32: walking a column from the bottom row up, the first run of min_run
+ *     consecutive pixels of label 2 (any other label starts the count again): free_row = the LOWEST row of that run (the
+ *     obstacle's base), free_disp = d there bit for bit;  -1 and +0.0 without such a run
+ *   bev (B,2,NZ,NX) int32: channel 0 counts the pixels of label 1, channel 1 those of label 2, per cell, with X and Z of
+ *     dca_point_cloud (Z = fb / den;  X = ((float(c) - cx) * Z) / f):
+ *       fx = floorf((X - x_min) * inv_cell);   fz = floorf(Z * inv_cell)     inv_cell: fp32, rounded once by the host
+ *     a pixel counts iff 0 <= fx < NX, 0 <= fz < NZ (compared in float, then converted) and Z <= max_depth
+ * TWO launches: (1) one lane per column walks it (the label is a function of the pixel and the record alone and is evaluated
+ * again), and the same launch clears bev; (2) one thread per pixel writes label and height and adds to bev -- one integer
+ * atomic per run of consecutive lanes of a wave that hit the same cell.  The kernel boundary orders the clearing before the adds.
+ * Refused: NULL d / plane, no output, one of free_row / free_disp without the other, B outside [1, 65535], a window outside the
+ * frame, rows or cols > DCA_GROUND_MAX_DIM, max_disp outside [8, DCA_GROUND_MAX_DISP], min_disp, tol_d, h_ground negative or not
+ * finite, h_max not finite, min_run < 1, a NaN mask_min with a mask, f or fb not positive and finite, cx, doffs or x_min not
+ * finite, with bev: inv_cell or max_depth not positive and finite, NX or NZ < 1, 2 NX NZ >= 2^31. */
+#define DCA_GROUND_PLANE_LEN 16
+#define DCA_GROUND_WS_LEN 48
+#define DCA_GROUND_MAX_REFINE 4
+#define DCA_GROUND_MAX_DISP 1024
+#define DCA_GROUND_MAX_DIM 32768
+int dca_ground_plane(const float* d, const float* mask, double* plane, int* vdisp, long long* ws, int B, int Hc, int Wc, int y0,
+                     int rows, int cols, int max_disp, int r_lo, int r_hi, int min_rise, int min_votes, int refine,
+                     int min_inliers, float min_disp, float tol, float mask_min, int calibrated, double f, double baseline,
+                     double cx, double cy, double doffs, double v0, hipStream_t stream);
+int dca_ground_segment(const float* d, const float* mask, const double* plane, unsigned char* label, float* height,
+                       int* free_row, float* free_disp, int* bev, int B, int Hc, int Wc, int y0, int rows, int cols,
+                       int max_disp, float min_disp, float mask_min, float tol_d, float h_ground, float h_max, int min_run,
+                       float f, float fb, float cx, float doffs, float x_min, float inv_cell, float max_depth, int NX, int NZ,
+                       hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
