@@ -154,6 +154,11 @@ __global__ __launch_bounds__(256, 2) void conv1_x3_kernel(C1XArgs a) {
           if (stat_first) {   // the wave's first group: the shift of (half, r) = what lane 0 of the half produced
             const float kf = fs_half_first(o0, half);
             if ((lane & 31) == 0) fs_slot(stat_w, half, r)[0] = kf;
+            // one lane writes, the whole half reads: without an ordering the compiler knows of it may read the slot first
+            // (it does once it can prove a single trip through the group loop).  Wavefront scope: no instruction emitted
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
           }
           const float k = fs_slot(stat_w, half, r)[0];
           const float d0 = inr ? o0 - k : 0.f, d1 = inr ? o1 - k : 0.f, d2 = inr ? o2 - k : 0.f, d3 = inr ? o3 - k : 0.f;

@@ -51,6 +51,8 @@ CASES = {
     "proj_leaky": (32, 0, 32, 0.1, True, 1, (4, 6, 10)),                    # a _ProjLayer: slope 0.1
     "eval_bn": (32, 0, 32, 1.0, False, 2, (4, 6, 12)),                      # eval-mode BatchNorm with grad enabled
     "pipeline": (32, 0, 32, 1.0, True, 3, (12, 34, 120)),                   # 576 tiles for at most 512 workgroups
+    "pipeline_deep": (32, 0, 32, 1.0, True, 9, (12, 34, 120)),              # 1728 tiles: at least three per workgroup
+    "pipeline_deep_two_inputs": (32, 32, 32, 1.0, True, 9, (12, 34, 120)),
 }
 FALLBACKS = {
     "s_not_multiple_of_4": (32, 0, 32, 1.0, True, 2, (3, 5, 9)),
