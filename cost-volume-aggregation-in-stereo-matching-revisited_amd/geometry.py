@@ -694,3 +694,100 @@ class LidarProjector:
             yield self._project(cur)
             cur = nxt
         yield self._project(cur)
+
+
+# ------------------------------------------------------------------------------------------------
+# Camera poses of a drive, float64 on the host: what `temporal.reproject_matrix` takes is the pose of the
+# previous rectified left camera in the current one, `relative_pose` of two world poses.
+# ------------------------------------------------------------------------------------------------
+EARTH_RADIUS = 6378137.0           # metres, the KITTI raw devkit's
+
+
+def _pose44(T, name):
+    T = np.asarray(T, np.float64)
+    if T.shape == (3, 4):
+        T = np.vstack([T, [0.0, 0.0, 0.0, 1.0]])
+    if T.shape != (4, 4) or not np.isfinite(T).all():
+        raise ValueError(f"{name}: a pose is a finite (4,4) or (3,4) array, got shape {T.shape}")
+    return T
+
+
+def _rigid_inv(T):
+    """the inverse of a rigid motion [R t; 0 1]: [R' -R' t; 0 1]"""
+    out = np.eye(4)
+    out[:3, :3] = T[:3, :3].T
+    out[:3, 3] = -T[:3, :3].T @ T[:3, 3]
+    return out
+
+
+def relative_pose(T_world_prev, T_world_cur) -> np.ndarray:
+    """(4,4) float64 inv(T_world_cur) @ T_world_prev: the pose of the previous camera in the current one, from the two cameras'
+    poses in one world (camera coordinates -> world coordinates, as KITTI's odometry poses are)"""
+    return _rigid_inv(_pose44(T_world_cur, "relative_pose")) @ _pose44(T_world_prev, "relative_pose")
+
+
+def read_kitti_poses(path, calib_text=None, camera: str = "P2") -> np.ndarray:
+    """KITTI odometry `poses/XX.txt` (a path or the text): 12 numbers per line, the (3,4) pose of cam0 in the first frame's cam0
+    -> (N,4,4) float64.  With `calib_text` (the sequence's calib.txt, a path or the text) the poses are moved to `camera`
+    (default the left colour camera P2), which lies x = P[0,3] / P[0,0] beside cam0 along the rectified x axis:
+    T' = S T inv(S) with S the translation by x; the first pose stays the identity."""
+    poses = []
+    for n, line in enumerate(_text(path).splitlines()):
+        if not line.strip():
+            continue
+        try:
+            vals = [float(v) for v in line.split()]
+        except ValueError:
+            raise ValueError(f"read_kitti_poses: line {n + 1} holds something that is not a number") from None
+        if len(vals) != 12:
+            raise ValueError(f"read_kitti_poses: line {n + 1} has {len(vals)} numbers, expected 12")
+        poses.append(_pose44(np.array(vals).reshape(3, 4), "read_kitti_poses"))
+    if not poses:
+        raise ValueError("read_kitti_poses: no pose in the text")
+    poses = np.stack(poses)
+    if calib_text is not None:
+        P = _kitti_numbers(_kitti_rows(calib_text), camera, 12).reshape(3, 4)
+        if not P[0, 0] > 0:
+            raise ValueError(f"read_kitti_poses: {camera} has no positive focal length")
+        S, Si = np.eye(4), np.eye(4)
+        S[0, 3] = P[0, 3] / P[0, 0]
+        Si[0, 3] = -S[0, 3]
+        poses = S @ poses @ Si
+    return poses
+
+
+def oxts_poses(rows, imu_to_velo, velo_to_cam, R_rect) -> np.ndarray:
+    """The OXTS records of a KITTI raw drive -> (N,4,4) float64 poses of the rectified reference camera relative to its first
+    frame, the raw devkit's construction restated: rows (N,>=6) = lat, lon (degrees), alt (metres), roll, pitch, yaw (radians),
+    the leading columns of `oxts/data/*.txt`.  Mercator with scale = cos(lat_0 pi / 180) and the earth radius 6378137:
+    x = scale lon pi r / 180, y = scale r log(tan((90 + lat) pi / 360)), z = alt;  R = Rz(yaw) Ry(pitch) Rx(roll);  the IMU's pose
+    relative to its first one, then the chain C = [R_rect 0; 0 1] velo_to_cam imu_to_velo into the rectified camera:
+    T_i = C inv(P_0) P_i inv(C).  imu_to_velo, velo_to_cam: (4,4) or (3,4); R_rect: (3,3) (R_rect_00)."""
+    rows = np.asarray(rows, np.float64)
+    if rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] < 6 or not np.isfinite(rows[:, :6]).all():
+        raise ValueError(f"oxts_poses: rows must be a finite (N,>=6) array, got shape {rows.shape}")
+    R_rect = np.asarray(R_rect, np.float64)
+    if R_rect.shape != (3, 3) or not np.isfinite(R_rect).all():
+        raise ValueError(f"oxts_poses: R_rect must be a finite (3,3) array, got shape {R_rect.shape}")
+    R0 = np.eye(4)
+    R0[:3, :3] = R_rect
+    C = R0 @ _pose44(velo_to_cam, "oxts_poses") @ _pose44(imu_to_velo, "oxts_poses")
+    Ci = np.linalg.inv(C)
+    scale = np.cos(rows[0, 0] * np.pi / 180.0)
+    out = np.empty((rows.shape[0], 4, 4))
+    P0i = t0 = None
+    for i, (lat, lon, alt, roll, pitch, yaw) in enumerate(rows[:, :6]):
+        P = np.eye(4)
+        t = np.array([scale * lon * np.pi * EARTH_RADIUS / 180.0,
+                      scale * EARTH_RADIUS * np.log(np.tan((90.0 + lat) * np.pi / 360.0)), alt])
+        t0 = t if t0 is None else t0
+        P[:3, 3] = t - t0              # (the first position is taken off before anything is rotated: no large numbers cancel)
+        cr, sr, cp, sp, cy, sy = np.cos(roll), np.sin(roll), np.cos(pitch), np.sin(pitch), np.cos(yaw), np.sin(yaw)
+        Rx = np.array([[1, 0, 0], [0, cr, -sr], [0, sr, cr]])
+        Ry = np.array([[cp, 0, sp], [0, 1, 0], [-sp, 0, cp]])
+        Rz = np.array([[cy, -sy, 0], [sy, cy, 0], [0, 0, 1]])
+        P[:3, :3] = Rz @ Ry @ Rx
+        if P0i is None:
+            P0i = _rigid_inv(P)
+        out[i] = C @ P0i @ P @ Ci
+    return out

@@ -535,7 +535,35 @@ class KittiInferenceLR(KittiInference):
         return r["filled"], r["valid"]
 
 
-class KittiInferenceGuided(KittiInference):
+class _HintsMixin:
+    """The hints of a guided network as an instance holds them: `guide` = (k, c) of `ops.cost_volume`, or
+    None for an unguided network; `hints4`, the ONE (1,Hc/4,Wc/4) buffer that every frame rewrites whole; and the two hooks of
+    `forward_frame` that hand both to the (graphed) hot path.  Shared by KittiInferenceGuided (hints from outside) and
+    KittiInferenceTemporal (hints from the previous frame)."""
+
+    guide = None
+    hints4 = None
+
+    def _take_guide(self, guide):
+        from .guided import guide_params
+        guide_params(type(self).__name__, guide)
+        if self.crop_height % 4 or self.crop_width % 4:
+            raise ValueError(f"{type(self).__name__}: the frame must be a multiple of 4 in both directions")
+        self.guide = (float(guide[0]), float(guide[1]))
+
+    def _hot_kwargs(self):
+        return {} if self.guide is None else {"guide": self.guide}
+
+    def _hot_inputs(self):
+        return {} if self.guide is None else {"hints4": self.hints4}
+
+    def _hints4_buffer(self, dev):
+        if self.hints4 is None:
+            self.hints4 = torch.zeros((1, self.crop_height // 4, self.crop_width // 4), device=dev, dtype=torch.float32)
+        return self.hints4
+
+
+class KittiInferenceGuided(_HintsMixin, KittiInference):
     """`disp = KittiInferenceGuided(model, ...)(left_rgb, right_rgb, hints)`: KittiInference (device I/O; eager or graph, fp32
     or reduced precision, rectify=) whose network is guided by sparse disparity hints: `__call__` and
     `stream(triples)` take a third item per frame.
@@ -553,21 +581,12 @@ class KittiInferenceGuided(KittiInference):
 
     def __init__(self, model, *args, lidar=None, guide=(10.0, 1.0), **kwargs):
         super().__init__(model, *args, **kwargs)
-        from .guided import guide_params
-        guide_params("KittiInferenceGuided", guide)
+        self._take_guide(guide)
         if lidar is not None and not isinstance(lidar, LidarCalib):
             raise TypeError(f"lidar= must be a geometry.LidarCalib, got {type(lidar)}")
-        if self.crop_height % 4 or self.crop_width % 4:
-            raise ValueError("KittiInferenceGuided: the frame must be a multiple of 4 in both directions")
-        self.lidar, self.guide = lidar, (float(guide[0]), float(guide[1]))
+        self.lidar = lidar
         self._proj = None            # the LidarProjector, built with the first scan
         self.hints4 = None           # (1,Hc/4,Wc/4): the frame's hints, rewritten whole by every frame
-
-    def _hot_kwargs(self):
-        return {"guide": self.guide}
-
-    def _hot_inputs(self):
-        return {"hints4": self.hints4}
 
     @torch.no_grad()
     def forward_frame(self, left, right, hints=None):
@@ -585,11 +604,6 @@ class KittiInferenceGuided(KittiInference):
     def __call__(self, left_rgb, right_rgb, hints, as_uint16: bool = False):
         self._check_format(as_uint16)
         return self._call_device(left_rgb, right_rgb, as_uint16, hints)
-
-    def _hints4_buffer(self, dev):
-        if self.hints4 is None:
-            self.hints4 = torch.zeros((1, self.crop_height // 4, self.crop_width // 4), device=dev, dtype=torch.float32)
-        return self.hints4
 
     def _upload(self, s, left_rgb, right_rgb, copy, hints):
         super()._upload(s, left_rgb, right_rgb, copy)
@@ -1031,6 +1045,149 @@ class KittiInferenceGround(KittiInference):
         names = ("label", "free_row", "free_disp", "bev")
         ops.ground_segment(pred, out["plane"], self.calib, grid=self.grid, outputs=names, out={k: out[k] for k in names}, **frame,
                            **self.segment_kw)
+
+
+FrameTemporal = collections.namedtuple("FrameTemporal", "disp var age")
+
+
+class _Temporal:
+    """What KittiInferenceTemporal keeps between the frames of a sequence, for images whose window is rows x cols: the state
+    (disp, var, age), the prediction (pred, var, age, hints) and the workspace of `ops.disp_reproject`.  Allocated once."""
+
+    def __init__(self, device, rows, cols):
+        from . import ops
+        f32 = dict(device=device, dtype=torch.float32)
+        self.state = {"disp": torch.zeros((rows, cols), **f32), "var": torch.zeros((rows, cols), **f32),
+                      "age": torch.zeros((rows, cols), device=device, dtype=torch.uint8)}
+        self.pred = {"pred": torch.zeros((rows, cols), **f32), "var": torch.zeros((rows, cols), **f32),
+                     "age": torch.zeros((rows, cols), device=device, dtype=torch.uint8), "hints": torch.zeros((rows, cols), **f32)}
+        self.workspace = ops.temporal_workspace(rows, cols, device)
+
+
+class KittiInferenceTemporal(_HintsMixin, KittiInference):
+    """`disp, var, age = KittiInferenceTemporal(model, calib, ...)(left_rgb, right_rgb, pose)`: KittiInference with device I/O
+    (required: the state lives where the disparity lies) over a SEQUENCE: `__call__` and
+    `stream(triples)` take the camera's world pose as a third item per frame -- a (4,4) or (3,4) array, camera coordinates ->
+    world coordinates, of the rectified left camera (`geometry.read_kitti_poses`, `geometry.oxts_poses`) -- and every frame
+    does, on the compute stream, in input order:
+      1. `ops.disp_reproject`: the state of the frame before, warped by the ego-motion between the two poses into this image;
+      2. with guide=(k, c): `ops.hints_to_quarter` of the prediction's `hints` into the instance's `hints4` buffer, which guides
+         the network as LiDAR hints guide KittiInferenceGuided's (zero hints, the first frame's, are the unguided network bit
+         for bit);
+      3. the network (eager or graph, fp32 or reduced precision; mask=None | "confidence" | "lr" as KittiInference3D has them);
+      4. `ops.temporal_fuse` of prediction and measurement into the new state.
+    calib: the geometry.StereoCalib of the images as they are handed in; with `rectify=` of the rectified pair, by default the
+    maps' own.  meas_var: the variance of a measurement in px^2, a scalar; q, occl, hint_min_age, min_disp, max_disp (default the
+    model's maxdisp): `ops.disp_reproject`'s; gate, var_max: `ops.temporal_fuse`'s; None means the named default of temporal.py
+    (meas_var 0.25, q 0, gate 3, occl (1, 1, 1.0), hint_min_age 1, min_disp 1/16, var_max inf).  pose=None, an image of another size, or
+    `reset()` drops the state: that frame is a first frame.  The state lives in two buffer sets and a workspace that the
+    instance owns, allocated with the first frame of a size; a frame hands out
+      disp float32 (h,w)   the fused disparity, +0.0: nothing     var float32 (h,w)   its variance in px^2
+      age  uint8   (h,w)   the frames since the pixel's filter started
+    in one copy and one synchronisation.  The reprojection takes the pose by value and is launched eagerly, in front of the
+    graph.  No accuracy is claimed for guide=: the repository ships no trained weights.  Not combined with the other subclasses."""
+
+    device_io = True
+    needs_device_io = "the state of the sequence lives on the device, next to the disparity"
+    has_uint16 = False
+    Frame = FrameTemporal
+
+    def __init__(self, model, calib=None, *args, guide=None, meas_var: float = None, q: float = None, gate: float = None,
+                 occl=None, hint_min_age: int = None, mask=None, mask_min: float = 0.5, radius: int = 1, tau: float = 1.0,
+                 min_disp: float = None, max_disp: float = None, var_max: float = None, **kwargs):
+        from . import temporal as T
+        super().__init__(model, *args, **kwargs)
+        name = type(self).__name__
+        if calib is None:
+            calib = getattr(self.rectify, "calib", None)
+            if calib is None:
+                raise ValueError(f"{name} needs calib=, or rectify= maps that carry the rectified pair's calibration")
+        self._take_mask(mask, mask_min, radius, tau)
+        if guide is not None:
+            if mask == "lr":
+                raise ValueError(f"{name}: guide= is not combined with mask='lr' (the second, mirrored pass has no hints of its own)")
+            self._take_guide(guide)
+        if max_disp is None:
+            max_disp = getattr(self.net, "maxdisp", None)
+            if max_disp is None:
+                raise ValueError(f"{name} needs max_disp=: the model has no `maxdisp`")
+        pick = lambda v, default: default if v is None else v      # noqa: E731
+        self.reproject_kw = dict(max_disp=float(max_disp), min_disp=float(pick(min_disp, T.TEMPORAL_MIN_DISP)),
+                                 occl=tuple(pick(occl, T.TEMPORAL_OCCL)), q=float(pick(q, T.TEMPORAL_Q)),
+                                 hint_min_age=pick(hint_min_age, T.TEMPORAL_HINT_MIN_AGE))
+        self.fuse_kw = dict(meas_var=float(pick(meas_var, T.TEMPORAL_MEAS_VAR)), min_disp=self.reproject_kw["min_disp"],
+                            gate=float(pick(gate, T.TEMPORAL_GATE)), var_max=float(pick(var_max, T.TEMPORAL_VAR_MAX)))
+        # the operators' ranges, up front
+        T.reproject_matrix(calib, np.eye(4))
+        T.reproject_scalars(name, ValueError, self.crop_height, self.crop_width, np.eye(3, 4), T._doffs(name, ValueError, calib, None),
+                            min_ratio=T.TEMPORAL_MIN_RATIO, **self.reproject_kw)
+        T.fuse_scalars(name, ValueError, **self.fuse_kw)
+        self.calib = calib
+        self._sets = {}              # (rows, cols) -> _Temporal
+        self._last = None            # (the pose, (src_y0, rows, cols)) of the frame that wrote the state; None: no state
+
+    def reset(self):
+        """drops the state: the next frame is a first frame"""
+        self._last = None
+
+    def __call__(self, left_rgb, right_rgb, pose, as_uint16: bool = False):
+        self._check_format(as_uint16)
+        return self._call_device(left_rgb, right_rgb, as_uint16, pose)
+
+    def _upload(self, s, left_rgb, right_rgb, copy, pose):
+        """host, in input order: also the frame's matrix G from the pose before and this one (None: a first frame)"""
+        from . import temporal as T
+        from .geometry import _pose44, relative_pose
+        if pose is not None:
+            pose = _pose44(pose, type(self).__name__)
+        super()._upload(s, left_rgb, right_rgb, copy)
+        src_y0, _, rows, cols = s.meta[3]
+        key = (src_y0, rows, cols)
+        s.G = None
+        if pose is not None and self._last is not None and self._last[1] == key:
+            # the window's row 0 is image row src_y0: the principal point moves up by as much
+            cal = self.calib if src_y0 == 0 else type(self.calib)(self.calib.f, self.calib.baseline, self.calib.cx,
+                                                                 self.calib.cy - src_y0, self.calib.doffs)
+            s.G = T.reproject_matrix(cal, relative_pose(self._last[0], pose))
+        self._last = None if pose is None else (pose, key)
+
+    def _set(self, s):
+        rows, cols = s.meta[3][2:]
+        if (rows, cols) not in self._sets:
+            self._sets[(rows, cols)] = _Temporal(s.device, rows, cols)
+        return self._sets[(rows, cols)]
+
+    def _net_pair(self, s, left, right, h, w):
+        """current stream, in front of the network: the prediction from the state of the frame before, and the frame's `hints4`"""
+        from . import ops
+        t = self._set(s)
+        if s.G is not None:
+            names = ("pred", "var", "age") + (("hints",) if self.guide is not None else ())
+            ops.disp_reproject(t.state, s.G, self.calib, outputs=names, out={k: t.pred[k] for k in names}, workspace=t.workspace,
+                               **self.reproject_kw)
+        if self.guide is not None:
+            if s.G is not None:
+                dst_y0, rows, cols = s.meta[3][1:]
+                ops.hints_to_quarter(t.pred["hints"], (self.crop_height, self.crop_width), (0, dst_y0, rows, cols),
+                                     maxdisp=self.net.maxdisp, out=self._hints4_buffer(s.device)[0])
+            else:
+                self._hints4_buffer(s.device).zero_()
+        return left, right, h, w
+
+    def _fields(self, rows, cols, as_uint16):
+        """the floats first, the bytes last: every field lies at a multiple of its element size"""
+        return [("disp", torch.float32, (rows, cols)), ("var", torch.float32, (rows, cols)), ("age", torch.uint8, (rows, cols))]
+
+    def _export(self, s, maps, out):
+        """current stream, behind the network: prediction and measurement into the state, the state into the record"""
+        from . import ops
+        t = self._set(s)
+        meas = maps[0].contiguous()
+        mask = maps[1].contiguous() if len(maps) > 1 else None
+        ops.temporal_fuse(t.pred if s.G is not None else None, meas, window=s.meta[3][1:], mask=mask, mask_min=self.mask_min,
+                          out=t.state, **self.fuse_kw)
+        for k, v in t.state.items():
+            out[k].copy_(v, non_blocking=True)
 
 
 class KittiInferenceColor(KittiInference):

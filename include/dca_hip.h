@@ -1122,6 +1122,77 @@ int dca_ground_segment(const float* d, const float* mask, const double* plane, u
                        float f, float fb, float cx, float doffs, float x_min, float inv_cell, float max_depth, int NX, int NZ,
                        hipStream_t stream);
 
+/* ---- temporal stereo (temporal.hip, temporal_math.h); inference only, no counterpart in the reference ---
+ * The STATE of a sequence is three dense (H,W) maps in image coordinates: disp fp32 (+0.0: nothing), var fp32 (px^2), age uint8
+ * (frames since the pixel's filter started).
+ *
+ * dca_disp_reproject: the previous state warped by the known ego-motion into the current left image.  g00 .. g23: the 3x4
+ * matrix G of temporal.reproject_matrix,  G = (1/f) [ K R A | K t / baseline ]  with K = [[f,0,cx],[0,f,cy],[0,0,1]],
+ * A = [[1,0,-cx],[0,1,-cy],[0,0,f]] and (R | t) the pose of the previous rectified left camera in the current one; formed in
+ * fp64 and rounded once by the host; exactly [I | 0] for the identity pose.  mask (H,W) fp32 or NULL: a source pixel takes
+ * part where mask >= mask_min.  In fp32, every operation rounded on its own (no fused multiply-adds), IEEE division, per
+ * SOURCE pixel (u = column, v = row) with disparity d:
+ *   den = d + doffs
+ *   x = ((g00 u + g01 v) + g02) + g03 den        (y and z likewise from rows 1 and 2;  z is Z_cur / Z_prev)
+ *   u' = x / z;  v' = y / z;  uf = floorf(u' + 0.5f);  vf = floorf(v' + 0.5f)
+ *   den' = den / z;  d' = den' - doffs
+ *   keep = d finite && d >= min_disp && mask && z >= min_ratio && 0 <= uf < W && 0 <= vf < H && d' >= min_disp && d' < max_disp
+ * All comparisons are made in float before anything is converted to int: a NaN fails them, an infinity or 1e30 fails them
+ * without overflowing an int (a point behind the camera has z <= 0 and fails z >= min_ratio, or, with min_ratio = 0 and
+ * z = 0, the range of d').  A kept pixel proposes the key  bits(den') << 32 | (0xFFFFFFFF - source index)  to the target
+ * word vf W + uf of the workspace, cleared to 0, with an agent-scope, relaxed 64-bit INTEGER fetch_max.  min_disp >= 0 and
+ * doffs >= 0 make den' >= 0, whose bits order as the floats do: the nearest surface wins, among equal den' the smallest
+ * source index, and the result does not depend on the order of arrival.
+ * Per target (r, c) with a non-zero key: denmax = the maximum of the winners' den' over rows r-ry .. r+ry and columns
+ * c-rx .. c+rx clipped to the image (the pixel itself included; an empty target counts as 0);
+ *   visible = den' + occl_px >= denmax       an ABSOLUTE threshold in pixels; rx = ry = 0 switches the test off
+ * It removes background seen through the cracks that forward splatting opens in a magnified foreground.  The payload is
+ * gathered from the winning source pixel src:  pred = d';  pred_var = var[src] / (z z) + q  with z recomputed from src by the
+ * expression above;  pred_age = min(age[src] + 1, 255);  hints = pred where pred_age >= hint_min_age, else +0.0.
+ * Outputs, (H,W) each, +0.0 / 0 where nothing is visible; any may be NULL, not all five:
+ *   pred fp32, pred_var fp32, pred_age uint8, hints fp32 (the hint map of dca_hints_to_quarter)
+ *   count  2 words: count[0] = visible targets, count[1] = kept sources; integer atomics, one per workgroup
+ * No output may overlap an input.  workspace: H W 64-bit words, 8-byte aligned, the caller's; after the call it holds the keys.
+ * THREE launches on the stream: clear the workspace and the counters; scatter; resolve (a workgroup stages a tile of the
+ * keys' high words with the halo in LDS and takes the window maximum along rows, then along columns; eight workgroups per CU
+ * walk the tiles).  No floating-point atomic.  Everything is passed BY VALUE, the twelve matrix entries too: a launch
+ * captured into a hipGraph keeps the pose it was captured with, so the operator is launched eagerly, next to the graph.
+ * Refused: NULL disp / var / age, non-positive H or W, H W >= 2^31, a matrix entry that is not finite, rx or ry outside
+ * [0, DCA_TEMPORAL_MAX_RADIUS], occl_px, q or min_ratio negative or not finite, doffs or min_disp negative or not finite,
+ * max_disp not finite or < min_disp, hint_min_age outside [0, 255], a NaN mask_min with a mask, NULL workspace, five NULL
+ * outputs.
+ *
+ * dca_temporal_fuse: prediction and measurement into a new state, ONE launch, per pixel.  pred, pred_var, pred_age: (rows,cols)
+ * dense, the outputs of dca_disp_reproject; pred NULL: no prediction anywhere (the first frame of a sequence).  meas: a frame
+ * map (Hc,Wc) read through the window rows x cols at frame row y0, column 0, as in dca_disp_export -- never copied; mask
+ * (Hc,Wc) fp32 or NULL and meas_var_map (Hc,Wc) fp32 or NULL are indexed like meas; with meas_var_map NULL the measurement's
+ * variance is the scalar meas_var.  With m the measurement and vm its variance:
+ *   m_ok = m finite && m >= min_disp && mask >= mask_min && 0 < vm < inf
+ *   p_ok = pred > 0 && 0 <= pred_var <= var_max
+ *   neither                 disp = +0.0   var = +0.0       age = 0
+ *   only m_ok               disp = m      var = vm         age = 0
+ *   only p_ok (coast)       disp = pred   var = pred_var   age = pred_age
+ *   both:  e = m - pred;  s = pred_var + vm
+ *     e e <= gate2 s        k = pred_var / s;  disp = pred + k e;  var = pred_var - k pred_var;  age = pred_age
+ *     otherwise             disp = m      var = vm         age = 0      (a new surface: the filter starts again)
+ * in fp32, every operation rounded on its own.  gate2 = +inf switches the gate off, var_max = +inf the variance limit.
+ * Outputs (rows,cols), any may be NULL, not all: disp, var fp32, age uint8, and innov fp32 = |e| where both are valid, else +0.0
+ * (a moving-object / mismatch cue).  disp / var / age may be the very buffers pred / pred_var / pred_age, or the buffers
+ * dca_disp_reproject read (that launch has finished): a thread reads its pixel before it writes it.
+ * Refused: NULL meas, no output, pred without pred_var and pred_age, a window outside the frame, without meas_var_map a
+ * meas_var that is not positive and finite, min_disp negative or not finite, gate2 or var_max negative or NaN, a NaN
+ * mask_min with a mask. */
+#define DCA_TEMPORAL_MAX_RADIUS 8
+int dca_disp_reproject(const float* disp, const float* var, const unsigned char* age, const float* mask, float mask_min,
+                       float g00, float g01, float g02, float g03, float g10, float g11, float g12, float g13, float g20,
+                       float g21, float g22, float g23, int H, int W, float doffs, float min_disp, float max_disp,
+                       float min_ratio, int rx, int ry, float occl_px, float q, int hint_min_age, float* pred, float* pred_var,
+                       unsigned char* pred_age, float* hints, long long* count, long long* workspace, hipStream_t stream);
+int dca_temporal_fuse(const float* pred, const float* pred_var, const unsigned char* pred_age, const float* meas,
+                      const float* mask, const float* meas_var_map, float meas_var, float* disp, float* var, unsigned char* age,
+                      float* innov, int Hc, int Wc, int y0, int rows, int cols, float min_disp, float mask_min, float gate2,
+                      float var_max, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
