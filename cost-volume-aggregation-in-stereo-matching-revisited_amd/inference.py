@@ -1021,6 +1021,15 @@ class KittiInferenceGround(KittiInference):
 
     def _export(self, s, maps, out):
         from . import ops
+        pred, frame = self._plane(s, maps, out)
+        names = ("label", "free_row", "free_disp", "bev")
+        ops.ground_segment(pred, out["plane"], self.calib, grid=self.grid, outputs=names, out={k: out[k] for k in names}, **frame,
+                           **self.segment_kw)
+
+    def _plane(self, s, maps, out):
+        """current stream: the filters, then `ops.ground_plane` into out["plane"] (and the disparity it read into out["disp"]);
+        returns that disparity and the frame keywords (max_disp, mask, mask_min, window, min_disp) of the stage behind"""
+        from . import ops
         h, w, c, (src_y0, dst_y0, rows, cols), _ = s.meta
         g = s.scratch("ground", lambda: _Ground(s.device, self.crop_height, self.crop_width, self.max_disp))
         pred = maps[0].contiguous()
@@ -1042,9 +1051,61 @@ class KittiInferenceGround(KittiInference):
         frame = dict(max_disp=self.max_disp, mask=mask, mask_min=self.mask_min, window=window, min_disp=self.min_disp)
         ops.ground_plane(pred, calib=self.calib, v0=src_y0, workspace=g.workspace,
                          out={"plane": out["plane"], "vdisp": g.vdisp[:rows]}, **frame, **self.plane_kw)
-        names = ("label", "free_row", "free_disp", "bev")
-        ops.ground_segment(pred, out["plane"], self.calib, grid=self.grid, outputs=names, out={k: out[k] for k in names}, **frame,
-                           **self.segment_kw)
+        return pred, frame
+
+
+FrameStixels = collections.namedtuple("FrameStixels", "disp plane count stixels energy")
+
+
+class KittiInferenceStixels(KittiInferenceGround):
+    """`disp, plane, count, stixels, energy = KittiInferenceStixels(model, calib, mask=None | "confidence" | "lr", ...)(left_rgb,
+    right_rgb)`: KittiInferenceGround's mask source, filters (`median=`, `speckle=`) and plane fit (`plane=`), followed on the
+    same stream by `ops.stixels` instead of the per-pixel segmentation: the image is cut into columns of
+    `width` pixels and cells of `row_step` rows, and every column bottom-up into ground / object / sky segments.
+      disp     float32 (h,w)                       the disparity the stage read
+      plane    float64 (16,)                       the plane record (`ground.PLANE_FIELDS`)
+      count    int32   (w // width,)               the segments of every column (also beyond max_segments); 0: no road plane
+      stixels  int32   (w // width, max_segments, 4)   bottom-up: first and last row of `disp`, class 0 / 1 / 2, disparity in
+                                                   sixteenths (-1: none); zero beyond `count`
+      energy   int64   (w // width,)               the column's least energy
+    `stixel.stixels_metric(stixels, count, plane, calib, width)` gives X, Z and the heights of foot and head in metres.
+    `stixel=`: a dict of further keywords of `ops.stixels` (min_valid, params).  A few hundred records per frame instead of a
+    label per pixel; the whole record comes back in one copy and one synchronisation per frame."""
+
+    needs_device_io = "the stixel stage runs on the device, next to the disparity"
+    Frame = FrameStixels
+    STIXEL_KEYS = ("min_valid", "params")
+
+    def __init__(self, model, calib=None, *args, width=None, row_step=None, max_segments=None, stixel=None, **kwargs):
+        from . import stixel as S
+        if "grid" in kwargs or "segment" in kwargs:
+            raise TypeError(f"{type(self).__name__} has no per-pixel segmentation: grid= and segment= belong to KittiInferenceGround")
+        super().__init__(model, calib, *args, **kwargs)
+        name = type(self).__name__
+        stixel = dict(stixel or {})
+        if set(stixel) - set(self.STIXEL_KEYS):
+            raise ValueError(f"{name}: stixel= takes {self.STIXEL_KEYS}, got {sorted(stixel)}")
+        # the operator's ranges, up front, for the frame (an image may be smaller: the operator checks it again)
+        _, self.width, self.row_step, _, self.max_segments, _, _, _ = S.grid_scalars(
+            name, ValueError, self.crop_height, self.crop_width, self.max_disp, S.STIXEL_WIDTH if width is None else width,
+            S.STIXEL_ROW_STEP if row_step is None else row_step, stixel.get("min_valid", S.STIXEL_MIN_VALID),
+            S.STIXEL_MAX_SEGMENTS if max_segments is None else max_segments, self.min_disp)
+        S.energy_params(name, ValueError, stixel.get("params"))
+        self.stixel_kw = stixel
+
+    def _fields(self, rows, cols, as_uint16):
+        """the 8-byte fields first: every field lies at a multiple of its element size"""
+        CS = cols // self.width
+        return [("plane", torch.float64, (16,)), ("energy", torch.int64, (CS,)), ("disp", torch.float32, (rows, cols)),
+                ("count", torch.int32, (CS,)), ("stixels", torch.int32, (CS, self.max_segments, 4))]
+
+    def _export(self, s, maps, out):
+        from . import ops
+        pred, frame = self._plane(s, maps, out)
+        ws = s.scratch("stixel", lambda: ops.stixel_workspace(self.crop_height, self.crop_width, s.device, self.width, self.row_step))
+        names = ("count", "stixels", "energy")
+        ops.stixels(pred, out["plane"], width=self.width, row_step=self.row_step, max_segments=self.max_segments, outputs=names,
+                    out={k: out[k] for k in names}, workspace=ws, **frame, **self.stixel_kw)
 
 
 FrameTemporal = collections.namedtuple("FrameTemporal", "disp var age")

@@ -2200,6 +2200,8 @@ from .highres import (  # noqa: E402,F401
 # ... and those for the ground plane (ground.py)
 from .ground import (  # noqa: E402,F401
     GROUND_PLANE_LEN, GROUND_WS_LEN, GROUND_SUMS_AT, GROUND_OUTPUTS, ground_workspace, ground_plane, ground_segment)
+# ... and the stixel world on top of it (stixel.py)
+from .stixel import STIXEL_OUTPUTS, stixel_workspace, stixels  # noqa: E402,F401
 # ... and those of temporal stereo (temporal.py)
 from .temporal import (  # noqa: E402,F401
     TEMPORAL_MAX_RADIUS, TEMPORAL_REPROJECT_OUTPUTS, TEMPORAL_FUSE_OUTPUTS, temporal_workspace, disp_reproject, temporal_fuse)

@@ -1122,6 +1122,70 @@ int dca_ground_segment(const float* d, const float* mask, const double* plane, u
                        float f, float fb, float cx, float doffs, float x_min, float inv_cell, float max_depth, int NX, int NZ,
                        hipStream_t stream);
 
+/* ---- stixels: per-column ground / object / sky segments from disparity (stixel.hip, stixel_math.h);
+ * inference only, no backward, no counterpart in the reference.  dcanet_amd/stixel.py holds the numpy restatement.
+ * d, mask, the window (y0, rows, cols), NB = max_disp, min_disp, mask_min and the VALID test with its quantisation q (the
+ * disparity in sixteenths) are those of dca_ground_plane; `plane` is its record (B, DCA_GROUND_PLANE_LEN), read from device
+ * memory: a32, b32, c32 are [0], [1], [2] rounded once to fp32.  Everything below is integer arithmetic in units of 1/16 px
+ * and (1/16 px)^2 but the one fp32 formula of g; there is no atomic of any kind: every output is bitwise defined.
+ *
+ * Cells.  CS = cols / width stixel columns (column s covers window columns [s width, (s + 1) width)) of H = rows / row_step cells
+ * (integer divisions); cell k = 0 is the BOTTOM cell and covers window rows [rows - (k + 1) row_step, rows - k row_step).  The
+ * cols % width columns on the right and the rows % row_step rows at the top are not covered.
+ *   q[k] = the lower median -- rank (n - 1) / 2 of the n values in ascending order -- of the q of the cell's valid pixels;
+ *          -1 when n < min_valid (min_valid >= 1)
+ *   g[k] = floorf(((a32 * float(u') + b32 * float(v')) + c32) * 16.0f + 0.5f) clamped in float to [-16 NB, 16 NB] (a NaN: the
+ *          lower end) at the cell's centre pixel: column s width + width / 2, row rows - (k + 1) row_step + row_step / 2,
+ *          u' = column - cols / 2, v' = row - rows / 2 (integer divisions throughout)
+ * Energy of a column.  A segmentation is a list of segments (kb, kt, c), kb <= kt, that covers the cells [0, H) bottom-up;
+ * c = 0 ground, 1 object, 2 sky.  With n, S1, S2 the count, the sum and the sum of squares of the valid q of a segment
+ * (a cell with q = -1 costs nothing in any class) and cp the class of the segment below, its cost is data + seg[c] + prior:
+ *   data   ground: sum min((q - g)^2, Tg);   sky: sum min(q^2, Ts);
+ *          object: S2 - 2 mu S1 + n mu^2 with mu = (2 S1 + n) / (2 n) (integer division: the mean rounded to a sixteenth);
+ *          n = 0: data 0 and mu = -1
+ *   prior  the bottom segment: first[c];  any other: T[cp][c], where a NEGATIVE entry forbids the pair
+ *          + far    for an object with 0 <= mu < mu_min (a bottom segment included)
+ *          + below  for an object directly on a ground segment with mu > g[kb] + eps   (its foot would lie under the road)
+ *          + hang   for an object directly on a ground segment with mu < g[kb] - eps   (it hangs in the air behind the road);
+ *                   both compare mu as it is, -1 for n = 0
+ * Recursion.  cost[kt][c] = min over kb <= kt and cp of cost[kb - 1][cp] + prior + data + seg[c] (kb = 0: no cp, nothing below).
+ * Ties go to the smallest kb, then the smallest cp: the unsigned minimum of  cost << 12 | kb << 2 | cp  with cp = 3 for kb = 0.
+ * The class of the top segment has the smallest cost[H - 1][c], then the smallest c; the back-pointers give the rest.  The prior
+ * depends on the segment's own values and the class below only, so the minimum is exact.  A single segment of any class is
+ * never forbidden: a segmentation always exists.
+ * Bound: with q < 2^14, H <= DCA_STIXEL_MAX_CELLS = 1024 and every constant <= DCA_STIXEL_MAX_CONST = 2^20 the object term is
+ * below 2^38, a column's ground or sky terms below 2^30 and all seg + prior below 2^33: every total stays below 2^39 < 2^50.
+ * A record of status 1, or without a calibration (not float([9]) > 0): no segmentation -- count 0, energy 0, the list zero,
+ * seg_class DCA_STIXEL_NO_CLASS, seg_disp +0.0; cells is written as defined.
+ * Outputs, any may be NULL, not all; only those given are written, every word of them on every call:
+ *   cells (B,H,CS,2) int16: q, g;   seg_class (B,H,CS) uint8: the class of every cell;
+ *   seg_disp (B,H,CS) fp32: float(mu) / 16.0f in the cells of an object with n > 0, +0.0 elsewhere
+ *   count (B,CS) int32: the number of segments, also when it exceeds max_segments;   energy (B,CS) int64: the minimum
+ *   stixels (B,CS,max_segments,4) int32, bottom-up, the lowest max_segments segments: the segment's first (upper) window row
+ *     rows - (kt + 1) row_step, its last (lower) window row rows - kb row_step - 1, c, and mu of an object (-1 for ground, sky
+ *     and n = 0); the entries from `count` on are zero
+ * ws: (B,H,CS,2) int16 of workspace, the caller's, where (q, g) pass from the first launch to the second; needed only when
+ * cells is NULL; never read before it is written.
+ * TWO launches (one when only cells is given): (1) one thread per cell; (2) one wave per stixel column: prefix sums in LDS,
+ * H dependent steps, the walk back in the same launch.  56 (H + 1) + 6 H bytes of LDS, 63.5 KB at H = 1024.  Nothing is
+ * allocated, nothing waits.
+ * Refused: NULL d / plane, no output, cells and ws both NULL, B outside [1, 65535], a window outside the frame, Hc Wc >= 2^31,
+ * rows or cols > DCA_GROUND_MAX_DIM, max_disp outside [8, DCA_GROUND_MAX_DISP], min_disp negative or not finite, a NaN mask_min
+ * with a mask, width outside [1, DCA_STIXEL_MAX_WIDTH], row_step outside [1, DCA_STIXEL_MAX_ROW_STEP], H outside
+ * [2, DCA_STIXEL_MAX_CELLS], CS < 1, min_valid outside [1, width row_step], max_segments outside [1, DCA_STIXEL_MAX_SEGMENTS],
+ * a constant outside [0, DCA_STIXEL_MAX_CONST], an entry of T outside [-1, DCA_STIXEL_MAX_CONST]. */
+#define DCA_STIXEL_MAX_WIDTH 16
+#define DCA_STIXEL_MAX_ROW_STEP 8
+#define DCA_STIXEL_MAX_CELLS 1024
+#define DCA_STIXEL_MAX_SEGMENTS 64
+#define DCA_STIXEL_MAX_CONST 1048576
+#define DCA_STIXEL_NO_CLASS 255
+int dca_stixels(const float* d, const float* mask, const double* plane, short* ws, short* cells, unsigned char* seg_class,
+                float* seg_disp, int* count, int* stixels, long long* energy, int B, int Hc, int Wc, int y0, int rows, int cols,
+                int max_disp, int width, int row_step, int min_valid, int max_segments, float min_disp, float mask_min, int Tg,
+                int Ts, int eps, int below, int hang, int mu_min, int far, int seg0, int seg1, int seg2, int first0, int first1,
+                int first2, int t00, int t01, int t02, int t10, int t11, int t12, int t20, int t21, int t22, hipStream_t stream);
+
 /* ---- temporal stereo (temporal.hip, temporal_math.h); inference only, no counterpart in the reference ---
  * The STATE of a sequence is three dense (H,W) maps in image coordinates: disp fp32 (+0.0: nothing), var fp32 (px^2), age uint8
  * (frames since the pixel's filter started).
