@@ -24,6 +24,10 @@ StereoCalib, filtered by the confidence or the left-right validity (DESIGN.md se
 `KittiInferenceColor` hands out the colour-coded disparity map (the KITTI devkit's colours, or grey) next to the disparity,
 coloured on the device in one launch behind any of the three (csrc/visualize.hip).
 
+`SGMInference` takes no model: semi-global matching on a census cost (csrc/sgm.hip) turns the uploaded
+uint8 pair into `(disp, valid)`, optionally through its own left-right check and the post-filter;
+`KittiInferenceGuided(model, sgm=...)` uses that map as the hints of the guided network, so guided stereo needs no LiDAR.
+
 Every class takes `rectify=` a geometry.RectifyMaps: the pair is then a RAW camera pair, rectified on the device in one
 launch (csrc/rectify.hip) in front of the unchanged chain."""
 from __future__ import annotations
@@ -335,8 +339,13 @@ class KittiInference:
         return [(name, dtype, (rows, cols)) for name in ("disp", "mask")[:self.nmaps]]
 
     # ---- device I/O: three stages per frame, each enqueued on the stream it is given --------------------------------
+    @property
+    def _device(self):
+        """the device the frames live on: the network's (SGMInference: its own)"""
+        return next(self.net.parameters()).device
+
     def _slot(self, i):
-        dev = next(self.net.parameters()).device
+        dev = self._device
         if self._frames is None:
             self._frames = torch.empty((2, 3, self.crop_height, self.crop_width), device=dev, dtype=torch.float32)
         while len(self._slots) <= i:
@@ -427,7 +436,7 @@ class KittiInference:
         return tuple(out.values()) if len(out) > 1 else out["disp"]
 
     def _call_device(self, left_rgb, right_rgb, as_uint16, *more):
-        dev = next(self.net.parameters()).device
+        dev = self._device
         cur = torch.cuda.current_stream(dev)
         s = self._slot(0)
         self._upload(s, left_rgb, right_rgb, cur, *more)
@@ -449,7 +458,7 @@ class KittiInference:
         if depth < 1:
             raise ValueError("depth >= 1")
         self._check_format(as_uint16)
-        dev = next(self.net.parameters()).device
+        dev = self._device
         compute = torch.cuda.current_stream(dev)
         if self._copy_stream is None:
             self._copy_stream = torch.cuda.Stream(dev)
@@ -563,6 +572,49 @@ class _HintsMixin:
         return self.hints4
 
 
+SGM_KEYS = ("max_disp", "paths", "P1", "P2", "uniqueness", "min_disp", "lr_tau")
+
+
+def _check_sgm(name, opts):
+    """the options of semi-global matching as a wrapper takes them (SGM_KEYS; the defaults are those of `ops.sgm_disparity`,
+    max_disp 192 and lr_tau 1.0) -> (the keywords of `ops.sgm_disparity`, lr_tau or None)"""
+    from . import sgm as _sgm
+    if not isinstance(opts, dict) or set(opts) - set(SGM_KEYS):
+        raise TypeError(f"{name}: the options of semi-global matching are a dict with keys out of {SGM_KEYS}, got {opts!r}")
+    kw = dict(max_disp=192, paths=_sgm.SGM_PATHS, P1=_sgm.SGM_P1, P2=_sgm.SGM_P2, uniqueness=_sgm.SGM_UNIQUENESS,
+              min_disp=_sgm.SGM_MIN_DISP)
+    kw.update({k: v for k, v in opts.items() if k != "lr_tau"})
+    kw = dict(zip(kw, _sgm.sgm_scalars(name, ValueError, _sgm.MIN_DIM, _sgm.MIN_DIM, **kw)))
+    lr_tau = opts.get("lr_tau", 1.0)
+    return kw, None if lr_tau is None else _check_tau(lr_tau)
+
+
+class _SGM:
+    """Per-slot buffers of semi-global matching for h x w images, allocated once: the workspace of `ops.sgm_disparity` and the
+    maps it writes -- the left disparity and its validity, with a left-right check also the mirrored right view"""
+
+    def __init__(self, device, h, w, max_disp, lr):
+        from . import ops
+        self.workspace = ops.sgm_workspace(h, w, max_disp, device)
+        names = ("disp", "valid") + (("disp_right_mirrored",) if lr else ())
+        self.out = {k: torch.empty((h, w), device=device, dtype=torch.float32) for k in names}
+
+
+def _sgm_maps(s, left, right, kw, lr_tau):
+    """current stream: (disp, valid), both float32 (h,w), of the uint8 pair as it lies in device memory:
+    `ops.sgm_disparity` under the keywords `kw`; with `lr_tau` its right view -- read from the same aggregation -- goes through
+    `ops.lr_consistency`, the two validities are multiplied and the disparity is +0.0 where the product is 0."""
+    from . import ops
+    h, w = int(left.shape[0]), int(left.shape[1])
+    buf = s.scratch(("sgm", h, w), lambda: _SGM(s.device, h, w, kw["max_disp"], lr_tau is not None))
+    r = ops.sgm_disparity(left, right, outputs=tuple(buf.out), out=buf.out, workspace=buf.workspace, **kw)
+    disp, valid = r["disp"], r["valid"]
+    if lr_tau is not None:
+        valid = valid * ops.lr_consistency(disp[None], r["disp_right_mirrored"][None], lr_tau, outputs=("valid",))["valid"][0]
+        disp = disp * valid
+    return disp, valid
+
+
 class KittiInferenceGuided(_HintsMixin, KittiInference):
     """`disp = KittiInferenceGuided(model, ...)(left_rgb, right_rgb, hints)`: KittiInference (device I/O; eager or graph, fp32
     or reduced precision, rectify=) whose network is guided by sparse disparity hints: `__call__` and
@@ -572,18 +624,28 @@ class KittiInferenceGuided(_HintsMixin, KittiInference):
                                on the device (read on the current stream)
       lidar=geometry.LidarCalib   the (N,4) float32 scan: staged through a `geometry.LidarProjector` and projected with
                                `ops.lidar_disparity` (hw of the calibration = the image's size)
+      sgm=dict(...)            NO third item: the hint map is computed from the pair itself by semi-global matching (DESIGN.md
+                               section 6r) on the uint8 images already in device memory, under the options of SGM_KEYS
+                               (`ops.sgm_disparity`'s, and lr_tau, default 1.0: its left-right check; None: none); an invalid
+                               pixel is +0.0, "nothing measured".  Not together with lidar=.
     `ops.hints_to_quarter` writes the frame's hints through the frame's placement into ONE buffer the instance owns, and
     `forward_frame` hands it to the (graphed) hot path: no allocation per frame.  guide = (k, c) of `ops.cost_volume`.  The
     record handed out is KittiInference's.  Not combined with the other subclasses."""
 
     device_io = True
     needs_device_io = "the hints are brought to the network's frame on the device"
+    sgm = None                   # the keywords of `ops.sgm_disparity`, with sgm=
+    sgm_lr_tau = None
 
-    def __init__(self, model, *args, lidar=None, guide=(10.0, 1.0), **kwargs):
+    def __init__(self, model, *args, lidar=None, sgm=None, guide=(10.0, 1.0), **kwargs):
         super().__init__(model, *args, **kwargs)
         self._take_guide(guide)
         if lidar is not None and not isinstance(lidar, LidarCalib):
             raise TypeError(f"lidar= must be a geometry.LidarCalib, got {type(lidar)}")
+        if sgm is not None:
+            if lidar is not None:
+                raise ValueError("KittiInferenceGuided: sgm= computes the hints from the pair, lidar= from a scan: give one of them")
+            self.sgm, self.sgm_lr_tau = _check_sgm("KittiInferenceGuided", sgm)
         self.lidar = lidar
         self._proj = None            # the LidarProjector, built with the first scan
         self.hints4 = None           # (1,Hc/4,Wc/4): the frame's hints, rewritten whole by every frame
@@ -601,12 +663,22 @@ class KittiInferenceGuided(_HintsMixin, KittiInference):
             raise RuntimeError("KittiInferenceGuided.forward_frame: no hints yet (hand them in, or go through __call__)")
         return super().forward_frame(left, right)
 
-    def __call__(self, left_rgb, right_rgb, hints, as_uint16: bool = False):
+    def __call__(self, left_rgb, right_rgb, hints=None, as_uint16: bool = False):
         self._check_format(as_uint16)
+        self._check_item(hints)
         return self._call_device(left_rgb, right_rgb, as_uint16, hints)
 
-    def _upload(self, s, left_rgb, right_rgb, copy, hints):
+    def _check_item(self, hints):
+        if (hints is None) != (self.sgm is not None):
+            raise TypeError("KittiInferenceGuided: with sgm= a frame is the pair alone, the hints are computed from it; without, a "
+                            "frame is (left, right, hints)")
+
+    def _upload(self, s, left_rgb, right_rgb, copy, hints=None):
+        self._check_item(hints)
         super()._upload(s, left_rgb, right_rgb, copy)
+        if self.sgm is not None:
+            s.hints = ("sgm", None)
+            return
         hw = tuple(s.meta[:2]) if self.rectify is None else tuple(self.rectify.dst_hw)
         if self.lidar is not None:
             if tuple(self.lidar.hw) != hw:
@@ -637,9 +709,100 @@ class KittiInferenceGuided(_HintsMixin, KittiInference):
             if self._proj is None:
                 self._proj = LidarProjector(self.lidar, s.device, capacity=max(1 << 18, int(np.asarray(item).shape[0])))
             item = self._proj(item)["disp"]
+        elif kind == "sgm":
+            item = _sgm_maps(s, left, right, self.sgm, self.sgm_lr_tau)[0]
         ops.hints_to_quarter(item, (self.crop_height, self.crop_width), s.meta[3], maxdisp=self.net.maxdisp,
                              out=self._hints4_buffer(s.device)[0])
         return left, right, h, w
+
+
+class SGMInference(KittiInference):
+    """`disp, valid = SGMInference(max_disp=192, paths=8, P1=10, P2=120, uniqueness=15, lr_tau=1.0, median=0, speckle=None)(
+    left_rgb, right_rgb)`: a disparity map without a network.  It takes NO model.  The uint8 pair is
+    uploaded through the slots of KittiInference (rectified first with rectify=), `ops.sgm_disparity` runs on it as it lies in
+    device memory, and with `lr_tau` (None: off) `ops.lr_consistency` cross-checks the left view against `disp_right_mirrored`,
+    which is read from the same aggregation: the two validities are multiplied and the disparity is +0.0 where the product is 0.
+    Then the post-filter of section 6l on the same stream: `ops.median_filter` (`median` = 3 or 5; 0: off) and
+    `ops.speckle_filter` (`speckle` = (max_size, max_diff); None: off) with that validity as the mask.  `disp` is float32 (h,w)
+    in pixels, `valid` float32 1.0 / 0.0; both come back in ONE copy of exactly their bytes and one synchronisation per frame;
+    `stream(pairs)` pipelines frames as for the other classes.  There is no frame to pad into: the maps are the image's own
+    size, images of different sizes may follow each other (the buffers grow to the largest seen), each within the limits of
+    `ops.sgm_disparity`.  No uint16 form.  device: where the frames live."""
+
+    nmaps = 2
+    device_io = True
+    needs_device_io = "semi-global matching runs on the device only"
+    has_uint16 = False
+    mask_min = 0.5               # the post-filter's threshold on the validity
+
+    def __init__(self, max_disp: int = 192, paths: int = 8, P1: int = 10, P2: int = 120, uniqueness: int = 15, lr_tau=1.0,
+                 median: int = 0, speckle=None, rectify=None, *, min_disp: int = 1, device="cuda"):
+        if rectify is not None and not all(hasattr(rectify, k) for k in ("src_hw", "dst_hw", "X", "Y", "valid")):
+            raise TypeError(f"rectify= must be a geometry.RectifyMaps, got {type(rectify)}")
+        self.sgm, self.lr_tau = _check_sgm("SGMInference", dict(max_disp=max_disp, paths=paths, P1=P1, P2=P2, uniqueness=uniqueness,
+                                                                min_disp=min_disp, lr_tau=lr_tau))
+        self.median, self.speckle = _check_post(median, speckle)
+        self.net, self.graph, self.dtype, self._graphed = None, False, None, None
+        self.rectify = rectify
+        self._dev = torch.device(device)
+        self.crop_height, self.crop_width = (7, 7) if rectify is None else tuple(rectify.dst_hw)      # the largest image so far
+        self._frames, self._slots, self._copy_stream = None, [], None
+
+    @property
+    def _device(self):
+        return self._dev
+
+    def _fields(self, rows, cols, as_uint16):
+        return [("disp", torch.float32, (rows, cols)), ("valid", torch.float32, (rows, cols))]
+
+    def _slot(self, i):
+        while len(self._slots) <= i:
+            self._slots.append(_Slot(self._device, _nbytes(self._fields(self.crop_height, self.crop_width, False))))
+            self._slots[-1].room = (self.crop_height, self.crop_width)
+        return self._slots[i]
+
+    def _grow(self, s, h, w):
+        """room for h x w maps in THIS slot, whose previous frame has been handed out (rare: the largest image so far grew)"""
+        self.crop_height, self.crop_width = max(h, self.crop_height), max(w, self.crop_width)
+        if s.room == (self.crop_height, self.crop_width):
+            return
+        s.done.synchronize()                     # the read-back out of the old buffers
+        n = _nbytes(self._fields(self.crop_height, self.crop_width, False))
+        s.out_dev = torch.empty(n, device=s.device, dtype=torch.uint8)
+        s.out_pin = torch.empty(n, dtype=torch.uint8).pin_memory()
+        s._scratch.pop("post", None)             # the post-filter's buffers are sized for the largest image too
+        s.room = (self.crop_height, self.crop_width)
+
+    def _upload(self, s, left_rgb, right_rgb, copy):
+        if self.rectify is None and np.ndim(left_rgb) == 3:
+            self._grow(s, *np.shape(left_rgb)[:2])
+        super()._upload(s, left_rgb, right_rgb, copy)
+        h, w = s.meta[:2] if self.rectify is None else self.rectify.dst_hw
+        s.meta = s.meta[:3] + ((0, 0, h, w),) + s.meta[4:]         # no frame: the window is the image
+
+    @torch.no_grad()
+    def _compute(self, s, compute, as_uint16):
+        """`compute` stream: [rectify ->] semi-global matching [-> left-right check] [-> post-filter] into the slot's device output"""
+        from . import ops
+        h, w, c, _, off = s.meta
+        n = h * w * c
+        with torch.cuda.stream(compute):
+            compute.wait_event(s.uploaded)
+            compute.wait_event(s.done)               # the previous read-back of this slot's output
+            left, right = s.in_dev[:n].view(h, w, c), s.in_dev[off:off + n].view(h, w, c)
+            if self.rectify is not None:
+                h, w = self.rectify.dst_hw
+                left, right = ops.rectify_pair(left, right, self.rectify, out=s.rectified(h, w, c))
+            s.left, s.out_hw = left, (h, w)
+            s.set_fields(self._fields(h, w, False))
+            disp, valid = _sgm_maps(s, left, right, self.sgm, self.lr_tau)
+            if self.median or self.speckle is not None:
+                # as KittiInferenceFiltered: without a speckle filter, max_size 0 keeps every active pixel
+                _post_filter(self, s, disp, valid, (0, h, w), s.dev["disp"], self.speckle or (0, 0.0), False, s.dev["valid"])
+            else:
+                s.dev["disp"].copy_(disp)
+                s.dev["valid"].copy_(valid)
+            s.computed.record(compute)
 
 
 def _check_post(median, speckle):

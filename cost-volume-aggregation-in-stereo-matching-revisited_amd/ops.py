@@ -2202,6 +2202,8 @@ from .ground import (  # noqa: E402,F401
     GROUND_PLANE_LEN, GROUND_WS_LEN, GROUND_SUMS_AT, GROUND_OUTPUTS, ground_workspace, ground_plane, ground_segment)
 # ... and the stixel world on top of it (stixel.py)
 from .stixel import STIXEL_OUTPUTS, stixel_workspace, stixels  # noqa: E402,F401
+# ... and semi-global matching, the disparity source without a network (sgm.py)
+from .sgm import SGM_OUTPUTS, sgm_workspace, sgm_census, sgm_disparity  # noqa: E402,F401
 # ... and those of temporal stereo (temporal.py)
 from .temporal import (  # noqa: E402,F401
     TEMPORAL_MAX_RADIUS, TEMPORAL_REPROJECT_OUTPUTS, TEMPORAL_FUSE_OUTPUTS, temporal_workspace, disp_reproject, temporal_fuse)

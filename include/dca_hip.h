@@ -1257,6 +1257,71 @@ int dca_temporal_fuse(const float* pred, const float* pred_var, const unsigned c
                       float* innov, int Hc, int Wc, int y0, int rows, int cols, float min_disp, float mask_min, float gate2,
                       float var_max, hipStream_t stream);
 
+/* ---- semi-global matching on a census cost (sgm.hip, sgm_math.h; Hirschmueller 2008, Zabih & Woodfill
+ * 1994): a disparity source that needs no weights.  Inference only, no counterpart in the reference.  dcanet_amd/sgm.py holds
+ * the numpy restatement.  Integer arithmetic from the first byte to the last: no tolerance, no atomic of any kind, every output
+ * bitwise defined and independent of the order of execution.
+ *
+ * Inputs.  One rectified pair of uint8 images, (H,W) grey (C = 1) or interleaved (H,W,C) with C = 3 or 4 (a fourth channel is
+ * ignored).  Colour is reduced to grey by  g = (77 R + 150 G + 29 B + 128) >> 8.
+ * Limits: DCA_SGM_MIN_DIM = 7 <= H, W <= DCA_SGM_MAX_DIM = 8192, D = max_disp an integer in [DCA_SGM_MIN_DISP, DCA_SGM_MAX_DISP]
+ * = [8, 256], H W D < 2^30.  D need not be a multiple of anything.
+ *
+ * Census.  The window is 9 wide and 7 high.  Each pixel gets DCA_SGM_CENSUS_BITS = 62 bits in a uint64: the neighbours are
+ * visited row-major, dy = -3..3 outer, dx = -4..4 inner, the centre skipped; the first neighbour is bit 61, the last bit 0.  A
+ * bit is 1 iff the neighbour lies inside the image and g(neighbour) < g(centre).
+ *
+ * Matching cost.  C(y,x,d) = popcount(cL(y,x) ^ cR(y,x-d)) for x - d >= 0, and DCA_SGM_COST_OUT = 62 otherwise.
+ *
+ * Paths.  paths = 4: the predecessor offsets r = (dy,dx) in {(0,+1), (0,-1), (+1,0), (-1,0)};  paths = 8 adds (+1,+1), (+1,-1),
+ * (-1,+1), (-1,-1).  If p - r lies outside the image, L_r(p,d) = C(p,d): there is no wrap-around.  Otherwise, with
+ * m = min_k L_r(p-r,k):
+ *   L_r(p,d) = C(p,d) + min( L_r(p-r,d), L_r(p-r,d-1) + P1 [d >= 1], L_r(p-r,d+1) + P1 [d <= D-2], m + P2 ) - m
+ * S = the sum over r of L_r.  1 <= P1 <= P2 <= DCA_SGM_MAX_P = 4095.  Then C <= L_r <= 62 + P2 and S <= 8 * 4157 = 33256: every
+ * L_r and S fits uint16 and nothing saturates anywhere.
+ *
+ * Left disparity.  d* = the lowest index of min_d S(p,d), s = S(p,d*).  Uniqueness u, an integer in 0..99: the pixel passes iff
+ * every k with |k - d*| > 1 has  S(p,k) * (100 - u) >= 100 * s  (u = 0 switches the test off).  Sub-pixel step in sixteenths: if
+ * 0 < d* < D-1 and den = S(d*-1) + S(d*+1) - 2 s > 0 then
+ *   off = (16 * (S(d*-1) - S(d*+1)) + 17 * den) / (2 * den) - 8
+ * (the numerator is at least den > 0, so the division is one of positive integers; off lies in [-8, 8] and is 8 (S(d*-1) -
+ * S(d*+1)) / den rounded half up), otherwise off = 0;  q = 16 d* + off.  valid = passes && d* >= min_disp, min_disp an integer
+ * in 0..D-1.   disp = float(q) / 16.0f where valid, +0.0 elsewhere (one exact fp32 division);  cost = s, for every pixel.
+ *
+ * Right-view disparity, from the same S.  The bins present at right-image pixel (y,x) are k < min(D, W - x) with
+ * S_R(y,x,k) = S(y,x+k,k): the lowest argmin, then the same sub-pixel rule when both neighbours are present.  No uniqueness
+ * test; every pixel is written.  disp_right is in the right image's own coordinates, disp_right_mirrored holds column i at index
+ * W-1-i (the second argument of dca_lr_consistency).
+ *
+ * dca_sgm_workspace_bytes(H, W, max_disp): the bytes of `workspace`, 16 H W for the census of both images (2,H,W) uint64
+ * followed by 2 H W D for S (H,W,D) uint16, d innermost; -1 for sizes outside the limits.  The workspace is the caller's,
+ * 8-byte aligned, and may hold garbage: nothing is read before it is written.
+ * dca_sgm_census: grey conversion and census of both images in ONE launch (a tile with its 4 x 3 halo in LDS) into
+ * census (2,H,W) uint64, left first.
+ * dca_sgm_disparity: the census launch, then ONE launch per path -- one wave per scanline (a row for the horizontal paths; a
+ * start column for the others, the column moving by dx per row and starting a new path where it re-enters on the other side),
+ * each lane holding ceil(D / 64) consecutive bins, the cost formed from the census words as the scan goes and never stored; the
+ * first path writes S, the others add to it -- then the winner-take-all launch of the left view and, only when disp_right or
+ * disp_right_mirrored is given, that of the right view.  Outputs (H,W), any may be NULL, not all: disp fp32, valid fp32
+ * 1.0 / 0.0, cost int32, disp_right fp32, disp_right_mirrored fp32; only those given are written, every word of them.  All
+ * launches go on `stream`; nothing is allocated, nothing waits.
+ * Refused: NULL images, census or workspace, a workspace or a census that is not 8-byte aligned, C not 1, 3 or 4, H, W or
+ * max_disp outside the limits, H W D >= 2^30, paths not 4 or 8, P1 < 1, P1 > P2, P2 > DCA_SGM_MAX_P, uniqueness outside
+ * [0, 99], min_disp outside [0, D-1], no output. */
+#define DCA_SGM_MIN_DIM 7
+#define DCA_SGM_MAX_DIM 8192
+#define DCA_SGM_MIN_DISP 8
+#define DCA_SGM_MAX_DISP 256
+#define DCA_SGM_MAX_P 4095
+#define DCA_SGM_CENSUS_BITS 62
+#define DCA_SGM_COST_OUT 62
+long dca_sgm_workspace_bytes(int H, int W, int max_disp);
+int dca_sgm_census(const unsigned char* left, const unsigned char* right, unsigned long long* census, int H, int W, int C,
+                   hipStream_t stream);
+int dca_sgm_disparity(const unsigned char* left, const unsigned char* right, void* workspace, float* disp, float* valid,
+                      int* cost, float* disp_right, float* disp_right_mirrored, int H, int W, int C, int max_disp, int paths,
+                      int P1, int P2, int uniqueness, int min_disp, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
