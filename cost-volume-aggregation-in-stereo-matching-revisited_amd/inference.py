@@ -29,7 +29,13 @@ uint8 pair into `(disp, valid)`, optionally through its own left-right check and
 `KittiInferenceGuided(model, sgm=...)` uses that map as the hints of the guided network, so guided stereo needs no LiDAR.
 
 Every class takes `rectify=` a geometry.RectifyMaps: the pair is then a RAW camera pair, rectified on the device in one
-launch (csrc/rectify.hip) in front of the unchanged chain."""
+launch (csrc/rectify.hip) in front of the unchanged chain.
+
+Two layers.  `FramePipeline` is the device I/O of a frame without any network: slots, upload, the head of
+the compute stage (waits, `rectify=`), read-back, result, `stream`; a subclass fills one hook, `_fill`, which turns the uint8 pair
+in device memory into the frame's record.  `KittiInference` fills it with the network and its fixed frame, `SGMInference` with
+semi-global matching.  The stages behind the network (filters, geometry, ground, stixels, colour) share one preamble,
+`_StageMixin._stage_maps`."""
 from __future__ import annotations
 
 import collections
@@ -127,6 +133,22 @@ def imagenet_lut() -> torch.Tensor:
     return torch.stack([lut, lut]).contiguous()
 
 
+class _Frame(collections.namedtuple("_Frame", "h w c src_y0 dst_y0 rows cols off")):
+    """The frame in a slot: the h x w x c uint8 images as they were uploaded, the right one `off` bytes behind the left; and the
+    placement of the image (the rectified one, with rectify=) in the network's frame as `placement` gives it -- rows x cols
+    pixels from source row src_y0 land at frame row dst_y0.  Without a network's frame the window is the image itself."""
+    __slots__ = ()
+
+    @property
+    def window(self):
+        """(y0, rows, cols): where the image lies in the frame's maps"""
+        return self.dst_y0, self.rows, self.cols
+
+    @property
+    def placement(self):
+        return self.src_y0, self.dst_y0, self.rows, self.cols
+
+
 class _Slot:
     """Buffers and events of one frame in flight (device I/O): pinned + device uint8 inputs that grow on demand, and ONE device +
     ONE pinned byte buffer for what the frame hands out, sized once for the class's worst case.  The record of the frame in
@@ -140,7 +162,8 @@ class _Slot:
         self.out_pin = torch.empty(out_capacity, dtype=torch.uint8).pin_memory()
         self.dev, self.pin, self.out_bytes = {}, {}, 0
         self.uploaded, self.computed, self.done = (torch.cuda.Event() for _ in range(3))
-        self.meta = None             # (h, w, c, placement, offset of the right image) of the frame in the slot
+        self.frame = None            # the _Frame in the slot
+        self.item = None             # what the frame carries beside the pair, as the class's `_upload` left it (hints, a matrix)
         self.out_hw = None           # the size of the maps the frame hands out (the window's; HighResInference: the image's)
         self.copy = None             # the stream the record went out on
         self.rect = {}               # channels -> the rectified pair (rectify=), allocated once for the maps' dst_hw
@@ -155,6 +178,17 @@ class _Slot:
             self.in_pin = torch.empty(off + nbytes, dtype=torch.uint8).pin_memory()
             self.in_dev = torch.empty(off + nbytes, device=self.device, dtype=torch.uint8)
         return off
+
+    def reserve_output(self, nbytes, drop=()):
+        """room for a record of nbytes, after the slot's previous frame has been handed out (rare: SGMInference's largest image
+        grew); `drop`: the scratch keys whose buffers were sized with the record, to be built again"""
+        if self.out_dev.numel() >= nbytes:
+            return
+        self.done.synchronize()                      # the read-back out of the old buffers
+        self.out_dev = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+        self.out_pin = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        for key in drop:
+            self._scratch.pop(key, None)
 
     def rectified(self, hd, wd, c):
         """the two (hd,wd,c) uint8 images `ops.rectify_pair` writes, the second at a multiple of 16 bytes (vector stores)"""
@@ -187,6 +221,19 @@ def _nbytes(fields):
     return sum(math.prod(shape) * dtype.itemsize for _, dtype, shape in fields)
 
 
+def _disp_valid(rows, cols):
+    """the record of the classes that hand out a float32 disparity and its float32 1.0 / 0.0 validity"""
+    return [("disp", torch.float32, (rows, cols)), ("valid", torch.float32, (rows, cols))]
+
+
+def _maps2d(maps):
+    """the frame's disparity and its mask (None: none), contiguous, as 2-D views"""
+    pred = maps[0].contiguous()
+    pred = pred.view(pred.shape[-2:])
+    mask = maps[1] if len(maps) > 1 else None
+    return pred, None if mask is None else mask.contiguous().view_as(pred)
+
+
 def _check_tau(tau) -> float:
     tau = float(tau)
     if not (0.0 <= tau < float("inf")):
@@ -194,7 +241,188 @@ def _check_tau(tau) -> float:
     return tau
 
 
-class KittiInference:
+class FramePipeline:
+    """The frame pipeline of device I/O, apart from any network: slots of buffers for the frames in flight, and three stages per
+    frame, each enqueued on the stream it is given -- `_upload` (the uint8 pair into pinned memory and on to the device),
+    `_compute` (the waits, the two views of the pair, `rectify=`, then the class's own work) and `_readback` (the frame's record
+    in ONE copy of exactly its bytes) -- with `_result`, the one synchronisation of a frame, `__call__` and `stream` on top.
+
+    What a subclass states: `_device`, where the frames live; `_fields`, the record a frame hands out; `_fill`, which turns the
+    uint8 pair in device memory into that record; and, where it has a frame of fixed size to place the image in, `_place` and
+    `_room`.  KittiInference puts a network's frame there; SGMInference has none."""
+
+    out_scale = 1                # the maps handed out are at most this many times the room in each direction (HighResInference)
+    device_io = True             # what `device_io=None` means for the class
+    needs_device_io = None       # the reason why the class refuses device_io=False, if it does
+    has_uint16 = True            # False: the record has no uint16 form, `as_uint16=True` is refused
+    Frame = None                 # a namedtuple type to hand the fields out in, by name; None: a tuple (one field: itself)
+
+    def __init__(self, device=None, device_io: bool = None, rectify=None):
+        if rectify is not None and not all(hasattr(rectify, k) for k in ("src_hw", "dst_hw", "X", "Y", "valid")):
+            raise TypeError(f"rectify= must be a geometry.RectifyMaps, got {type(rectify)}")
+        if device_io is not None:
+            self.device_io = device_io
+        if self.needs_device_io and not self.device_io:
+            raise ValueError(f"{type(self).__name__} needs device_io=True: {self.needs_device_io}")
+        self.rectify = rectify
+        self._dev = None if device is None else torch.device(device)
+        self._slots = []
+        self._copy_stream = None
+
+    @property
+    def _device(self):
+        """the device the frames live on"""
+        return self._dev
+
+    def _room(self):
+        """(rows, cols): the largest window a frame can have; the slots' records and the post-filter's buffers are sized for it"""
+        raise NotImplementedError
+
+    def _place(self, h, w):
+        """(src_y0, dst_y0, rows, cols) of an h x w image (the rectified one, with rectify=).  Here: the window is the image"""
+        return 0, 0, h, w
+
+    def _fields(self, rows, cols, as_uint16):
+        """the record of a frame whose maps are rows x cols: (name, dtype, shape) in the order they lie in the slot's buffer"""
+        raise NotImplementedError
+
+    def _fill(self, s, left, right, h, w, as_uint16):
+        """current stream: the (h,w,c) uint8 pair as it lies in device memory (rectified, with rectify=) -> the frame's record:
+        lays it out (`s.set_fields`) and writes every field of `s.dev`"""
+        raise NotImplementedError
+
+    def _slot(self, i):
+        while len(self._slots) <= i:
+            rows, cols = self._room()
+            self._slots.append(_Slot(self._device, _nbytes(self._fields(rows * self.out_scale, cols * self.out_scale, False))))
+        return self._slots[i]
+
+    def _upload(self, s, left_rgb, right_rgb, copy):
+        """host: the pair into the slot's pinned buffer; `copy` stream: pinned -> device"""
+        left_rgb, right_rgb = np.ascontiguousarray(left_rgb), np.ascontiguousarray(right_rgb)
+        if left_rgb.dtype != np.uint8 or right_rgb.dtype != np.uint8 or left_rgb.ndim != 3 \
+                or left_rgb.shape[2] not in (3, 4) or left_rgb.shape != right_rgb.shape:
+            raise ValueError(f"device_io takes two (H,W,3) or (H,W,4) uint8 images of one shape, got {left_rgb.dtype} "
+                             f"{left_rgb.shape} and {right_rgb.dtype} {right_rgb.shape}")
+        h, w, c = left_rgb.shape
+        if self.rectify is not None and (h, w) != tuple(self.rectify.src_hw):
+            raise ValueError(f"rectify= was built for {self.rectify.src_hw[0]} x {self.rectify.src_hw[1]} raw images, got "
+                             f"{h} x {w}")
+        place = self._place(*((h, w) if self.rectify is None else self.rectify.dst_hw))
+        n = h * w * c
+        off = s.reserve_input(n)
+        s.uploaded.synchronize()                     # the previous copy out of the pinned buffer
+        pin = s.in_pin.numpy()
+        pin[:n] = left_rgb.reshape(-1)
+        pin[off:off + n] = right_rgb.reshape(-1)
+        with torch.cuda.stream(copy):
+            copy.wait_event(s.computed)              # the previous frame of this slot has read its input
+            s.in_dev[:off + n].copy_(s.in_pin[:off + n], non_blocking=True)      # one copy for the pair
+            s.uploaded.record(copy)
+        s.frame, s.item = _Frame(h, w, c, *place, off), None
+
+    @torch.no_grad()
+    def _compute(self, s, compute, as_uint16):
+        """`compute` stream: [rectify ->] `_fill` into the slot's device output"""
+        from . import ops
+        f = s.frame
+        h, w, n = f.h, f.w, f.h * f.w * f.c
+        with torch.cuda.stream(compute):
+            compute.wait_event(s.uploaded)
+            compute.wait_event(s.done)               # the previous read-back of this slot's output
+            left, right = s.in_dev[:n].view(h, w, f.c), s.in_dev[f.off:f.off + n].view(h, w, f.c)
+            if self.rectify is not None:
+                h, w = self.rectify.dst_hw
+                left, right = ops.rectify_pair(left, right, self.rectify, out=s.rectified(h, w, f.c))
+            s.left, s.out_hw = left, (f.rows, f.cols)
+            self._fill(s, left, right, h, w, as_uint16)
+            s.computed.record(compute)
+
+    def _readback(self, s, copy):
+        """`copy` stream: the frame's record, device output -> pinned, in one copy of exactly its bytes"""
+        n = s.out_bytes
+        with torch.cuda.stream(copy):
+            copy.wait_event(s.computed)
+            s.out_pin[:n].copy_(s.out_dev[:n], non_blocking=True)
+            s.done.record(copy)
+        s.copy = copy
+
+    def _rest(self, s, head):
+        """host, after the frame's wait: sends for what the frame hands out beyond its record `head` (the fields in the pinned
+        buffer) and returns a function that waits for it and gives it as {name: array}.  Here: nothing, an empty dict.
+        KittiInference3D: the vertices."""
+        return dict
+
+    def _result(self, s):
+        """host: the one synchronisation of a frame, then a copy of every field out of the pinned buffer"""
+        s.done.synchronize()
+        rest = self._rest(s, s.pin)                  # (in flight while the host copies the fields)
+        out = {name: v.numpy().copy() for name, v in s.pin.items()}
+        out.update(rest())
+        if self.Frame is not None:
+            return self.Frame(*(out.get(name) for name in self.Frame._fields))
+        return tuple(out.values()) if len(out) > 1 else out["disp"]
+
+    def _call_device(self, left_rgb, right_rgb, as_uint16, *more):
+        dev = self._device
+        cur = torch.cuda.current_stream(dev)
+        s = self._slot(0)
+        self._upload(s, left_rgb, right_rgb, cur, *more)
+        self._compute(s, cur, as_uint16)
+        self._readback(s, cur)
+        return self._result(s)
+
+    def _check_format(self, as_uint16):
+        if as_uint16 and not self.has_uint16:
+            raise TypeError(f"{type(self).__name__} hands out no uint16 form of its frames: as_uint16=True is not for it")
+
+    def stream(self, pairs, depth: int = 2, as_uint16: bool = False):
+        """Generator over an iterable of (left_rgb, right_rgb) uint8 pairs (sizes may differ as long as each fits the
+        frame): yields what `__call__` gives for each pair, byte for byte, in input order, `depth` frames in flight.  A copy
+        stream beside the compute stream carries the upload of frame i+1 and the read-back of frame i-1 while frame i
+        computes."""
+        if not self.device_io:
+            raise RuntimeError("stream() needs KittiInference(..., device_io=True)")
+        if depth < 1:
+            raise ValueError("depth >= 1")
+        self._check_format(as_uint16)
+        dev = self._device
+        compute = torch.cuda.current_stream(dev)
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(dev)
+        copy = self._copy_stream
+        copy.wait_stream(compute)
+        inflight = collections.deque()               # slots in input order; [slot, read-back enqueued]
+        try:
+            for i, (left_rgb, right_rgb, *more) in enumerate(pairs):      # (more: what a subclass's `_upload` takes per frame)
+                if len(inflight) == depth:               # slot i % depth is the oldest frame's: hand that frame out first
+                    old = inflight.popleft()
+                    if not old[1]:
+                        self._readback(old[0], copy)
+                    yield self._result(old[0])
+                s = self._slot(i % depth)
+                self._upload(s, left_rgb, right_rgb, copy, *more)
+                self._compute(s, compute, as_uint16)
+                # the read-back of the frame before goes behind this upload on the copy stream: it waits for that frame's
+                # compute, and an upload queued behind it would wait too
+                if inflight and not inflight[-1][1]:
+                    self._readback(inflight[-1][0], copy)
+                    inflight[-1][1] = True
+                inflight.append([s, False])
+            while inflight:
+                old = inflight.popleft()
+                if not old[1]:
+                    self._readback(old[0], copy)
+                yield self._result(old[0])
+        finally:
+            compute.wait_stream(copy)                # later work on the compute stream may reuse slot 0 (`__call__`)
+
+    def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray, as_uint16: bool = False):
+        self._check_format(as_uint16)
+        return self._call_device(left_rgb, right_rgb, as_uint16)
+
+
+class KittiInference(FramePipeline):
     """`disp = KittiInference(model)(left_rgb, right_rgb)`: my_img.py:89-110 `my()` without the file I/O.
 
     `model` is a GwcNet (or the nn.DataParallel wrapper the reference builds, my_img.py:37) already on the GPU with its
@@ -210,19 +438,18 @@ class KittiInference:
     everything behind (normalisation, placement, the maps handed out) is of the rectified images (maps.dst_hw): the result is
     what rectifying on the host and handing the rectified pair in gives.  None (the default) changes nothing.
 
-    What a subclass states: its mask mode, through `_take_mask` (which disparity and which mask `_frame_maps` yields); the
-    record a frame hands out, through `_fields`; and how the frame's maps get into that record, through `_export`.  The
-    buffers, the read-back, the result, `stream` and `__call__` are here, once."""
+    Two layers.  FramePipeline owns what does not depend on a network: the slots, the upload, the head of the compute stage
+    (waits, rectify=), the read-back, the result and `stream`.  This class fills its hooks with the network: the model, eager or
+    graphed, the (Hc,Wc) frame and the image's placement in it (`_place`, `_room`), and `_fill`: histogram -> table -> frames ->
+    model -> `_export`.  What a subclass states: its mask mode, through `_take_mask` (which disparity and which mask
+    `_frame_maps` yields); the record a frame hands out, through `_fields`; and how the frame's maps get into that record,
+    through `_export`.  A stage behind the network that reads (disparity, mask, window) starts from `_StageMixin`."""
 
     confidence = False           # True: a confidence map next to every disparity map (mask mode "confidence")
     radius = 1                   # its window, in 1/4-res disparity bins either side of the peak
     mask_mode = None             # None | "confidence" | "lr": what `_frame_maps` yields next to the disparity
     CONF_U16_SCALE = 65535.0      # uint16 scale of the second map (a confidence in [0,1]; a 0 / 1 validity mask)
-    out_scale = 1                # the maps handed out are at most this many times the frame in each direction (HighResInference)
-    device_io = False            # what `device_io=None` means for the class
-    needs_device_io = None       # the reason why the class refuses device_io=False, if it does
-    has_uint16 = True            # False: the record has no uint16 form, `as_uint16=True` is refused
-    Frame = None                 # a namedtuple type to hand the fields out in, by name; None: a tuple (one field: itself)
+    device_io = False            # (the host path is the reference's own)
     _mirrored = None             # (2,1,3,Hc,Wc): the mirrored, swapped frames of `_lr_maps`, rewritten whole by every frame
 
     @property
@@ -234,24 +461,43 @@ class KittiInference:
                  device_io: bool = None, *, rectify=None):
         """dtype: None (fp32) or torch.float16 / torch.bfloat16 -- the reduced-precision path of BASELINE config 5
         ("fp16, hipGraph-captured 3D hourglass"): the captured hot path runs under ops.reduced_precision(dtype)."""
-        if rectify is not None and not all(hasattr(rectify, k) for k in ("src_hw", "dst_hw", "X", "Y", "valid")):
-            raise TypeError(f"rectify= must be a geometry.RectifyMaps, got {type(rectify)}")
+        super().__init__(device_io=device_io, rectify=rectify)
         self.net = model.module if isinstance(model, torch.nn.DataParallel) else model
         self.crop_height, self.crop_width = crop_height, crop_width
         self.graph = graph
         self.dtype = dtype
         self._graphed = None
-        if device_io is not None:
-            self.device_io = device_io
-        if self.needs_device_io and not self.device_io:
-            raise ValueError(f"{type(self).__name__} needs device_io=True: {self.needs_device_io}")
-        self.rectify = rectify
         if rectify is not None:
-            placement(*self._net_hw(*rectify.dst_hw), crop_height, crop_width)      # the rectified image must fit or cover the frame
+            self._place(*rectify.dst_hw)             # the rectified image must fit or cover the frame
         self._frames = None          # (2,3,Hc,Wc): the network's inputs, rewritten whole by every frame
-        self._slots = []
-        self._copy_stream = None
         self.net.eval()
+
+    @property
+    def _device(self):
+        """the network's"""
+        return next(self.net.parameters()).device
+
+    def _room(self):
+        return self.crop_height, self.crop_width
+
+    def _place(self, h, w):
+        return placement(*self._net_hw(h, w), self.crop_height, self.crop_width)
+
+    def _calib_or_maps(self, calib):
+        """calib=, or else the calibration the rectify= maps carry"""
+        if calib is None:
+            calib = getattr(self.rectify, "calib", None)
+            if calib is None:
+                raise ValueError(f"{type(self).__name__} needs calib=, or rectify= maps that carry the rectified pair's calibration")
+        return calib
+
+    def _max_disp_or_model(self, max_disp):
+        """max_disp=, or else the model's `maxdisp`"""
+        if max_disp is None:
+            max_disp = getattr(self.net, "maxdisp", None)
+            if max_disp is None:
+                raise ValueError(f"{type(self).__name__} needs max_disp=: the model has no `maxdisp`")
+        return max_disp
 
     def _take_mask(self, mask, mask_min=0.5, radius=1, tau=1.0):
         """The mask mode of the instance, checked and stored: which disparity and which mask a frame yields (`_frame_maps`).
@@ -338,156 +584,25 @@ class KittiInference:
         dtype = torch.uint16 if as_uint16 else torch.float32
         return [(name, dtype, (rows, cols)) for name in ("disp", "mask")[:self.nmaps]]
 
-    # ---- device I/O: three stages per frame, each enqueued on the stream it is given --------------------------------
-    @property
-    def _device(self):
-        """the device the frames live on: the network's (SGMInference: its own)"""
-        return next(self.net.parameters()).device
-
-    def _slot(self, i):
-        dev = self._device
-        if self._frames is None:
-            self._frames = torch.empty((2, 3, self.crop_height, self.crop_width), device=dev, dtype=torch.float32)
-        while len(self._slots) <= i:
-            worst = self._fields(self.crop_height * self.out_scale, self.crop_width * self.out_scale, False)
-            self._slots.append(_Slot(dev, _nbytes(worst)))
-        return self._slots[i]
-
-    def _upload(self, s, left_rgb, right_rgb, copy):
-        """host: the pair into the slot's pinned buffer; `copy` stream: pinned -> device"""
-        left_rgb, right_rgb = np.ascontiguousarray(left_rgb), np.ascontiguousarray(right_rgb)
-        if left_rgb.dtype != np.uint8 or right_rgb.dtype != np.uint8 or left_rgb.ndim != 3 \
-                or left_rgb.shape[2] not in (3, 4) or left_rgb.shape != right_rgb.shape:
-            raise ValueError(f"device_io takes two (H,W,3) or (H,W,4) uint8 images of one shape, got {left_rgb.dtype} "
-                             f"{left_rgb.shape} and {right_rgb.dtype} {right_rgb.shape}")
-        h, w, c = left_rgb.shape
-        if self.rectify is not None and (h, w) != tuple(self.rectify.src_hw):
-            raise ValueError(f"rectify= was built for {self.rectify.src_hw[0]} x {self.rectify.src_hw[1]} raw images, got "
-                             f"{h} x {w}")
-        place = placement(*self._net_hw(*((h, w) if self.rectify is None else self.rectify.dst_hw)), self.crop_height,
-                          self.crop_width)
-        n = h * w * c
-        off = s.reserve_input(n)
-        s.uploaded.synchronize()                     # the previous copy out of the pinned buffer
-        pin = s.in_pin.numpy()
-        pin[:n] = left_rgb.reshape(-1)
-        pin[off:off + n] = right_rgb.reshape(-1)
-        with torch.cuda.stream(copy):
-            copy.wait_event(s.computed)              # the previous frame of this slot has read its input
-            s.in_dev[:off + n].copy_(s.in_pin[:off + n], non_blocking=True)      # one copy for the pair
-            s.uploaded.record(copy)
-        s.meta = (h, w, c, place, off)
-
-    @torch.no_grad()
-    def _compute(self, s, compute, as_uint16):
-        """`compute` stream: histogram -> table -> frames -> model -> export into the slot's device output"""
+    def _fill(self, s, left, right, h, w, as_uint16):
+        """current stream: histogram -> table -> frames -> model -> export into the slot's device output"""
         from . import ops
-        h, w, c, (src_y0, dst_y0, rows, cols), off = s.meta
-        n = h * w * c
-        with torch.cuda.stream(compute):
-            compute.wait_event(s.uploaded)
-            compute.wait_event(s.done)               # the previous read-back of this slot's output
-            left, right = s.in_dev[:n].view(h, w, c), s.in_dev[off:off + n].view(h, w, c)
-            if self.rectify is not None:
-                h, w = self.rectify.dst_hw
-                left, right = ops.rectify_pair(left, right, self.rectify, out=s.rectified(h, w, c))
-            s.left, s.out_hw = left, (rows, cols)
-            left, right, h, w = self._net_pair(s, left, right, h, w)
-            lut, _ = ops.frame_lut(ops.frame_histogram(left, right), h * w)
-            fl, fr = ops.frame_apply(left, right, lut, (self.crop_height, self.crop_width), src_y0, dst_y0, rows, cols,
-                                     out=self._frames)
-            s.set_fields(self._fields(*s.out_hw, as_uint16))
-            self._export(s, self._frame_maps(fl, fr, cols), s.dev)
-            s.computed.record(compute)
+        if self._frames is None:
+            self._frames = torch.empty((2, 3, self.crop_height, self.crop_width), device=s.device, dtype=torch.float32)
+        left, right, h, w = self._net_pair(s, left, right, h, w)
+        lut, _ = ops.frame_lut(ops.frame_histogram(left, right), h * w)
+        fl, fr = ops.frame_apply(left, right, lut, self._room(), *s.frame.placement, out=self._frames)
+        s.set_fields(self._fields(*s.out_hw, as_uint16))
+        self._export(s, self._frame_maps(fl, fr, s.frame.cols), s.dev)
 
     def _export(self, s, maps, out):
         """current stream: the frame's maps, cropped to the image's window, into `out`, the fields in the slot's device output"""
         from . import ops
-        dst_y0, rows, cols = s.meta[3][1:]
         for m, o, scale in zip(maps, out.values(), (256.0, self.CONF_U16_SCALE)):
             if o.dtype == torch.uint16:
-                ops.disp_export(m.contiguous(), dst_y0, rows, cols, scale=scale, f32=False, u16=True, out_u16=o)
+                ops.disp_export(m.contiguous(), *s.frame.window, scale=scale, f32=False, u16=True, out_u16=o)
             else:
-                ops.disp_export(m.contiguous(), dst_y0, rows, cols, out_f32=o)
-
-    def _readback(self, s, copy):
-        """`copy` stream: the frame's record, device output -> pinned, in one copy of exactly its bytes"""
-        n = s.out_bytes
-        with torch.cuda.stream(copy):
-            copy.wait_event(s.computed)
-            s.out_pin[:n].copy_(s.out_dev[:n], non_blocking=True)
-            s.done.record(copy)
-        s.copy = copy
-
-    def _rest(self, s, head):
-        """host, after the frame's wait: sends for what the frame hands out beyond its record `head` (the fields in the pinned
-        buffer) and returns a function that waits for it and gives it as {name: array}.  Here: nothing, an empty dict.
-        KittiInference3D: the vertices."""
-        return dict
-
-    def _result(self, s):
-        """host: the one synchronisation of a frame, then a copy of every field out of the pinned buffer"""
-        s.done.synchronize()
-        rest = self._rest(s, s.pin)                  # (in flight while the host copies the fields)
-        out = {name: v.numpy().copy() for name, v in s.pin.items()}
-        out.update(rest())
-        if self.Frame is not None:
-            return self.Frame(*(out.get(name) for name in self.Frame._fields))
-        return tuple(out.values()) if len(out) > 1 else out["disp"]
-
-    def _call_device(self, left_rgb, right_rgb, as_uint16, *more):
-        dev = self._device
-        cur = torch.cuda.current_stream(dev)
-        s = self._slot(0)
-        self._upload(s, left_rgb, right_rgb, cur, *more)
-        self._compute(s, cur, as_uint16)
-        self._readback(s, cur)
-        return self._result(s)
-
-    def _check_format(self, as_uint16):
-        if as_uint16 and not self.has_uint16:
-            raise TypeError(f"{type(self).__name__} hands out no uint16 form of its frames: as_uint16=True is not for it")
-
-    def stream(self, pairs, depth: int = 2, as_uint16: bool = False):
-        """Generator over an iterable of (left_rgb, right_rgb) uint8 pairs (sizes may differ as long as each fits the
-        frame): yields what `__call__` gives for each pair, byte for byte, in input order, `depth` frames in flight.  A copy
-        stream beside the compute stream carries the upload of frame i+1 and the read-back of frame i-1 while frame i
-        computes."""
-        if not self.device_io:
-            raise RuntimeError("stream() needs KittiInference(..., device_io=True)")
-        if depth < 1:
-            raise ValueError("depth >= 1")
-        self._check_format(as_uint16)
-        dev = self._device
-        compute = torch.cuda.current_stream(dev)
-        if self._copy_stream is None:
-            self._copy_stream = torch.cuda.Stream(dev)
-        copy = self._copy_stream
-        copy.wait_stream(compute)
-        inflight = collections.deque()               # slots in input order; [slot, read-back enqueued]
-        try:
-            for i, (left_rgb, right_rgb, *more) in enumerate(pairs):      # (more: what a subclass's `_upload` takes per frame)
-                if len(inflight) == depth:               # slot i % depth is the oldest frame's: hand that frame out first
-                    old = inflight.popleft()
-                    if not old[1]:
-                        self._readback(old[0], copy)
-                    yield self._result(old[0])
-                s = self._slot(i % depth)
-                self._upload(s, left_rgb, right_rgb, copy, *more)
-                self._compute(s, compute, as_uint16)
-                # the read-back of the frame before goes behind this upload on the copy stream: it waits for that frame's
-                # compute, and an upload queued behind it would wait too
-                if inflight and not inflight[-1][1]:
-                    self._readback(inflight[-1][0], copy)
-                    inflight[-1][1] = True
-                inflight.append([s, False])
-            while inflight:
-                old = inflight.popleft()
-                if not old[1]:
-                    self._readback(old[0], copy)
-                yield self._result(old[0])
-        finally:
-            compute.wait_stream(copy)                # later work on the compute stream may reuse slot 0 (`__call__`)
+                ops.disp_export(m.contiguous(), *s.frame.window, out_f32=o)
 
     def __call__(self, left_rgb: np.ndarray, right_rgb: np.ndarray, as_uint16: bool = False):
         self._check_format(as_uint16)
@@ -677,18 +792,18 @@ class KittiInferenceGuided(_HintsMixin, KittiInference):
         self._check_item(hints)
         super()._upload(s, left_rgb, right_rgb, copy)
         if self.sgm is not None:
-            s.hints = ("sgm", None)
+            s.item = ("sgm", None)
             return
-        hw = tuple(s.meta[:2]) if self.rectify is None else tuple(self.rectify.dst_hw)
+        hw = (s.frame.h, s.frame.w) if self.rectify is None else tuple(self.rectify.dst_hw)
         if self.lidar is not None:
             if tuple(self.lidar.hw) != hw:
                 raise ValueError(f"lidar= projects into {self.lidar.hw[0]} x {self.lidar.hw[1]} images, got {hw[0]} x {hw[1]}")
-            s.hints = ("scan", hints)
+            s.item = ("scan", hints)
             return
         if isinstance(hints, torch.Tensor):
             if not hints.is_cuda or hints.dtype != torch.float32 or tuple(hints.shape) != hw or not hints.is_contiguous():
                 raise ValueError(f"hints must be a contiguous float32 {hw} map, got {hints.dtype} {tuple(hints.shape)}")
-            s.hints = ("map", hints)
+            s.item = ("map", hints)
             return
         hints = np.ascontiguousarray(hints)
         if hints.dtype != np.float32 or hints.shape != hw:
@@ -699,27 +814,27 @@ class KittiInferenceGuided(_HintsMixin, KittiInference):
         with torch.cuda.stream(copy):
             dev.copy_(pin, non_blocking=True)
             s.uploaded.record(copy)  # again: the pair and the hints
-        s.hints = ("map", dev)
+        s.item = ("map", dev)
 
     def _net_pair(self, s, left, right, h, w):
         """current stream: also the frame's `hints4`, from the slot's map (or scan) through the slot's placement"""
         from . import ops
-        kind, item = s.hints
+        kind, item = s.item
         if kind == "scan":
             if self._proj is None:
                 self._proj = LidarProjector(self.lidar, s.device, capacity=max(1 << 18, int(np.asarray(item).shape[0])))
             item = self._proj(item)["disp"]
         elif kind == "sgm":
             item = _sgm_maps(s, left, right, self.sgm, self.sgm_lr_tau)[0]
-        ops.hints_to_quarter(item, (self.crop_height, self.crop_width), s.meta[3], maxdisp=self.net.maxdisp,
+        ops.hints_to_quarter(item, self._room(), s.frame.placement, maxdisp=self.net.maxdisp,
                              out=self._hints4_buffer(s.device)[0])
         return left, right, h, w
 
 
-class SGMInference(KittiInference):
+class SGMInference(FramePipeline):
     """`disp, valid = SGMInference(max_disp=192, paths=8, P1=10, P2=120, uniqueness=15, lr_tau=1.0, median=0, speckle=None)(
     left_rgb, right_rgb)`: a disparity map without a network.  It takes NO model.  The uint8 pair is
-    uploaded through the slots of KittiInference (rectified first with rectify=), `ops.sgm_disparity` runs on it as it lies in
+    uploaded through the slots of FramePipeline (rectified first with rectify=), `ops.sgm_disparity` runs on it as it lies in
     device memory, and with `lr_tau` (None: off) `ops.lr_consistency` cross-checks the left view against `disp_right_mirrored`,
     which is read from the same aggregation: the two validities are multiplied and the disparity is +0.0 where the product is 0.
     Then the post-filter of section 6l on the same stream: `ops.median_filter` (`median` = 3 or 5; 0: off) and
@@ -729,80 +844,42 @@ class SGMInference(KittiInference):
     size, images of different sizes may follow each other (the buffers grow to the largest seen), each within the limits of
     `ops.sgm_disparity`.  No uint16 form.  device: where the frames live."""
 
-    nmaps = 2
-    device_io = True
     needs_device_io = "semi-global matching runs on the device only"
     has_uint16 = False
     mask_min = 0.5               # the post-filter's threshold on the validity
 
     def __init__(self, max_disp: int = 192, paths: int = 8, P1: int = 10, P2: int = 120, uniqueness: int = 15, lr_tau=1.0,
                  median: int = 0, speckle=None, rectify=None, *, min_disp: int = 1, device="cuda"):
-        if rectify is not None and not all(hasattr(rectify, k) for k in ("src_hw", "dst_hw", "X", "Y", "valid")):
-            raise TypeError(f"rectify= must be a geometry.RectifyMaps, got {type(rectify)}")
+        super().__init__(device=device, rectify=rectify)
         self.sgm, self.lr_tau = _check_sgm("SGMInference", dict(max_disp=max_disp, paths=paths, P1=P1, P2=P2, uniqueness=uniqueness,
                                                                 min_disp=min_disp, lr_tau=lr_tau))
         self.median, self.speckle = _check_post(median, speckle)
-        self.net, self.graph, self.dtype, self._graphed = None, False, None, None
-        self.rectify = rectify
-        self._dev = torch.device(device)
-        self.crop_height, self.crop_width = (7, 7) if rectify is None else tuple(rectify.dst_hw)      # the largest image so far
-        self._frames, self._slots, self._copy_stream = None, [], None
+        self._largest = (7, 7) if rectify is None else tuple(rectify.dst_hw)       # the largest image so far: the room of a frame
 
-    @property
-    def _device(self):
-        return self._dev
+    def _room(self):
+        return self._largest
 
     def _fields(self, rows, cols, as_uint16):
-        return [("disp", torch.float32, (rows, cols)), ("valid", torch.float32, (rows, cols))]
-
-    def _slot(self, i):
-        while len(self._slots) <= i:
-            self._slots.append(_Slot(self._device, _nbytes(self._fields(self.crop_height, self.crop_width, False))))
-            self._slots[-1].room = (self.crop_height, self.crop_width)
-        return self._slots[i]
-
-    def _grow(self, s, h, w):
-        """room for h x w maps in THIS slot, whose previous frame has been handed out (rare: the largest image so far grew)"""
-        self.crop_height, self.crop_width = max(h, self.crop_height), max(w, self.crop_width)
-        if s.room == (self.crop_height, self.crop_width):
-            return
-        s.done.synchronize()                     # the read-back out of the old buffers
-        n = _nbytes(self._fields(self.crop_height, self.crop_width, False))
-        s.out_dev = torch.empty(n, device=s.device, dtype=torch.uint8)
-        s.out_pin = torch.empty(n, dtype=torch.uint8).pin_memory()
-        s._scratch.pop("post", None)             # the post-filter's buffers are sized for the largest image too
-        s.room = (self.crop_height, self.crop_width)
+        return _disp_valid(rows, cols)
 
     def _upload(self, s, left_rgb, right_rgb, copy):
         if self.rectify is None and np.ndim(left_rgb) == 3:
-            self._grow(s, *np.shape(left_rgb)[:2])
+            # room for the image's maps in THIS slot, whose previous frame has been handed out (rare: the largest image so far grew)
+            h, w = np.shape(left_rgb)[:2]
+            self._largest = (max(h, self._largest[0]), max(w, self._largest[1]))
+            s.reserve_output(_nbytes(self._fields(*self._largest, False)), drop=("post",))     # (the post-filter's buffers too)
         super()._upload(s, left_rgb, right_rgb, copy)
-        h, w = s.meta[:2] if self.rectify is None else self.rectify.dst_hw
-        s.meta = s.meta[:3] + ((0, 0, h, w),) + s.meta[4:]         # no frame: the window is the image
 
-    @torch.no_grad()
-    def _compute(self, s, compute, as_uint16):
-        """`compute` stream: [rectify ->] semi-global matching [-> left-right check] [-> post-filter] into the slot's device output"""
-        from . import ops
-        h, w, c, _, off = s.meta
-        n = h * w * c
-        with torch.cuda.stream(compute):
-            compute.wait_event(s.uploaded)
-            compute.wait_event(s.done)               # the previous read-back of this slot's output
-            left, right = s.in_dev[:n].view(h, w, c), s.in_dev[off:off + n].view(h, w, c)
-            if self.rectify is not None:
-                h, w = self.rectify.dst_hw
-                left, right = ops.rectify_pair(left, right, self.rectify, out=s.rectified(h, w, c))
-            s.left, s.out_hw = left, (h, w)
-            s.set_fields(self._fields(h, w, False))
-            disp, valid = _sgm_maps(s, left, right, self.sgm, self.lr_tau)
-            if self.median or self.speckle is not None:
-                # as KittiInferenceFiltered: without a speckle filter, max_size 0 keeps every active pixel
-                _post_filter(self, s, disp, valid, (0, h, w), s.dev["disp"], self.speckle or (0, 0.0), False, s.dev["valid"])
-            else:
-                s.dev["disp"].copy_(disp)
-                s.dev["valid"].copy_(valid)
-            s.computed.record(compute)
+    def _fill(self, s, left, right, h, w, as_uint16):
+        """current stream: semi-global matching [-> left-right check] [-> post-filter] into the slot's device output"""
+        s.set_fields(self._fields(h, w, False))
+        disp, valid = _sgm_maps(s, left, right, self.sgm, self.lr_tau)
+        if self.median or self.speckle is not None:
+            # as KittiInferenceFiltered: without a speckle filter, max_size 0 keeps every active pixel
+            _post_filter(self, s, disp, valid, (0, h, w), s.dev["disp"], self.speckle or (0, 0.0), False, s.dev["valid"])
+        else:
+            s.dev["disp"].copy_(disp)
+            s.dev["valid"].copy_(valid)
 
 
 def _check_post(median, speckle):
@@ -842,7 +919,7 @@ def _post_filter(infer, s, pred, mask, window, out_disp, speckle, fold, out_vali
     removed pixel is no measurement), which is sound only where the stage behind applies a mask_min > 0.  Nothing is allocated
     after the slot's first frame, but the product of a fold."""
     from . import ops
-    post = s.scratch("post", lambda: _Post(s.device, infer.crop_height, infer.crop_width))
+    post = s.scratch("post", lambda: _Post(s.device, *infer._room()))
     y0, rows, cols = window
     med, cropped, disp, valid = (post.maps[k, :rows * cols].view(rows, cols) for k in range(4))
     pred = pred.view(pred.shape[-2:])
@@ -864,7 +941,58 @@ def _post_filter(infer, s, pred, mask, window, out_disp, speckle, fold, out_vali
     return r["disp"], cropped, (0, rows, cols)
 
 
-class KittiInferenceFiltered(KittiInference):
+class _StageMixin:
+    """What the stages behind the network share (KittiInferenceFiltered, KittiInference3D, KittiInferenceGround and so
+    KittiInferenceStixels, KittiInferenceColor): the `median=` / `speckle=` keywords, and ONE preamble, `_stage_maps`, that turns
+    the frame's maps into the (pred, mask, window) a stage reads."""
+
+    _validity = False            # True: with rectify=, the maps' validity (`rectify.valid[0]`) is the mask, or multiplies it
+    _valid_frame = None          # that validity placed in the frame, float32 (Hc,Wc), built once
+
+    def _take_post(self, median, speckle):
+        self.median, self.speckle = _check_post(median, speckle)
+
+    def _validity_in_mask(self, mask_min, speckle=False):
+        """the class lets `rectify=`'s validity into the mask (and states with `speckle=True` that it always folds the speckle
+        filter's): both are 0 / 1, so a mask_min <= 0 would switch nothing off"""
+        self._validity = True
+        if self.rectify is not None and not float(mask_min) > 0.0:
+            raise ValueError("with rectify= the maps' validity (0 / 1) enters the mask: mask_min must be > 0")
+        if speckle and self.speckle is not None and not float(mask_min) > 0.0:
+            raise ValueError("with speckle= the filter's validity (0 / 1) enters the mask: mask_min must be > 0")
+
+    def _stage_maps(self, s, maps, out, fold, export=True, speckle=None, out_valid=None):
+        """current stream: the frame's maps -> (pred, mask, window), 2-D views.  With `median=` / `speckle=` the post-filter runs
+        (`fold`, `out_valid`: `_post_filter`'s; `speckle`: the filter to run in place of the instance's own) and writes the
+        disparity it gives into out["disp"]; without, `export` puts the window of the disparity there.  Then `rectify=`'s validity
+        enters the mask, where the class has said so: a pixel without a full source footprint is no measurement."""
+        from . import ops
+        f = s.frame
+        pred, mask = _maps2d(maps)
+        window = f.window
+        speckle = self.speckle if speckle is None else speckle
+        filtered = bool(self.median) or speckle is not None
+        if filtered:
+            pred, mask, window = _post_filter(self, s, pred, mask, window, out["disp"], speckle, fold, out_valid)
+        elif export:
+            ops.disp_export(pred, *window, out_f32=out["disp"])
+        if self._validity and self.rectify is not None:
+            valid = self._valid(pred.device, f)
+            if filtered:                             # (pred and mask are the window's own from here on)
+                valid = valid[f.dst_y0:f.dst_y0 + f.rows, :f.cols].contiguous()
+            mask = valid if mask is None else mask * valid
+        return pred, mask, window
+
+    def _valid(self, device, f):
+        """rectify.valid[0] as a float32 mask placed in the frame like the image; built once (the frame size is fixed)"""
+        if self._valid_frame is None or self._valid_frame.device != device:
+            frame = np.zeros(self._room(), np.float32)
+            frame[f.dst_y0:f.dst_y0 + f.rows, :f.cols] = self.rectify.valid[0][f.src_y0:f.src_y0 + f.rows, :f.cols]
+            self._valid_frame = torch.from_numpy(frame).to(device)
+        return self._valid_frame
+
+
+class KittiInferenceFiltered(_StageMixin, KittiInference):
     """`disp, valid = KittiInferenceFiltered(model, ..., median=0, speckle=(200, 2.0), mask=None | "confidence" | "lr")(left_rgb,
     right_rgb)`: KittiInference with device I/O (required: the filters run where the disparity lies) followed by the
     post-filter on the same stream: `ops.median_filter` (`median` = 3 or 5; 0: off), then
@@ -887,17 +1015,15 @@ class KittiInferenceFiltered(KittiInference):
                  tau: float = 1.0, **kwargs):
         super().__init__(model, *args, **kwargs)
         self._take_mask(mask, mask_min, radius, tau)
-        self.median, self.speckle = _check_post(median, speckle)
+        self._take_post(median, speckle)
 
     def _fields(self, rows, cols, as_uint16):
-        return [("disp", torch.float32, (rows, cols)), ("valid", torch.float32, (rows, cols))]
+        return _disp_valid(rows, cols)
 
     def _export(self, s, maps, out):
-        pred = maps[0].contiguous()
-        mask = maps[1].contiguous() if len(maps) > 1 else None
         # without a speckle filter, max_size 0 keeps every active pixel: valid = active, and only the others go.  `valid` is
         # handed out itself: nothing behind reads the mask, so nothing is folded into it
-        _post_filter(self, s, pred, mask, s.meta[3][1:], out["disp"], self.speckle or (0, 0.0), False, out["valid"])
+        self._stage_maps(s, maps, out, False, speckle=self.speckle or (0, 0.0), out_valid=out["valid"])
 
 
 class HighResInference(KittiInference):
@@ -963,16 +1089,17 @@ class HighResInference(KittiInference):
         return buf[:2 * hs * ws * c].view(2, hs, ws, c)
 
     def _fields(self, h, w, as_uint16):
-        return [("disp", torch.float32, (h, w)), ("valid", torch.float32, (h, w))]
+        return _disp_valid(h, w)
 
     def _export(self, s, maps, out):
         from . import highres, ops
         if self._tables_dev is None or self._tables_dev[0].device != s.device:
             self._tables_dev = highres.device_tables(self.tables, s.device)
+        f = s.frame
         pred = maps[0].contiguous()
         mask = maps[1].contiguous().view_as(pred) if len(maps) > 1 else None
-        guide_lo = self._small(s, *s.meta[3][2:], s.left.shape[2])[0]        # (the small image fits the frame: the window is its size)
-        ops.guided_upsample(pred, guide_lo, s.left, self.scale, self._tables_dev, s.meta[3][1:], mask, self.mask_min, out=out)
+        guide_lo = self._small(s, f.rows, f.cols, s.left.shape[2])[0]        # (the small image fits the frame: the window is its size)
+        ops.guided_upsample(pred, guide_lo, s.left, self.scale, self._tables_dev, f.window, mask, self.mask_min, out=out)
 
 
 Frame3D = collections.namedtuple("Frame3D", "disp mask depth vertices")
@@ -990,7 +1117,7 @@ class _Geo:
         self.offsets = ops.point_cloud_workspace(crop_height, crop_width, device)[0]
 
 
-class KittiInference3D(KittiInference):
+class KittiInference3D(_StageMixin, KittiInference):
     """`disp, mask, depth, vertices = KittiInference3D(model, calib, mask=None | "confidence" | "lr", ...)(left_rgb,
     right_rgb)`: KittiInference with device I/O (required: the colours are the uint8 left image that already lies in device
     memory) followed by the geometry stage on the same stream: `ops.disp_to_depth` and
@@ -1023,16 +1150,9 @@ class KittiInference3D(KittiInference):
                  **kwargs):
         from . import frame_ops
         super().__init__(model, *args, **kwargs)
-        self.median, self.speckle = _check_post(median, speckle)
-        if calib is None:
-            calib = getattr(self.rectify, "calib", None)
-            if calib is None:
-                raise ValueError("KittiInference3D needs calib=, or rectify= maps that carry the rectified pair's calibration")
-        if self.rectify is not None and not float(mask_min) > 0.0:
-            raise ValueError("with rectify= the maps' validity (0 / 1) enters the mask: mask_min must be > 0")
-        if self.speckle is not None and not float(mask_min) > 0.0:
-            raise ValueError("with speckle= the filter's validity (0 / 1) enters the mask: mask_min must be > 0")
-        self._valid_frame = None     # rectify=: valid[0] placed in the frame, float32 (Hc,Wc), built once
+        self._take_post(median, speckle)
+        calib = self._calib_or_maps(calib)
+        self._validity_in_mask(mask_min, speckle=True)
         if int(stride) < 1:
             raise ValueError("stride >= 1")
         frame_ops._geo_scalars("KittiInference3D", calib, mask_min, min_disp, max_depth)       # the operators' ranges, up front
@@ -1050,36 +1170,18 @@ class KittiInference3D(KittiInference):
 
     def _export(self, s, maps, out):
         from . import ops
-        h, w, c, (src_y0, dst_y0, rows, cols), _ = s.meta
         g = self._geo(s)
-        pred = maps[0].contiguous()
-        mask = maps[1].contiguous() if len(maps) > 1 else None
-        ops.disp_export(pred, dst_y0, rows, cols, out_f32=out["disp"])
+        pred, mask = _maps2d(maps)
+        ops.disp_export(pred, *s.frame.window, out_f32=out["disp"])
         if mask is not None:
-            ops.disp_export(mask, dst_y0, rows, cols, out_f32=out["mask"])
-        window = (dst_y0, rows, cols)
-        valid = None
-        if self.rectify is not None:     # a pixel without a full source footprint is no measurement (the maps handed out stay as they are)
-            valid = self._valid(pred.device, src_y0, dst_y0, rows, cols)
-        if self.median or self.speckle is not None:
-            # the disparity handed out is the filtered one; a removed pixel is no measurement either: depth 0, no vertex
-            # (mask_min > 0 is enforced with speckle=, so the fold always holds)
-            pred, mask, window = _post_filter(self, s, pred, mask, window, out["disp"], self.speckle, True)
-            if valid is not None:
-                valid = valid[dst_y0:dst_y0 + rows, :cols].contiguous()
-        if valid is not None:
-            mask = valid.view_as(pred) if mask is None else mask * valid.view_as(pred)
+            ops.disp_export(mask, *s.frame.window, out_f32=out["mask"])
+        # the disparity handed out is the filtered one (the post-filter overwrites the export above); a removed pixel is no
+        # measurement: depth 0, no vertex (mask_min > 0 is enforced with speckle=, so the fold always holds).  The mask handed out
+        # stays as it is
+        pred, mask, window = self._stage_maps(s, (pred, mask), out, True, export=False)
         ops.disp_to_depth(pred, self.calib, window, mask, out_f32=out["depth"], **self.filters)
-        ops.point_cloud(pred, self.calib, s.left, mask, window, v0=src_y0, stride=self.stride,
+        ops.point_cloud(pred, self.calib, s.left, mask, window, v0=s.frame.src_y0, stride=self.stride,
                         out=g.vert_dev, workspace=(g.offsets, out["count"]), **self.filters)
-
-    def _valid(self, device, src_y0, dst_y0, rows, cols):
-        """rectify.valid[0] as a float32 mask placed in the frame like the image; built once (the frame size is fixed)"""
-        if self._valid_frame is None or self._valid_frame.device != device:
-            frame = np.zeros((self.crop_height, self.crop_width), np.float32)
-            frame[dst_y0:dst_y0 + rows, :cols] = self.rectify.valid[0][src_y0:src_y0 + rows, :cols]
-            self._valid_frame = torch.from_numpy(frame).to(device)
-        return self._valid_frame
 
     def _rest(self, s, head):
         """the vertex step: the count is on the host, so exactly the written records follow the maps on their copy stream;
@@ -1111,7 +1213,7 @@ class _Ground:
         self.workspace = ops.ground_workspace(crop_height, crop_width, max_disp, device)
 
 
-class KittiInferenceGround(KittiInference):
+class KittiInferenceGround(_StageMixin, KittiInference):
     """`disp, label, free_row, free_disp, bev, plane = KittiInferenceGround(model, calib, mask=None | "confidence" | "lr", ...)(
     left_rgb, right_rgb)`: KittiInference with device I/O (required: the stage runs where the disparity lies) followed by the
     ground stage on the same stream: `ops.ground_plane` -- v-disparity, Hough line, least squares with
@@ -1139,26 +1241,17 @@ class KittiInferenceGround(KittiInference):
     Frame = FrameGround
     PLANE_KEYS = ("fit_rows", "refine", "tol", "min_rise", "min_votes", "min_inliers")
     SEGMENT_KEYS = ("tol_d", "h_ground", "h_max", "min_run")
-    _valid = KittiInference3D._valid
-    _valid_frame = None
 
     def __init__(self, model, calib=None, *args, mask=None, mask_min: float = 0.5, radius: int = 1, tau: float = 1.0, speckle=None,
                  median: int = 0, max_disp=None, min_disp=None, grid=None, plane=None, segment=None, **kwargs):
         from . import ground as G
         super().__init__(model, *args, **kwargs)
         name = type(self).__name__
-        self.median, self.speckle = _check_post(median, speckle)
-        if calib is None:
-            calib = getattr(self.rectify, "calib", None)
-            if calib is None:
-                raise ValueError(f"{name} needs calib=, or rectify= maps that carry the rectified pair's calibration")
-        if self.rectify is not None and not float(mask_min) > 0.0:
-            raise ValueError("with rectify= the maps' validity (0 / 1) enters the mask: mask_min must be > 0")
+        self._take_post(median, speckle)
+        calib = self._calib_or_maps(calib)
+        self._validity_in_mask(mask_min)
         self._take_mask(mask, mask_min, radius, tau)
-        if max_disp is None:
-            max_disp = getattr(self.net, "maxdisp", None)
-            if max_disp is None:
-                raise ValueError(f"{name} needs max_disp=: the model has no `maxdisp`")
+        max_disp = self._max_disp_or_model(max_disp)
         plane, segment = dict(plane or {}), dict(segment or {})
         if set(plane) - set(self.PLANE_KEYS) or set(segment) - set(self.SEGMENT_KEYS):
             raise ValueError(f"{name}: plane= takes {self.PLANE_KEYS} and segment= takes {self.SEGMENT_KEYS}, got {sorted(plane)} and "
@@ -1193,27 +1286,12 @@ class KittiInferenceGround(KittiInference):
         """current stream: the filters, then `ops.ground_plane` into out["plane"] (and the disparity it read into out["disp"]);
         returns that disparity and the frame keywords (max_disp, mask, mask_min, window, min_disp) of the stage behind"""
         from . import ops
-        h, w, c, (src_y0, dst_y0, rows, cols), _ = s.meta
         g = s.scratch("ground", lambda: _Ground(s.device, self.crop_height, self.crop_width, self.max_disp))
-        pred = maps[0].contiguous()
-        pred = pred.view(pred.shape[-2:])
-        mask = maps[1].contiguous().view_as(pred) if len(maps) > 1 else None
-        window = (dst_y0, rows, cols)
-        valid = None
-        if self.rectify is not None:     # a pixel without a full source footprint is no measurement
-            valid = self._valid(pred.device, src_y0, dst_y0, rows, cols)
-        if self.median or self.speckle is not None:
-            # the filters run before the fit; a removed pixel is +0.0, below every min_disp > 0, and leaves the mask where it has one
-            pred, mask, window = _post_filter(self, s, pred, mask, window, out["disp"], self.speckle, self.mask_min > 0.0)
-            if valid is not None:
-                valid = valid[dst_y0:dst_y0 + rows, :cols].contiguous()
-        else:
-            ops.disp_export(pred, dst_y0, rows, cols, out_f32=out["disp"])
-        if valid is not None:
-            mask = valid if mask is None else mask * valid
+        # the filters run before the fit; a removed pixel is +0.0, below every min_disp > 0, and leaves the mask where it has one
+        pred, mask, window = self._stage_maps(s, maps, out, self.mask_min > 0.0)
         frame = dict(max_disp=self.max_disp, mask=mask, mask_min=self.mask_min, window=window, min_disp=self.min_disp)
-        ops.ground_plane(pred, calib=self.calib, v0=src_y0, workspace=g.workspace,
-                         out={"plane": out["plane"], "vdisp": g.vdisp[:rows]}, **frame, **self.plane_kw)
+        ops.ground_plane(pred, calib=self.calib, v0=s.frame.src_y0, workspace=g.workspace,
+                         out={"plane": out["plane"], "vdisp": g.vdisp[:s.frame.rows]}, **frame, **self.plane_kw)
         return pred, frame
 
 
@@ -1322,19 +1400,13 @@ class KittiInferenceTemporal(_HintsMixin, KittiInference):
         from . import temporal as T
         super().__init__(model, *args, **kwargs)
         name = type(self).__name__
-        if calib is None:
-            calib = getattr(self.rectify, "calib", None)
-            if calib is None:
-                raise ValueError(f"{name} needs calib=, or rectify= maps that carry the rectified pair's calibration")
+        calib = self._calib_or_maps(calib)
         self._take_mask(mask, mask_min, radius, tau)
         if guide is not None:
             if mask == "lr":
                 raise ValueError(f"{name}: guide= is not combined with mask='lr' (the second, mirrored pass has no hints of its own)")
             self._take_guide(guide)
-        if max_disp is None:
-            max_disp = getattr(self.net, "maxdisp", None)
-            if max_disp is None:
-                raise ValueError(f"{name} needs max_disp=: the model has no `maxdisp`")
+        max_disp = self._max_disp_or_model(max_disp)
         pick = lambda v, default: default if v is None else v      # noqa: E731
         self.reproject_kw = dict(max_disp=float(max_disp), min_disp=float(pick(min_disp, T.TEMPORAL_MIN_DISP)),
                                  occl=tuple(pick(occl, T.TEMPORAL_OCCL)), q=float(pick(q, T.TEMPORAL_Q)),
@@ -1365,18 +1437,17 @@ class KittiInferenceTemporal(_HintsMixin, KittiInference):
         if pose is not None:
             pose = _pose44(pose, type(self).__name__)
         super()._upload(s, left_rgb, right_rgb, copy)
-        src_y0, _, rows, cols = s.meta[3]
-        key = (src_y0, rows, cols)
-        s.G = None
+        src_y0 = s.frame.src_y0
+        key = (src_y0, s.frame.rows, s.frame.cols)
         if pose is not None and self._last is not None and self._last[1] == key:
             # the window's row 0 is image row src_y0: the principal point moves up by as much
             cal = self.calib if src_y0 == 0 else type(self.calib)(self.calib.f, self.calib.baseline, self.calib.cx,
                                                                  self.calib.cy - src_y0, self.calib.doffs)
-            s.G = T.reproject_matrix(cal, relative_pose(self._last[0], pose))
+            s.item = T.reproject_matrix(cal, relative_pose(self._last[0], pose))
         self._last = None if pose is None else (pose, key)
 
     def _set(self, s):
-        rows, cols = s.meta[3][2:]
+        rows, cols = s.frame.rows, s.frame.cols
         if (rows, cols) not in self._sets:
             self._sets[(rows, cols)] = _Temporal(s.device, rows, cols)
         return self._sets[(rows, cols)]
@@ -1385,14 +1456,13 @@ class KittiInferenceTemporal(_HintsMixin, KittiInference):
         """current stream, in front of the network: the prediction from the state of the frame before, and the frame's `hints4`"""
         from . import ops
         t = self._set(s)
-        if s.G is not None:
+        if s.item is not None:
             names = ("pred", "var", "age") + (("hints",) if self.guide is not None else ())
-            ops.disp_reproject(t.state, s.G, self.calib, outputs=names, out={k: t.pred[k] for k in names}, workspace=t.workspace,
+            ops.disp_reproject(t.state, s.item, self.calib, outputs=names, out={k: t.pred[k] for k in names}, workspace=t.workspace,
                                **self.reproject_kw)
         if self.guide is not None:
-            if s.G is not None:
-                dst_y0, rows, cols = s.meta[3][1:]
-                ops.hints_to_quarter(t.pred["hints"], (self.crop_height, self.crop_width), (0, dst_y0, rows, cols),
+            if s.item is not None:
+                ops.hints_to_quarter(t.pred["hints"], (self.crop_height, self.crop_width), (0,) + s.frame.window,
                                      maxdisp=self.net.maxdisp, out=self._hints4_buffer(s.device)[0])
             else:
                 self._hints4_buffer(s.device).zero_()
@@ -1408,13 +1478,13 @@ class KittiInferenceTemporal(_HintsMixin, KittiInference):
         t = self._set(s)
         meas = maps[0].contiguous()
         mask = maps[1].contiguous() if len(maps) > 1 else None
-        ops.temporal_fuse(t.pred if s.G is not None else None, meas, window=s.meta[3][1:], mask=mask, mask_min=self.mask_min,
+        ops.temporal_fuse(t.pred if s.item is not None else None, meas, window=s.frame.window, mask=mask, mask_min=self.mask_min,
                           out=t.state, **self.fuse_kw)
         for k, v in t.state.items():
             out[k].copy_(v, non_blocking=True)
 
 
-class KittiInferenceColor(KittiInference):
+class KittiInferenceColor(_StageMixin, KittiInference):
     """`disp, rgb = KittiInferenceColor(model, cmap="kitti", max_disp=None, mask=None | "confidence" | "lr", ...)(left_rgb,
     right_rgb)`: KittiInference with device I/O (required: the picture is made where the disparity lies) followed by one
     launch of `ops.disp_colorize` on the same stream.  `disp` is float32 (h,w), bitwise
@@ -1436,14 +1506,11 @@ class KittiInferenceColor(KittiInference):
     def __init__(self, model, *args, cmap: str = "kitti", max_disp=None, mask=None, mask_min: float = 0.5, radius: int = 1,
                  tau: float = 1.0, speckle=None, median: int = 0, **kwargs):
         super().__init__(model, *args, **kwargs)
-        self.median, self.speckle = _check_post(median, speckle)
+        self._take_post(median, speckle)
         if cmap not in ("kitti", "gray"):
             raise ValueError(f"cmap is 'kitti' or 'gray', got {cmap!r}")
         self._take_mask(mask, mask_min, radius, tau)
-        if max_disp is None:
-            max_disp = getattr(self.net, "maxdisp", None)
-            if max_disp is None:
-                raise ValueError("KittiInferenceColor needs max_disp=: the model has no `maxdisp`")
+        max_disp = self._max_disp_or_model(max_disp)
         if max_disp != "auto":
             max_disp = float(max_disp)
             if not 0.0 < max_disp < float("inf"):
@@ -1456,16 +1523,9 @@ class KittiInferenceColor(KittiInference):
 
     def _export(self, s, maps, out):
         from . import ops
-        y0, rows, cols = s.meta[3][1:]
-        pred = maps[0].contiguous()
-        mask = maps[1].contiguous().view_as(pred) if len(maps) > 1 else None
-        if self.median or self.speckle is not None:
-            # the disparity handed out is the filtered one (a removed pixel is +0.0: black).  With mask_min <= 0 the mask switches
-            # nothing off, so the filter's validity (0 / 1) must not enter it either
-            pred, mask, (y0, rows, cols) = _post_filter(self, s, pred, mask, (y0, rows, cols), out["disp"], self.speckle,
-                                                        self.mask_min > 0.0)
-        else:
-            ops.disp_export(pred, y0, rows, cols, out_f32=out["disp"])
+        # with the filters the disparity handed out is the filtered one (a removed pixel is +0.0: black).  With mask_min <= 0 the
+        # mask switches nothing off, so the filter's validity (0 / 1) must not enter it either
+        pred, mask, (y0, rows, cols) = self._stage_maps(s, maps, out, self.mask_min > 0.0)
         scale = {"max_disp": self.max_disp}
         if self.max_disp == "auto":
             scale = {"range": ops.disp_range(pred, (y0, rows, cols), mask, self.mask_min)}

@@ -1,5 +1,7 @@
 """What the GPU tests of the inference wrappers share: the seeded model, random uint8 pairs, a left-right threshold that
 splits a pair, rectification maps for the 32 x 64 frame, and the wrapper cases of test_gpu_inference_trace.py."""
+import collections
+
 import numpy as np
 import torch
 
@@ -51,10 +53,29 @@ def rectify_maps(raw=RAW, rect=RECT):
     return RectifyMaps.from_matrices(*REF.smooth_matrices(raw, rect), raw, rect)
 
 
+# model: False for a class that takes none (and so no frame and no graph=); items: None, or (rng, sizes) -> the third item of
+# every frame (a hint map, a pose), one per pair
+Case = collections.namedtuple("Case", "id cls ctor call sizes model items", defaults=(True, None))
+
+
+def hint_maps(rng, sizes, device=False):
+    """sparse float32 hint maps of the images: one pixel in eight carries a disparity in [1, 24), the others +0.0"""
+    maps = [np.where(rng.random((h, w)) < 0.125, rng.uniform(1.0, 24.0, (h, w)), 0.0).astype(np.float32) for h, w in sizes]
+    return [torch.from_numpy(m).to(DEV) for m in maps] if device else maps
+
+
+def poses(rng, sizes):
+    """the camera moves 2 cm forward per frame"""
+    pose = np.tile(np.eye(4), (len(sizes), 1, 1))
+    pose[:, 2, 3] = 0.02 * np.arange(len(sizes))
+    return list(pose)
+
+
 def wrapper_cases():
-    """(id, class name, constructor keywords, call keywords, sizes of the three pairs): the smallest set that reaches every
-    branch of the glue around the network in inference.py.  Every case runs eagerly (graph=False) in the 32 x 64 frame: a
-    full frame, an image smaller than the frame, the full frame again."""
+    """Case(id, class name, constructor keywords, call keywords, sizes of the three pairs[, model, items]): the smallest set
+    that reaches every branch of the glue around the network in inference.py.  Every case runs eagerly (graph=False) in the
+    32 x 64 frame: a full frame, an image smaller than the frame, the full frame again -- but small, full, full for
+    KittiInferenceTemporal, whose state drops when the window changes: the last call then reprojects and fuses."""
     from dcanet_amd.geometry import StereoCalib
     sizes, hr_sizes, raw_sizes = [(32, 64), (28, 50), (32, 64)], [(64, 128), (55, 99), (64, 128)], [RAW] * 3
     dev_io, u16 = dict(device_io=True), dict(as_uint16=True)
@@ -83,4 +104,22 @@ def wrapper_cases():
             ("color/gray", "KittiInferenceColor", dict(cmap="gray"), {}, sizes),
             ("color/post_mask_min0", "KittiInferenceColor", dict(mask_min=0.0, **post), {}, sizes),
             ("color/post_mask_min05", "KittiInferenceColor", dict(mask_min=0.5, **post), {}, sizes)]
+    out = [Case(*c) for c in out]
+    # the wrappers that came after the record of the cases above (see "added_on" in the golden file)
+    device_hints = lambda rng, sz: hint_maps(rng, sz, device=True)      # noqa: E731
+    ground = dict(calib=geo["calib"], grid=(0.5, 4.0, 16.0), plane=dict(min_votes=4, min_inliers=8), segment=dict(min_run=2))
+    seq = dict(calib=StereoCalib(40.0, 0.5, 24.5, 13.5), q=0.01, meas_var=1.0, gate=4.0)
+    seq_sizes = [sizes[1], sizes[0], sizes[0]]
+    post6 = dict(median=3, speckle=(6, 1.0))
+    out += [Case("guided/numpy", "KittiInferenceGuided", {}, {}, sizes, items=hint_maps),
+            Case("guided/device", "KittiInferenceGuided", {}, {}, sizes, items=device_hints),
+            Case("guided/sgm", "KittiInferenceGuided", dict(sgm=dict(max_disp=16)), {}, sizes),
+            Case("ground/none", "KittiInferenceGround", dict(mask=None, **ground), {}, sizes),
+            Case("ground/confidence_post", "KittiInferenceGround", dict(mask="confidence", **post, **ground), {}, sizes),
+            Case("ground/rectify", "KittiInferenceGround", dict(rectify=rectify_maps(), **{**ground, "calib": None}), {}, raw_sizes),
+            Case("stixels/defaults", "KittiInferenceStixels", dict(calib=geo["calib"]), {}, sizes),
+            Case("temporal/none_guide", "KittiInferenceTemporal", dict(mask=None, guide=(10.0, 1.0), **seq), {}, seq_sizes, items=poses),
+            Case("temporal/confidence", "KittiInferenceTemporal", dict(mask="confidence", **seq), {}, seq_sizes, items=poses),
+            Case("sgm/none", "SGMInference", dict(max_disp=16, lr_tau=None), {}, sizes, model=False),
+            Case("sgm/lr_post", "SGMInference", dict(max_disp=16, lr_tau=1.0, **post6), {}, sizes, model=False)]
     return out

@@ -272,9 +272,14 @@ def test_sgm_operators_refuse_with_their_names():
 def test_sgm_inference_wrappers_host_logic():
     """SGMInference takes no model; KittiInferenceGuided(sgm=...) takes pairs alone and refuses lidar= next to it"""
     from dcanet_amd.geometry import LidarCalib, StereoCalib
-    from dcanet_amd.inference import KittiInference, KittiInferenceGuided, SGMInference
+    from dcanet_amd.inference import FramePipeline, KittiInference, KittiInferenceGuided, SGMInference
     s = SGMInference()
-    assert isinstance(s, KittiInference) and s.device_io and not s.has_uint16
+    assert isinstance(s, FramePipeline) and not isinstance(s, KittiInference) and not hasattr(s, "net") and s.device_io \
+        and not s.has_uint16
+    # the frames go through the pipeline's own stages: nothing of them is restated for the class without a network
+    for name in ("stream", "_readback", "_result", "_compute", "_call_device"):
+        assert getattr(type(s), name) is getattr(FramePipeline, name), name
+    assert type(s)._upload is not FramePipeline._upload and type(s).__mro__[1] is FramePipeline, "its _upload extends the pipeline's"
     assert (s.sgm["max_disp"], s.sgm["paths"], s.sgm["P1"], s.sgm["P2"], s.sgm["uniqueness"], s.lr_tau, s.median, s.speckle) == \
         (192, 8, 10, 120, 15, 1.0, 0, None)
     assert [(n, dt) for n, dt, _ in s._fields(30, 101, False)] == [("disp", torch.float32), ("valid", torch.float32)]
