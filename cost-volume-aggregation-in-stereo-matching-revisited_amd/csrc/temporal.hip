@@ -12,6 +12,7 @@
 //  3. resolve: a workgroup stages the HIGH words of a TP_TW x TP_TH tile with its halo in LDS, takes the window maximum along
 //              rows, then along columns (as the LiDAR resolve takes its minimum), tests the winner against it and gathers
 //              the payload from the winning source pixel; eight workgroups per CU walk the tiles.
+// dca_disp_reproject_dev: the same three launches with the matrix read from device memory (a pose estimated there, odometry.hip).
 // dca_temporal_fuse: one launch, one thread per pixel.
 // The two counters take integer atomicAdds, one per workgroup.  Kernel boundaries are the only global synchronisation; the
 // keys, written by another kernel's atomics, are read with agent-scope loads.  ~40 B per pixel over
@@ -57,9 +58,20 @@ __global__ __launch_bounds__(TP_THREADS) void tp_clear_kernel(unsigned long long
   if (count && blockIdx.x == 0 && threadIdx.x < 2) count[threadIdx.x] = 0ull;
 }
 
+// DEV: the matrix is read from device memory (another kernel wrote it: agent-scope loads), the rest of `p` is by value
+template <bool DEV>
+__device__ __forceinline__ void tp_load_g(TmProj& p, const float* g) {
+  if (DEV) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) p.g[i] = dca_coherent_loadf(g + i);
+  }
+}
+
+template <bool DEV>
 __global__ __launch_bounds__(TP_THREADS) void tp_scatter_kernel(const float* __restrict__ disp, const float* __restrict__ mask,
-                                                                float mask_min, TmProj p, unsigned long long* ws,
+                                                                float mask_min, TmProj p, const float* g, unsigned long long* ws,
                                                                 unsigned long long* __restrict__ count) {
+  tp_load_g<DEV>(p, g);
   const long hw = (long)p.H * p.W;
   const long i = (long)blockIdx.x * TP_THREADS + threadIdx.x;
   bool keep = false;
@@ -87,10 +99,12 @@ struct TpOut {
 };
 
 // persistent: a workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... and adds its count once at the end
+template <bool DEV>
 __global__ __launch_bounds__(TP_THREADS) void tp_resolve_kernel(const unsigned long long* ws, const float* __restrict__ disp,
                                                                 const float* __restrict__ var,
-                                                                const unsigned char* __restrict__ age, TmProj p, int tiles_x,
-                                                                int tiles, int rx, int ry, TpOut o) {
+                                                                const unsigned char* __restrict__ age, TmProj p, const float* g,
+                                                                int tiles_x, int tiles, int rx, int ry, TpOut o) {
+  tp_load_g<DEV>(p, g);
   __shared__ unsigned tile[TP_TH + 2 * TP_R][TP_TW + 2 * TP_R];      // the high words of the tile with its halo; 0 outside the image
   __shared__ unsigned rowmax[TP_TH + 2 * TP_R][TP_TW];               // maximum over columns c-rx .. c+rx of every halo row
   const int H = p.H, W = p.W;
@@ -204,14 +218,13 @@ __global__ __launch_bounds__(TP_THREADS) void tp_fuse_kernel(TfArgs a) {
 
 inline bool finite_f(float v) { return fabsf(v) < INFINITY; }
 
-}  // namespace
-
-extern "C" int dca_disp_reproject(const float* disp, const float* var, const unsigned char* age, const float* mask,
-                                  float mask_min, float g00, float g01, float g02, float g03, float g10, float g11, float g12,
-                                  float g13, float g20, float g21, float g22, float g23, int H, int W, float doffs,
-                                  float min_disp, float max_disp, float min_ratio, int rx, int ry, float occl_px, float q,
-                                  int hint_min_age, float* pred, float* pred_var, unsigned char* pred_age, float* hints,
-                                  long long* count, long long* workspace, hipStream_t stream) {
+// the launches of both entry points: g_dev NULL -> the matrix of `p`, else the twelve floats at g_dev
+template <bool DEV>
+int tp_reproject(const float* disp, const float* var, const unsigned char* age, const float* mask, float mask_min, const TmProj& p,
+                 const float* g_dev, int rx, int ry, float occl_px, float q, int hint_min_age, float* pred, float* pred_var,
+                 unsigned char* pred_age, float* hints, long long* count, long long* workspace, hipStream_t stream) {
+  const int H = p.H, W = p.W;
+  const float doffs = p.doffs, min_disp = p.min_disp, max_disp = p.max_disp, min_ratio = p.min_ratio;
   DCA_REQUIRE(disp && var && age);
   DCA_REQUIRE(H > 0 && W > 0 && (long)H * W < (1L << 31));
   DCA_REQUIRE(rx >= 0 && rx <= DCA_TEMPORAL_MAX_RADIUS && ry >= 0 && ry <= DCA_TEMPORAL_MAX_RADIUS);
@@ -222,8 +235,11 @@ extern "C" int dca_disp_reproject(const float* disp, const float* var, const uns
   DCA_REQUIRE(!mask || mask_min == mask_min);
   DCA_REQUIRE(pred || pred_var || pred_age || hints || count);
   DCA_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0 && ((uintptr_t)count & 7) == 0);
-  const TmProj p = {{g00, g01, g02, g03, g10, g11, g12, g13, g20, g21, g22, g23}, doffs, min_disp, max_disp, min_ratio, H, W};
-  for (int i = 0; i < 12; ++i) DCA_REQUIRE(finite_f(p.g[i]));
+  if (DEV) {
+    DCA_REQUIRE(g_dev && ((uintptr_t)g_dev & 3) == 0);
+  } else {
+    for (int i = 0; i < 12; ++i) DCA_REQUIRE(finite_f(p.g[i]));
+  }
   const TpOut o = {pred, pred_var, pred_age, hints, (unsigned long long*)count, occl_px, q, hint_min_age};
   unsigned long long* ws = (unsigned long long*)workspace;
   const long hw = (long)H * W;
@@ -232,12 +248,35 @@ extern "C" int dca_disp_reproject(const float* disp, const float* var, const uns
   const int tiles_x = cdiv(W, TP_TW);
   const long tiles = (long)tiles_x * cdiv(H, TP_TH);
   hipLaunchKernelGGL(tp_clear_kernel, dim3((unsigned)clear), dim3(TP_THREADS), 0, stream, ws, hw, o.count);
-  hipLaunchKernelGGL(tp_scatter_kernel, dim3((unsigned)per_px), dim3(TP_THREADS), 0, stream, disp, mask, mask_min, p, ws,
-                     o.count);
+  hipLaunchKernelGGL(tp_scatter_kernel<DEV>, dim3((unsigned)per_px), dim3(TP_THREADS), 0, stream, disp, mask, mask_min, p, g_dev,
+                     ws, o.count);
   const long resolve = tiles < 8L * dca_num_cus() ? tiles : 8L * dca_num_cus();      // 8 x 4 waves: what a CU holds
-  hipLaunchKernelGGL(tp_resolve_kernel, dim3((unsigned)resolve), dim3(TP_THREADS), 0, stream, (const unsigned long long*)ws, disp,
-                     var, age, p, tiles_x, (int)tiles, rx, ry, o);
+  hipLaunchKernelGGL(tp_resolve_kernel<DEV>, dim3((unsigned)resolve), dim3(TP_THREADS), 0, stream, (const unsigned long long*)ws,
+                     disp, var, age, p, g_dev, tiles_x, (int)tiles, rx, ry, o);
   return dca_launch_status();
+}
+
+}  // namespace
+
+extern "C" int dca_disp_reproject(const float* disp, const float* var, const unsigned char* age, const float* mask,
+                                  float mask_min, float g00, float g01, float g02, float g03, float g10, float g11, float g12,
+                                  float g13, float g20, float g21, float g22, float g23, int H, int W, float doffs,
+                                  float min_disp, float max_disp, float min_ratio, int rx, int ry, float occl_px, float q,
+                                  int hint_min_age, float* pred, float* pred_var, unsigned char* pred_age, float* hints,
+                                  long long* count, long long* workspace, hipStream_t stream) {
+  const TmProj p = {{g00, g01, g02, g03, g10, g11, g12, g13, g20, g21, g22, g23}, doffs, min_disp, max_disp, min_ratio, H, W};
+  return tp_reproject<false>(disp, var, age, mask, mask_min, p, nullptr, rx, ry, occl_px, q, hint_min_age, pred, pred_var, pred_age,
+                             hints, count, workspace, stream);
+}
+
+extern "C" int dca_disp_reproject_dev(const float* disp, const float* var, const unsigned char* age, const float* mask,
+                                      float mask_min, const float* g, int H, int W, float doffs, float min_disp, float max_disp,
+                                      float min_ratio, int rx, int ry, float occl_px, float q, int hint_min_age, float* pred,
+                                      float* pred_var, unsigned char* pred_age, float* hints, long long* count,
+                                      long long* workspace, hipStream_t stream) {
+  const TmProj p = {{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, doffs, min_disp, max_disp, min_ratio, H, W};
+  return tp_reproject<true>(disp, var, age, mask, mask_min, p, g, rx, ry, occl_px, q, hint_min_age, pred, pred_var, pred_age, hints,
+                            count, workspace, stream);
 }
 
 extern "C" int dca_temporal_fuse(const float* pred, const float* pred_var, const unsigned char* pred_age, const float* meas,

@@ -1484,6 +1484,164 @@ class KittiInferenceTemporal(_HintsMixin, KittiInference):
             out[k].copy_(v, non_blocking=True)
 
 
+FrameOdometry = collections.namedtuple("FrameOdometry", "disp var age pose motion count residual status")
+
+
+class _Odometry:
+    """What KittiInferenceOdometry keeps between the frames of a sequence beside _Temporal's, for windows of rows x cols: two
+    grey pyramids (the previous and the current left image, swapped per frame), the disparity pyramid of the state, the
+    estimate's record, matrices and workspace, and the world pose.  Allocated once."""
+
+    def __init__(self, device, rows, cols, levels):
+        from . import odometry as OD
+        n = OD.pyramid_len(rows, cols, levels)
+        self.grey = [torch.empty(n, device=device, dtype=torch.uint8) for _ in range(2)]
+        self.cur = 0                                         # the index of the pyramid the NEXT frame writes
+        self.dpyr = torch.empty(n, device=device, dtype=torch.float32)
+        self.rec = torch.zeros(OD.REC_LEN, device=device, dtype=torch.float64)
+        self.g = torch.zeros(24, device=device, dtype=torch.float32)
+        self.sums = torch.zeros(OD.SUMS, device=device, dtype=torch.int64)
+        self.world = torch.zeros(12, device=device, dtype=torch.float64)
+        self.window = None                                   # the window's pixels where the image is wider than it
+        self.have_rec = False                                # the record holds the motion of the frame before
+
+
+class KittiInferenceOdometry(KittiInferenceTemporal):
+    """`frame = KittiInferenceOdometry(model, calib, ...)(left_rgb, right_rgb)`: KittiInferenceTemporal for a sequence WITHOUT
+    poses: a stereo-2015 pair, a Middlebury sequence, a user's own rig.  `__call__` and `stream(pairs)`
+    take (left, right); the motion of the left camera since the frame before is estimated on the device from that frame's
+    disparity state and the two left images, and every frame does, on the compute stream, in input order, in front of the network:
+      1. `ops.grey_pyramid` of the current left image (the window of it that the state covers), from the uint8 frame in device memory;
+      2. `ops.ego_motion` against the pyramids kept from the frame before, started from the motion of the frame before
+         (init="last": constant velocity; a failed or missing one: the identity) or always from the identity (init="identity");
+      3. `ops.disp_reproject` with the matrix G the estimate left ON THE DEVICE -- the host never sees it;
+    then KittiInferenceTemporal's own work (guide= included) with that prediction, and behind the fuse
+      4. `ops.disp_pyramid` of the new state, the swap of the image pyramids, and `ops.pose_chain`:
+         T_world <- T_world T_cur_from_prev^-1 on the device.
+    A failed estimate (too few textured pixels with disparity, a singular system) leaves G as NaN: the prediction is empty, the
+    fuse starts every pixel again from the measurement, the world pose stays.  The first frame, an image of another size and
+    `reset()` start a sequence: no estimate runs, the world pose is the identity.  levels, iters, grad_min, huber, min_pixels,
+    min_ratio: `ops.ego_motion`'s (None: the named defaults of odometry.py); the window must not exceed 2^20 pixels.  A frame
+    hands out, in its single read-back (the doubles first in the record),
+      FrameOdometry(disp, var, age,            KittiInferenceTemporal's
+                    pose (4,4) float64,        the camera in the world of the sequence's first frame
+                    motion (4,4) float64,      T_cur_from_prev in metres; the identity on a first frame or after a failure
+                    count, residual, status)   of the estimate's last iteration; status 0 ok, 1 failed
+    `pose=` may still be passed per frame (`infer(left, right, pose=T)`, or a third item in `stream`): the estimate does not run,
+    the frame's disp, var and age are KittiInferenceTemporal's bit for bit for the same calls, `pose` is the given pose, `motion`
+    the relative pose to the given pose before (the identity without one), status 0 and count 0; later estimated frames chain
+    on from the given pose."""
+
+    Frame = FrameOdometry
+
+    def __init__(self, model, calib=None, *args, levels: int = None, iters: int = None, init: str = "last", grad_min: int = None,
+                 huber: float = None, min_pixels: int = None, min_ratio: float = None, **kwargs):
+        from . import odometry as OD
+        super().__init__(model, calib, *args, **kwargs)
+        name = type(self).__name__
+        if init not in ("last", "identity"):
+            raise ValueError(f"{name}: init is 'last' or 'identity', got {init!r}")
+        pick = lambda v, default: default if v is None else v      # noqa: E731
+        self.init = init
+        self.ego_kw = dict(levels=pick(levels, OD.ODOMETRY_LEVELS), iters=pick(iters, OD.ODOMETRY_ITERS),
+                           min_disp=self.reproject_kw["min_disp"], max_disp=self.reproject_kw["max_disp"],
+                           min_ratio=pick(min_ratio, OD.ODOMETRY_MIN_RATIO), grad_min=pick(grad_min, OD.ODOMETRY_GRAD_MIN),
+                           huber=pick(huber, OD.ODOMETRY_HUBER), min_pixels=pick(min_pixels, OD.ODOMETRY_MIN_PIXELS))
+        levels = OD._levels(name, ValueError, 1 << OD.MAX_LEVELS, 1 << OD.MAX_LEVELS, self.ego_kw["levels"], None)
+        res = OD.ego_scalars(name, ValueError, 1 << (levels - 1), 1 << (levels - 1), self.calib, **self.ego_kw)   # the ranges, up front
+        self.ego_kw["levels"], self.ego_kw["iters"] = res[0], res[1]
+        self._osets = {}             # (rows, cols) -> _Odometry
+        self._okey = None            # (h, w, src_y0, rows, cols) of the frame before; None: no sequence runs
+        self._given = None           # the pose given with the frame before (pose=), or None
+
+    def reset(self):
+        super().reset()
+        self._okey = self._given = None
+
+    def __call__(self, left_rgb, right_rgb, pose=None, as_uint16: bool = False):
+        return super().__call__(left_rgb, right_rgb, pose, as_uint16)
+
+    def _fields(self, rows, cols, as_uint16):
+        from .odometry import FRAME_LEN
+        return [("odo", torch.float64, (FRAME_LEN,))] + super()._fields(rows, cols, as_uint16)
+
+    def _upload(self, s, left_rgb, right_rgb, copy, pose=None):
+        """host, in input order: what this frame is -- a first frame, an estimated one, or one with a given pose"""
+        from . import odometry as OD
+        from .geometry import _pose44, relative_pose
+        name = type(self).__name__
+        if pose is not None:
+            pose = _pose44(pose, name)
+        hw = np.shape(left_rgb)[:2] if self.rectify is None else tuple(self.rectify.dst_hw)
+        if len(hw) == 2:                                     # (anything else: the parent's refusal)
+            _, _, rows, cols = self._place(*hw)
+            if rows * cols > OD.MAX_PIXELS:
+                raise ValueError(f"{name}: the window of {rows} x {cols} pixels exceeds the estimate's {OD.MAX_PIXELS}")
+            OD._levels(name, ValueError, rows, cols, self.ego_kw["levels"], None)
+        super()._upload(s, left_rgb, right_rgb, copy, pose)
+        f = s.frame
+        key = (f.h, f.w, f.src_y0, f.rows, f.cols)
+        running = self._okey == key
+        if pose is not None:
+            motion = relative_pose(self._given, pose) if running and self._given is not None else np.eye(4)
+            s.odo = ("given", np.concatenate([pose.reshape(-1), motion.reshape(-1), [0.0, 0.0, 0.0]]))
+        else:
+            s.odo = ("estimate" if running else "first", None)
+        self._okey, self._given = key, pose
+
+    def _oset(self, s):
+        key = (s.frame.rows, s.frame.cols)
+        if key not in self._osets:
+            self._osets[key] = _Odometry(s.device, *key, self.ego_kw["levels"])
+        return self._osets[key]
+
+    def _window_calib(self, s):
+        """the window's row 0 is image row src_y0: the principal point moves up by as much"""
+        c, y0 = self.calib, s.frame.src_y0
+        return c if y0 == 0 else type(c)(c.f, c.baseline, c.cx, c.cy - y0, c.doffs)
+
+    def _net_pair(self, s, left, right, h, w):
+        """current stream, in front of the network: the pyramid of this image, the estimate, then the parent's prediction"""
+        from . import ops
+        f, o = s.frame, self._oset(s)
+        img = left[f.src_y0:f.src_y0 + f.rows, :f.cols]
+        if not img.is_contiguous():                          # an image wider than the frame: the window's pixels, packed
+            if o.window is None or o.window.shape != img.shape:
+                o.window = torch.empty(img.shape, device=s.device, dtype=torch.uint8)
+            o.window.copy_(img)
+            img = o.window
+        ops.grey_pyramid(img, self.ego_kw["levels"], out=o.grey[o.cur])
+        if s.odo[0] == "estimate":
+            ops.ego_motion(o.grey[1 - o.cur], o.grey[o.cur], o.dpyr, (f.rows, f.cols), self._window_calib(s),
+                           init=o.rec if self.init == "last" and o.have_rec else None, out={"rec": o.rec, "g": o.g},
+                           workspace=o.sums, **self.ego_kw)
+            s.item = o.g[:12].view(3, 4)                     # the parent hands it to `ops.disp_reproject`, which reads it on the device
+        return super()._net_pair(s, left, right, h, w)
+
+    def _export(self, s, maps, out):
+        """current stream, behind the fuse: the pyramid of the new state, the swap, the world pose into the record"""
+        from . import ops
+        super()._export(s, maps, out)
+        o = self._oset(s)
+        ops.disp_pyramid(self._set(s).state["disp"], self.ego_kw["levels"], self.ego_kw["min_disp"], out=o.dpyr)
+        o.cur = 1 - o.cur
+        if s.odo[0] == "given":
+            # through the slot's pinned record (the host has taken the slot's previous frame out of it): no pageable copy
+            s.pin["odo"].copy_(torch.from_numpy(s.odo[1]))
+            out["odo"].copy_(s.pin["odo"], non_blocking=True)
+            o.world.copy_(out["odo"][:12], non_blocking=True)
+        else:
+            ops.pose_chain(o.rec if s.odo[0] == "estimate" else None, o.world, out=out["odo"])
+        o.have_rec = s.odo[0] == "estimate"
+
+    def _result(self, s):
+        s.done.synchronize()
+        out = {name: v.numpy().copy() for name, v in s.pin.items()}
+        odo = out["odo"]
+        return FrameOdometry(out["disp"], out["var"], out["age"], odo[:16].reshape(4, 4), odo[16:32].reshape(4, 4), int(odo[32]),
+                             float(odo[33]), int(odo[34]))
+
+
 class KittiInferenceColor(_StageMixin, KittiInference):
     """`disp, rgb = KittiInferenceColor(model, cmap="kitti", max_disp=None, mask=None | "confidence" | "lr", ...)(left_rgb,
     right_rgb)`: KittiInference with device I/O (required: the picture is made where the disparity lies) followed by one

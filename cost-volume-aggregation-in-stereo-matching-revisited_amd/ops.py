@@ -2207,3 +2207,6 @@ from .sgm import SGM_OUTPUTS, sgm_workspace, sgm_census, sgm_disparity  # noqa: 
 # ... and those of temporal stereo (temporal.py)
 from .temporal import (  # noqa: E402,F401
     TEMPORAL_MAX_RADIUS, TEMPORAL_REPROJECT_OUTPUTS, TEMPORAL_FUSE_OUTPUTS, temporal_workspace, disp_reproject, temporal_fuse)
+# ... and those of stereo visual odometry (odometry.py)
+from .odometry import (  # noqa: E402,F401
+    ODOMETRY_MAX_LEVELS, ODOMETRY_REC_LEN, ODOMETRY_SUMS, grey_pyramid, disp_pyramid, ego_motion, pose_chain)

@@ -77,19 +77,21 @@ def _doffs(name, err, calib, doffs):
         raise err(f"{name}: calib must be a geometry.StereoCalib and doffs a number") from None
 
 
-def reproject_scalars(name, err, H, W, G, doffs, min_disp, max_disp, min_ratio, occl, q, hint_min_age):
+def reproject_scalars(name, err, H, W, G, doffs, min_disp, max_disp, min_ratio, occl, q, hint_min_age, nan_ok=False):
     """The scalar arguments of dca_disp_reproject, checked as its launcher checks them (on the float32 values it is handed) ->
     (g: 12 floats, doffs, min_disp, max_disp, min_ratio, rx, ry, occl_px, q, hint_min_age) with the floats already rounded to
-    float32; raises `err` otherwise."""
+    float32; raises `err` otherwise.  G None: a matrix on the device, which nobody can check here (g is None then); nan_ok: a
+    matrix that is NaN in all twelve entries (a failed estimate's) is let through: it keeps no source."""
     if H <= 0 or W <= 0 or H * W >= 1 << 31:
         raise err(f"{name}: the state must be a non-empty (H,W) map with H * W below 2^31, got {H} x {W}")
     try:
         with np.errstate(over="ignore"):
-            g = np.asarray(G, np.float64).astype(np.float32)
+            g = None if G is None else np.asarray(G, np.float64).astype(np.float32)
     except (TypeError, ValueError):
         raise err(f"{name}: G must be a (3,4) array of numbers") from None
-    if g.shape != (3, 4) or not np.isfinite(g).all():
-        raise err(f"{name}: G must be a finite (3,4) matrix (`temporal.reproject_matrix`), got shape {g.shape}")
+    if g is not None and (g.shape != (3, 4) or not (np.isfinite(g).all() or (nan_ok and np.isnan(g).all()))):
+        raise err(f"{name}: G must be a finite (3,4) matrix (`temporal.reproject_matrix`){', or all NaN' if nan_ok else ''}, got "
+                  f"shape {g.shape}")
     try:
         rx, ry, occl_px = int(occl[0]), int(occl[1]), float(np.float32(occl[2]))
         if len(occl) != 3 or rx != occl[0] or ry != occl[1]:
@@ -111,7 +113,8 @@ def reproject_scalars(name, err, H, W, G, doffs, min_disp, max_disp, min_ratio, 
         raise err(f"{name}: doffs >= 0 and 0 <= min_disp <= max_disp, all finite in float32, got {doffs}, {min_disp} and {max_disp}")
     if not whole or not 0 <= hint_min_age <= 255:
         raise err(f"{name}: hint_min_age is a whole number in [0, 255], got {hint_min_age}")
-    return [float(v) for v in g.reshape(-1)], doffs, min_disp, max_disp, min_ratio, rx, ry, occl_px, q, hint_min_age
+    return (None if g is None else [float(v) for v in g.reshape(-1)]), doffs, min_disp, max_disp, min_ratio, rx, ry, occl_px, q, \
+        hint_min_age
 
 
 def fuse_scalars(name, err, meas_var, min_disp, gate, var_max):
@@ -186,7 +189,9 @@ def disp_reproject_host(state, G, calib=None, doffs=None, max_disp=TEMPORAL_MAX_
     with `np.maximum.at` on the 64-bit keys as the scatter: the state {"disp","var","age"} of the previous frame warped by
     G = `reproject_matrix(calib, T_cur_from_prev)` -> a dict with the keys of `outputs` (default all of REPROJECT_OUTPUTS):
     pred, var float32 (H,W), age uint8 (H,W), hints float32 (H,W), count int64 (2,) = (visible targets, kept sources), and
-    "keys": the workspace as the kernels leave it, uint64 (H,W).  Equal to `ops.disp_reproject` bit for bit."""
+    "keys": the workspace as the kernels leave it, uint64 (H,W).  Equal to `ops.disp_reproject` bit for bit.  A G that is all
+    NaN -- what a failed `odometry.ego_motion_host` hands out -- is taken as `ops.disp_reproject` takes it from the device: every
+    comparison of the keep test fails, nothing is kept, the prediction is empty."""
     name = "disp_reproject_host"
     names = REPROJECT_OUTPUTS if outputs is None else tuple(outputs)
     if not names or any(k not in REPROJECT_OUTPUTS for k in names):
@@ -194,7 +199,8 @@ def disp_reproject_host(state, G, calib=None, doffs=None, max_disp=TEMPORAL_MAX_
     d, var, age = _state_host(name, state)
     H, W = d.shape
     g, doffs, min_disp, max_disp, min_ratio, rx, ry, occl_px, q, hint_min_age = reproject_scalars(
-        name, ValueError, H, W, G, _doffs(name, ValueError, calib, doffs), min_disp, max_disp, min_ratio, occl, q, hint_min_age)
+        name, ValueError, H, W, G, _doffs(name, ValueError, calib, doffs), min_disp, max_disp, min_ratio, occl, q, hint_min_age,
+        nan_ok=True)
     f32 = np.float32
     keep, target, dn, z = project_host(d, g, doffs, min_disp, max_disp, min_ratio)
     keep &= _pass_host(name, mask, d.shape, mask_min)
@@ -301,8 +307,9 @@ def temporal_fuse_host(pred, meas, meas_var=TEMPORAL_MEAS_VAR, window=None, mask
 # The operators on the device (csrc/temporal.hip), by the conventions of frame_ops.py: arguments are validated once, here, with
 # its helpers; a refusal names the operator and launches nothing; a tensor that is not on a ROCm device is an error; no launch
 # synchronises; with `out` and `workspace` passed in nothing is allocated either.  ops.py re-exports them.
-# The matrix goes to the kernels BY VALUE: a launch captured into a hipGraph would keep the pose it was captured with, so these
-# operators are launched eagerly, like every operator around the graphed hot path.
+# A host matrix goes to the kernels BY VALUE: a launch captured into a hipGraph would keep the pose it was captured with, so these
+# operators are launched eagerly, like every operator around the graphed hot path.  A matrix that is already on the device
+# (`odometry.ego_motion`) is read there by the same kernels (dca_disp_reproject_dev) and never comes back to the host.
 # ------------------------------------------------------------------------------------------------
 TEMPORAL_MAX_RADIUS = _C["DCA_TEMPORAL_MAX_RADIUS"]
 TEMPORAL_REPROJECT_OUTPUTS = REPROJECT_OUTPUTS
@@ -331,7 +338,9 @@ def disp_reproject(state, G, calib=None, doffs=None, max_disp=TEMPORAL_MAX_DISP,
     """The previous frame's state warped by the known ego-motion into the current left image, three launches (definitions:
     include/dca_hip.h, dca_disp_reproject; `temporal.disp_reproject_host` is the numpy restatement, equal bit for bit).
     state: {"disp": float32, "var": float32 (px^2), "age": uint8}, (H,W) each on the device, +0.0 = nothing.  G: the (3,4)
-    matrix of `temporal.reproject_matrix(calib, T_cur_from_prev)`, on the host.  calib (a geometry.StereoCalib) or doffs: the
+    matrix of `temporal.reproject_matrix(calib, T_cur_from_prev)`, on the host -- or a float32 (3,4) tensor on the DEVICE, what
+    `ops.ego_motion` estimates: it goes to dca_disp_reproject_dev, is read by the kernels and never by the host, so it cannot be
+    validated; a NaN in it (a failed estimate) keeps no source and leaves an empty prediction and count = (0, 0).  calib (a geometry.StereoCalib) or doffs: the
     disparity offset.  A source pixel is kept with a finite d >= min_disp, mask >= mask_min, a depth ratio z >= min_ratio, a
     target inside the image and a new disparity in [min_disp, max_disp); the nearest surface of a target wins (64-bit integer
     fetch_max of its den' bits and the source index: the same bits for every order of arrival); occl = (rx, ry, occl_px) drops a
@@ -343,7 +352,8 @@ def disp_reproject(state, G, calib=None, doffs=None, max_disp=TEMPORAL_MAX_DISP,
       hints  float32 (H,W)   pred where age >= hint_min_age, else +0.0: the hint map of `hints_to_quarter`
       count  int64   (2,)    visible targets, kept sources
     out: a dict of buffers for some or all of them (none may be a buffer of the state); workspace: `temporal_workspace(H, W, ...)`.
-    With both given nothing is allocated and the host never waits.  NOT for hipGraph capture: the matrix is passed by value."""
+    With both given nothing is allocated and the host never waits.  NOT for hipGraph capture: a host matrix is passed by value,
+    and capture with a device matrix is untested."""
     name = "disp_reproject"
     try:
         d, var, age = (state[k] for k in STATE_KEYS)
@@ -359,12 +369,16 @@ def disp_reproject(state, G, calib=None, doffs=None, max_disp=TEMPORAL_MAX_DISP,
     if mask is not None:
         _req_dev(mask, name, "the mask", torch.float32, (H, W), like=d)
     mask_min = _mask_min(name, mask_min, mask is not None)
+    g_dev = None
+    if isinstance(G, torch.Tensor) and G.is_cuda:
+        g_dev = _req_dev(G, name, "a device G", torch.float32, (3, 4), like=d)
     g, doffs, min_disp, max_disp, min_ratio, rx, ry, occl_px, q, hint_min_age = reproject_scalars(
-        name, RuntimeError, H, W, G, _doffs(name, RuntimeError, calib, doffs), min_disp, max_disp, min_ratio, occl, q, hint_min_age)
+        name, RuntimeError, H, W, None if g_dev is not None else G, _doffs(name, RuntimeError, calib, doffs), min_disp, max_disp,
+        min_ratio, occl, q, hint_min_age)
     if outputs is not None and not tuple(outputs):
         raise RuntimeError(f"{name}: outputs must name at least one of {REPROJECT_OUTPUTS}")
     res = _out_dict(name, _REPROJECT_KINDS, (), outputs, out, lambda k: (2,) if k == "count" else (H, W), d)
-    if any(_overlaps(o, s) for o in res.values() for s in (d, var, age) + (() if mask is None else (mask,))):
+    if any(_overlaps(o, s) for o in res.values() for s in (d, var, age) + tuple(t for t in (mask, g_dev) if t is not None)):
         raise RuntimeError(f"{name}: an output must not be a buffer of the state or the mask (the operator is not in place)")
     if workspace is None:
         workspace = temporal_workspace(H, W, d.device)
@@ -372,6 +386,12 @@ def disp_reproject(state, G, calib=None, doffs=None, max_disp=TEMPORAL_MAX_DISP,
     if workspace.numel() < H * W:
         raise RuntimeError(f"{name}: workspace must hold at least {H * W} int64 (`temporal_workspace`), got {workspace.numel()}")
     with torch.cuda.device_of(d):
+        if g_dev is not None:
+            _chk(_L().dca_disp_reproject_dev(_ptr(d), _ptr(var), _ptr(age), _ptr(mask), mask_min, _ptr(g_dev), H, W, doffs, min_disp,
+                                             max_disp, min_ratio, rx, ry, occl_px, q, hint_min_age,
+                                             *(_ptr(res.get(k)) for k in REPROJECT_OUTPUTS), _ptr(workspace), _stream()),
+                 "dca_disp_reproject_dev")
+            return res
         _chk(_L().dca_disp_reproject(_ptr(d), _ptr(var), _ptr(age), _ptr(mask), mask_min, *g, H, W, doffs, min_disp, max_disp,
                                      min_ratio, rx, ry, occl_px, q, hint_min_age, *(_ptr(res.get(k)) for k in REPROJECT_OUTPUTS),
                                      _ptr(workspace), _stream()), "dca_disp_reproject")

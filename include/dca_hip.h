@@ -1256,6 +1256,17 @@ int dca_temporal_fuse(const float* pred, const float* pred_var, const unsigned c
                       const float* mask, const float* meas_var_map, float meas_var, float* disp, float* var, unsigned char* age,
                       float* innov, int Hc, int Wc, int y0, int rows, int cols, float min_disp, float mask_min, float gate2,
                       float var_max, hipStream_t stream);
+/* dca_disp_reproject_dev: dca_disp_reproject with the twelve floats of G read from DEVICE memory (g: 12 fp32, row-major 3x4,
+ * 4-byte aligned), so that a pose estimated on the device (dca_ego_motion) is never read back in the middle of a frame.  The same
+ * kernels, the same arithmetic, the same other arguments and refusals.  (Capture into a hipGraph is untested.)  The launcher
+ * CANNOT validate a matrix it does not see.  With a NaN in it every float comparison of the keep test fails: no source is
+ * kept, the prediction is empty (+0.0 / 0 everywhere), count = (0, 0), and dca_temporal_fuse then starts every pixel again
+ * from the measurement -- a failed estimate (dca_ego_motion writes G as NaN) resets the sequence on the device.  Refused
+ * besides: NULL or misaligned g. */
+int dca_disp_reproject_dev(const float* disp, const float* var, const unsigned char* age, const float* mask, float mask_min,
+                           const float* g, int H, int W, float doffs, float min_disp, float max_disp, float min_ratio, int rx,
+                           int ry, float occl_px, float q, int hint_min_age, float* pred, float* pred_var,
+                           unsigned char* pred_age, float* hints, long long* count, long long* workspace, hipStream_t stream);
 
 /* ---- semi-global matching on a census cost (sgm.hip, sgm_math.h; Hirschmueller 2008, Zabih & Woodfill
  * 1994): a disparity source that needs no weights.  Inference only, no counterpart in the reference.  dcanet_amd/sgm.py holds
@@ -1321,6 +1332,92 @@ int dca_sgm_census(const unsigned char* left, const unsigned char* right, unsign
 int dca_sgm_disparity(const unsigned char* left, const unsigned char* right, void* workspace, float* disp, float* valid,
                       int* cost, float* disp_right, float* disp_right_mirrored, int H, int W, int C, int max_disp, int paths,
                       int P1, int P2, int uniqueness, int min_disp, hipStream_t stream);
+
+/* ---- stereo visual odometry (odometry.hip, odometry_math.h; Comport et al. 2007, Steinbruecker et al.
+ * 2011, Kerl et al. 2013): the motion of the left camera between two frames, the pose dca_disp_reproject needs, from the
+ * previous frame's disparity and the grey images of both.  Inference only, no counterpart in the reference.  dcanet_amd/odometry.py
+ * holds the numpy restatement; every output is bitwise defined and independent of the order of execution.
+ *
+ * Pyramids.  Level l of an H x W map is (H >> l) x (W >> l) (odd sizes drop the last row or column); a pyramid of `levels`
+ * levels is ONE dense buffer of dca_pyramid_len(H, W, levels) elements, level 0 first (-1 for levels outside
+ * [1, DCA_ODO_MAX_LEVELS], a coarsest level without a pixel or H W >= 2^31).
+ * dca_grey_pyramid: rgb (H,W,C) uint8 interleaved, C = 3 or 4 -> uint8; level 0 is (R + 2 G + B + 2) >> 2, each further level
+ * the 2x2 area mean (a + b + c + d + 2) >> 2 of the level above.  One launch per level.
+ * dca_disp_pyramid: disp (H,W) fp32 -> fp32; level 0 is a copy, each further level the LARGEST valid value of the 2x2 block
+ * (finite and >= min_disp at that level: the nearest surface), times 0.5f, plus 0.0f (so a -0.0, valid at min_disp = 0,
+ * leaves as +0.0 whichever zero the maximum kept); +0.0 where none is valid.  One launch per level.
+ * Refused: NULL pointers, C not 3 or 4, levels as above, H W >= 2^29, min_disp negative or not finite, out == disp.
+ *
+ * dca_ego_motion.  prev, cur: the grey pyramids of the previous and the current left image; disp: the disparity pyramid of
+ * the previous frame; f, baseline, cx, cy, doffs: the calibration.  The camera of level l, in fp64 and then rounded to fp32:
+ * f_l = f / 2^l, cx_l = (cx + 0.5) / 2^l - 0.5 (cy likewise), doffs_l = doffs / 2^l; max_disp_l = max_disp / 2^l; min_disp,
+ * min_ratio, grad_min and the Huber radius are the same at every level.  The estimate is T = (R | tau), the pose of the
+ * previous camera in the current one with the translation in BASELINES, held in fp64 in the record.  Levels run coarse to
+ * fine, `iters` Gauss-Newton iterations each; the count is fixed and nothing is read back.  One iteration is two launches.
+ *
+ * Sums.  Per source pixel (u, v), 1 <= u <= W_l - 2, 1 <= v <= H_l - 2, of the previous level image Ip, with d its disparity and
+ * G_l = (1/f_l) [ K_l R A_l | K_l tau ] (fp64 in the written order of temporal.reproject_matrix, rounded to fp32 once; exactly
+ * [I | 0] for the identity), in fp32 with every operation rounded on its own and IEEE division:
+ *   valid:    d finite && min_disp <= d < max_disp_l;  den = d + doffs_l
+ *             gx = Ip(u+1,v) - Ip(u-1,v);  gy = Ip(u,v+1) - Ip(u,v-1);  |gx| + |gy| >= grad_min
+ *   warp:     x = ((g00 u + g01 v) + g02) + g03 den  (y, z likewise);  z >= min_ratio
+ *   position: px = floorf((x / z) 16 + 0.5f);  py likewise;  0 <= px < 16 (W_l - 1) and 0 <= py < 16 (H_l - 1), compared in
+ *             float: the whole bilinear footprint x0 .. x0 + 1, y0 .. y0 + 1 lies in the current image, x0 = px >> 4, fx = px & 15
+ *   residual: r = (16-fy) ((16-fx) I00 + fx I01) + fy ((16-fx) I10 + fx I11) - (Ip(u,v) << 8)     an exact integer, 1/256 grey level
+ *   Jacobian: a = u - cx_l;  b = v - cy_l;  af = a / f_l;  bf = b / f_l
+ *             J0 = gx den;  J1 = gy den;  J2 = gx (-(af den)) + gy (-(bf den));  J3 = gx (-(af b)) + gy (-(f_l + bf b))
+ *             J4 = gx (f_l + af a) + gy (af b);  J5 = gx (-b) + gy a          (inverse-compositional: the gradient of Ip)
+ *   quantise: q_i = (int)rintf(J_i 2^e_i);  e_i = 17 - k_i with 510 B_i = m 2^k_i, m in [0.5, 1), in fp64, where B_i bounds
+ *             |Ju_i|, |Jv_i| over the level:  A = max(|cx_l|, |W_l - 1 - cx_l|), Bv likewise, Dn = max_disp_l + doffs_l,
+ *             B = (Dn, Dn, max(A, Bv) Dn / f_l, max(A Bv / f_l, f_l + Bv Bv / f_l), max(f_l + A A / f_l, A Bv / f_l), max(A, Bv))
+ *   weight:   k = rint(huber 256);  w = 64 if |r| <= k else (64 k) / |r|, an integer division
+ * and DCA_ODO_SUMS = 29 int64 sums over the pixels that pass: the 21 upper entries w q_i q_j (i <= j, row-major), the six
+ * w q_i r, w r r and the count.  |q_i| < 2^18, |r| < 2^16, w <= 2^6: every term is below 2^42 and H W <= 2^20 pixels cannot
+ * overflow a sum.  Per-lane registers, a cross-lane reduction, LDS across the waves, then ONE agent-scope relaxed INTEGER
+ * atomicAdd per (workgroup, sum); at most one workgroup per CU walks the pixels.  No floating-point atomic.
+ *
+ * Solve, one thread, fp64, only + - * / in ONE written order (odometry_math.h): A_ij = S_ij 2^(-e_i - e_j) with the diagonal
+ * times 1 + 2^-10, c_i = S_ir 2^(-e_i - 7) (r's 2^-8 and the 2 of the central difference); LDL^T and two substitutions give
+ * xi = (tau', omega); R' = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a) with a = omega / 2 (Cayley: no sin / cos, whose last
+ * bits differ between libraries);  R <- R R'^T, tau <- tau - R tau'  (T <- T [R' | tau']^-1).  It writes the record, G of
+ * level 0 and G_l of the next iteration's level, and clears the sums.  With count < min_pixels or a pivot that is not
+ * positive it sets status = 1 (failed) and writes both G as NaN; every later launch of the call returns at once.
+ *
+ * rec: DCA_ODO_REC_LEN = 24 doubles: [0..11] T_cur_from_prev (3,4) row-major with the translation in METRES (tau baseline),
+ * [12..14] tau, [15] the count and [16] the mean of w r^2 (w in (0,1], grey levels squared) of the last iteration that ran,
+ * [17] status 0 / 1, [18] iterations run, the rest 0.  On failure T keeps the last estimate.
+ * g: 24 fp32: G (3,4) of level 0 -- the argument of dca_disp_reproject_dev -- then G_l of the next iteration (scratch).
+ * sums: 29 int64 of scratch.  sums_out, or NULL: (levels iters, 29) int64, the sums of every iteration in the order they
+ * ran (a debug output; 0 for iterations after a failure).  All of them may hold garbage: the init launch writes them.
+ * Start: init_rec, a DEVICE record of an earlier call (R and tau are taken from it; the identity if its status is failed; it may
+ * be rec itself), or with init_rec NULL the host pose t00 .. t23 (3,4), translation in metres (the identity: 1 0 0 0 0 1 ...).
+ * 1 + 2 levels iters launches on the stream; nothing is allocated, nothing waits.
+ * Refused: NULL prev / cur / disp / rec / g / sums, levels as above, H W > 2^20, iters outside [1, DCA_ODO_MAX_ITERS], a
+ * calibration that is not finite or f, baseline <= 0 or doffs < 0, min_disp negative, max_disp <= min_disp, min_ratio <= 0
+ * (or any of them not finite), grad_min outside [0, 510], rint(huber 256) outside [1, 65280], min_pixels < 6, a host pose
+ * that is not finite, misaligned rec / g / sums / sums_out.
+ *
+ * dca_pose_chain: the world pose of a sequence kept on the device, one launch, one thread.  world: 12 doubles, the (3,4) pose of
+ * the current camera in the world (camera coordinates -> world coordinates, as KITTI's poses are).  rec NULL: a sequence
+ * starts, world = the identity.  Otherwise, if the record's status is 0, world <- world T^-1 with T = T_cur_from_prev of the
+ * record and T^-1 = (R^T | -R^T t), in ONE written order in fp64 (om_chain); a failed record leaves world as it is.
+ * out: DCA_ODO_FRAME_LEN = 35 doubles: [0..15] the world pose (4,4), [16..31] the motion T (4,4; the identity when a sequence
+ * starts or the estimate failed), [32] count, [33] residual, [34] status.  Refused: NULL world or out, misaligned pointers. */
+#define DCA_ODO_MAX_LEVELS 8
+#define DCA_ODO_MAX_ITERS 64
+#define DCA_ODO_SUMS 29
+#define DCA_ODO_REC_LEN 24
+#define DCA_ODO_FRAME_LEN 35
+long dca_pyramid_len(int H, int W, int levels);
+int dca_grey_pyramid(const unsigned char* rgb, int H, int W, int C, int levels, unsigned char* out, hipStream_t stream);
+int dca_disp_pyramid(const float* disp, int H, int W, int levels, float min_disp, float* out, hipStream_t stream);
+int dca_ego_motion(const unsigned char* prev, const unsigned char* cur, const float* disp, int H, int W, int levels, int iters,
+                   double f, double baseline, double cx, double cy, double doffs, float min_disp, float max_disp,
+                   float min_ratio, int grad_min, float huber, int min_pixels, const double* init_rec, double t00, double t01,
+                   double t02, double t03, double t10, double t11, double t12, double t13, double t20, double t21, double t22,
+                   double t23, double* rec, float* g, long long* sums, long long* sums_out, hipStream_t stream);
+
+int dca_pose_chain(const double* rec, double* world, double* out, hipStream_t stream);
 
 #ifdef __cplusplus
 }
